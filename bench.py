@@ -14,6 +14,12 @@ instead).  The timed region contains exactly one host synchronisation: the closi
 
 `--workload cfg4` (5 M triangles as texel primitives, 1296x968, 40 classes) and `--workload cfg5` (20 M triangles,
 4096x2160, 150 classes) run the other single-GPU BASELINE configs through the same code and print the same JSON.
+
+A plain run does only what the headline needs: set up, warm up, ONE timed region of exactly K steps, the JSON line.  `--full` adds
+everything else: the region repeated (`--repeats`, default 7, 25 for K <= 40; `value` is then the median region), the roofline of the
+dominant kernel (serialised leg, `--pmc` counter passes), the host-path and foreign-image legs and the CPU baseline.
+`--dump-outputs DIR`: after the timed steps, what the last timed region fused -- the `get()` rows a caller receives, a fixed sample of
+rows where the whole result would exceed the budget -- goes to DIR/*.npy (float32 / float64); the inputs depend on the arguments only.
 """
 import argparse
 import ctypes
@@ -296,6 +302,20 @@ def foreign_images(renderer, P, cams, probs, W, H, C, T_mean, device, views=8):
             "what": "add(device copy of a render, device probs), one call per view, %d views, host-timed" % views}
 
 
+DUMP_BYTES = 32 << 20      # --dump-outputs: at most this many bytes of fused rows (cfg2's whole result is 76 MB)
+
+
+def dump_outputs(out_dir, fused, first_row):
+    """--dump-outputs: the float32 rows of a get() result -- all of them if they fit in DUMP_BYTES, else a sorted sample drawn with a
+    fixed seed, the same for every run of the same shape -- as DIR/fused.npy, and their global row indices (float64) as DIR/fused_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, c = fused.shape
+    keep = max(1, DUMP_BYTES // (4 * max(c, 1)))
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    np.save(os.path.join(out_dir, "fused.npy"), np.ascontiguousarray(fused[rows], dtype=np.float32))
+    np.save(os.path.join(out_dir, "fused_rows.npy"), (rows + first_row).astype(np.float64))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` with N > 1 and no launcher (no RANK in the environment): this process becomes the launcher -- N
     ranks of this very command line, one per GPU (RANK = LOCAL_RANK = device, WORLD_SIZE = N, rendezvous on 127.0.0.1), exactly the
@@ -369,12 +389,18 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--workload", default="cfg2", choices=sorted(synth.CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: repeated regions, roofline (serialised leg, PMC passes), "
+                         "host-path and foreign-image legs, CPU baseline.  Off: one timed region of --steps steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the fused distribution of the last timed region (get(): float32 rows, a fixed "
+                         "sample of at most 32 MiB) and the row indices (float64) to DIR/fused.npy and DIR/fused_rows.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", action="store_true", help="also for workloads other than cfg2 (slow: the oracle at that size)")
     ap.add_argument("--no-host-path", action="store_true")
     ap.add_argument("--pmc", action="store_true", default=None,
                     help="measure roofline.traffic in this run: two extra short passes of this script under rocprofv3 --pmc (about a minute). "
-                         "Default: on for a one-GPU run of a triangle-renderer workload when rocprofv3 is on PATH")
+                         "Default: on for a one-GPU --full run of a triangle-renderer workload when rocprofv3 is on PATH")
     ap.add_argument("--no-pmc", dest="pmc", action="store_false", help="take roofline.traffic from the committed PMC summary instead")
     ap.add_argument("--views-per-call", type=int, default=int(os.environ.get("SMESH_BENCH_VIEWS_PER_CALL", "8")),
                     help="views handed to the library per call (fuse_views; 1 = one fuse_view call per view)")
@@ -391,7 +417,8 @@ def main():
                     help="one kernel at a time on the GPU throughout (what rounds 1-4 timed); the roofline comes from the timed region itself")
     ap.add_argument("--repeats", type=int, default=int(os.environ["SMESH_BENCH_REPEATS"]) if os.environ.get("SMESH_BENCH_REPEATS") else None,
                     help="the K-step timed region (barrier, K steps, exchange, barrier) is run this many times; `value` is the MEDIAN region, "
-                         "config.repeats / value_min / value_max / region_ms say how far the others were.  Default: 7, and 25 for K <= 40")
+                         "config.repeats / value_min / value_max / region_ms say how far the others were.  Default: 1; with --full 7, "
+                         "and 25 for K <= 40")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be at least 1")
@@ -407,6 +434,8 @@ def main():
     pipelined = bool(gp.value)
     if args.steps is None:
         args.steps = {"cfg5": 24}.get(args.workload, 200)
+    if args.repeats is None and not args.full:
+        args.repeats = 1      # a plain run: --steps is the number of timed steps
     if args.repeats is None:
         # A region of twenty cfg2 views is 1.3 ms of device time, and the first eight or so such regions of a process run 4 - 6 % slower than the
         # rest (1.37 -> 1.305 ms; profiles/r06_steps20_regions.txt): with seven regions the median sat on that ramp.  Short regions are repeated more
@@ -416,9 +445,11 @@ def main():
     if args.warmup is None:
         args.warmup = {"cfg5": 4}.get(args.workload, 10)
 
+    if args.pmc and not args.full:
+        raise SystemExit("bench: --pmc measures the roofline, which only a --full run reports")
     if args.pmc is None:
         import shutil
-        args.pmc = (args.gpus == 1 and "RANK" not in os.environ and shutil.which("rocprofv3") is not None
+        args.pmc = (args.full and args.gpus == 1 and "RANK" not in os.environ and shutil.which("rocprofv3") is not None
                     and not os.environ.get("SMESH_BENCH_NO_PMC"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -484,16 +515,18 @@ def main():
     probs = [bufs[i % nbuf] for i in range(total_views)]
     _lib.synchronize(device)
 
-    # distinct primitives touched per view (T of the algorithmic-bytes formula) and visible pixels, on a sample of views
-    sample = list(range(args.warmup, total_views, max(1, args.steps // 8)))[:8]
-    T, NV = [], []
-    for i in sample:
-        idx, _ = renderer.render(cams[i])
-        u = np.unique(np.asarray(idx))
-        T.append(int((u < P).sum()))
-        NV.append(int((np.asarray(idx) < P).sum()))
-        del idx
-    T_mean, NV_mean = float(np.mean(T)), float(np.mean(NV))
+    # distinct primitives touched per view (T of the algorithmic-bytes formula) and visible pixels, on a sample of views (--full: roofline)
+    T_mean, NV_mean = 0.0, 0.0
+    if args.full:
+        sample = list(range(args.warmup, total_views, max(1, args.steps // 8)))[:8]
+        T, NV = [], []
+        for i in sample:
+            idx, _ = renderer.render(cams[i])
+            u = np.unique(np.asarray(idx))
+            T.append(int((u < P).sum()))
+            NV.append(int((np.asarray(idx) < P).sum()))
+            del idx
+        T_mean, NV_mean = float(np.mean(T)), float(np.mean(NV))
 
     def barrier():
         """every rank's queued work has finished and every rank has arrived (one host synchronisation)"""
@@ -605,8 +638,9 @@ def main():
     # With the group pipeline the rasteriser of the next group runs BESIDE a fusion launch, so a launch's duration inside the timed
     # regions is not the kernel's own: the regions run without event pairs around the fusion launches (which also spares them the
     # ~6 us of stream idle time per event), and the kernel is timed in a serialised leg afterwards (below).
-    serial_leg = pipelined and not launched and prof_mask != 0
-    region_mask = (prof_mask & ~(1 << _lib.PROF_FUSE_SCATTER)) if serial_leg else prof_mask
+    # A plain run reports no roofline: its regions bracket no fusion launch either.
+    serial_leg = args.full and pipelined and not launched and prof_mask != 0
+    region_mask = (prof_mask & ~(1 << _lib.PROF_FUSE_SCATTER)) if (serial_leg or not args.full) else prof_mask
     # HIP events on the library's stream around every 8th launch of the dominant kernel when every view is its own call (an event
     # pair costs ~4 us of stream time = 5 % of a cfg2 view); with fuse_views around the fusion launches of every THIRD group, the
     # first one included (measured: the two events of a group keep the stream idle for 2 x 6 us = 2 % of a group of eight cfg2
@@ -667,6 +701,19 @@ def main():
     else:
         exchange_ms_max = flat_max[-1]
 
+    # ---- what the timed path computed: the last region's fused rows as a caller of get() receives them (untimed) ----
+    bench_dump = os.environ.get("SMESH_BENCH_DUMP") if exchange == "allreduce" else None
+    if rank == 0 and (args.dump_outputs or bench_dump):
+        lo, hi = (0, P) if exchange == "allreduce" else owned
+        fused = agg.get() if exchange == "allreduce" else agg.get_rows(lo, hi)
+        if bench_dump:
+            # (tests: a sample of the fused rows, to be compared with a single-process fusion of the same views)
+            sample_rows = np.unique(np.linspace(0, max(P - 1, 0), 4096).astype(np.int64))
+            np.savez(bench_dump, rows=sample_rows, fused=fused[sample_rows])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, fused, lo)
+        del fused
+
     # ---- the serialised leg: the fusion kernel's own duration (roofline), one kernel at a time on the GPU ----
     leg_views = 0
     if serial_leg:
@@ -684,19 +731,16 @@ def main():
         _lib.check(_lib.lib().smesh_set_option(b"group_pipeline", 1))
         # (the accumulator now holds the leg's views too: the result checks below only count annotated primitives)
 
-    t1 = time.perf_counter()
-    fused = agg.get() if exchange == "allreduce" else agg.get_rows(*owned)
-    get_first_ms = 1e3 * (time.perf_counter() - t1)     # (the first get() of the process also allocates its page-locked landing buffer)
-    annotated = int((fused.sum(axis=1) > 0.9).sum())
-    if os.environ.get("SMESH_BENCH_DUMP") and rank == 0 and exchange == "allreduce":
-        # (tests: a sample of the fused rows, to be compared with a single-process fusion of the same views)
-        sample_rows = np.unique(np.linspace(0, max(P - 1, 0), 4096).astype(np.int64))
-        np.savez(os.environ["SMESH_BENCH_DUMP"], rows=sample_rows, fused=fused[sample_rows])
-    del fused
-    t1 = time.perf_counter()
-    fused = agg.get() if exchange == "allreduce" else agg.get_rows(*owned)     # ... which the next result of that size recycles
-    get_ms = 1e3 * (time.perf_counter() - t1)
-    del fused
+    if args.full:
+        t1 = time.perf_counter()
+        fused = agg.get() if exchange == "allreduce" else agg.get_rows(*owned)
+        get_first_ms = 1e3 * (time.perf_counter() - t1)     # (the first get() of the process also allocates its page-locked landing buffer)
+        annotated = int((fused.sum(axis=1) > 0.9).sum())
+        del fused
+        t1 = time.perf_counter()
+        fused = agg.get() if exchange == "allreduce" else agg.get_rows(*owned)     # ... which the next result of that size recycles
+        get_ms = 1e3 * (time.perf_counter() - t1)
+        del fused
     nranks_reported = world
     if comm is not None:
         rk, nr = ctypes.c_int(), ctypes.c_int()
@@ -707,85 +751,9 @@ def main():
     if nranks_reported != args.gpus:
         raise SystemExit("bench: --gpus %d but the process group spans %d rank(s)" % (args.gpus, nranks_reported))
 
-    fuse_kernel = _lib.last_fuse_kernel()
-    k_ms, k_regions, k_launches, k_views = prof_read(device, _lib.PROF_FUSE_SCATTER)
-    entered = ctypes.c_uint64(0)       # regions of the dominant kernel the timed loop went through, bracketed or not
-    _lib.check(_lib.lib().smesh_profile_regions(device, _lib.PROF_FUSE_SCATTER, ctypes.byref(entered)))
-    k_entered = int(entered.value)
-    hist_ms, hist_regions, _, _ = prof_read(device, _lib.PROF_FUSE_HIST)
-    raster_ms, raster_regions, _, _ = prof_read(device, _lib.PROF_RASTER)
-
     if rank == 0:
         N = W * H
         F = len(mesh.faces)
-        # idx + probs + accumulator read-modify-write of the T primitives touched
-        bytes_per_view = 4 * N + 4 * N * C + 8 * C * T_mean
-        # what a triangle-order kernel has to move at least: the index plane, the class vectors of the VISIBLE pixels only,
-        # the per-triangle records, the touched accumulator rows both ways
-        needed_per_view = 4 * N + 4 * C * NV_mean + 16 * F + 8 * C * T_mean
-        t_launch = k_ms * 1e-3 / max(k_launches, 1)                  # average duration of one launch of the dominant kernel
-        views_per_launch = k_views / max(k_launches, 1)
-        # which launches those were: a call of n views is cut into launches of 8 / 4 / 2 / 1 views, largest first (the library's
-        # rule, smesh_fuse_views); cross-checked against the library's own counters
-        mix = {}
-        if B > 1 and prof_mask and not ranged:
-            cap = 8     # smesh_aggregator_max_fused_views (Mul with 41 .. 48 classes: 2 -- not a bench workload)
-            cap = min(cap, int(os.environ.get("SMESH_FUSE_VIEWS", "8")))
-            # the calls whose fusion launches were bracketed: those of the serialised leg, or of every timed region
-            first_call, end_call, times = ((args.warmup, args.warmup + leg_views, 1) if serial_leg else (args.warmup, total_views, args.repeats))
-            for call, i in enumerate(range(first_call, end_call, B)):
-                if call % prof_every:
-                    continue           # (not one of the bracketed calls)
-                left = min(i + B, end_call) - i
-                while left:
-                    nv = 1
-                    while nv * 2 <= min(cap, left):
-                        nv *= 2
-                    mix[nv] = mix.get(nv, 0) + times
-                    left -= nv
-            if sum(mix.values()) != k_launches or sum(k * v for k, v in mix.items()) != k_views:
-                mix = {}
-        timed = k_launches > 0 and k_ms > 0     # (N > 1 with the exchange under the fusion: the fusion launches are not bracketed)
-        achieved = bytes_per_view * k_views / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        achieved_needed = needed_per_view * k_views / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        # roofline.traffic: HBM bytes per launch from the PMC counters, for the instance that fuses the most views per launch;
-        # frac_traffic: the counter bytes of ALL the timed launches (each instance's own bytes x how often it was timed; an
-        # instance the counter passes did not see: the largest one's bytes scaled by views) over the time those launches took --
-        # round 4 divided the eight-view instance's bytes by the mean duration of an {8, 8, 4} mix
-        traffic, traffic_source, traffic_by_nv, traffic_timed = None, None, None, None
-        vpl_int = int(round(views_per_launch)) if views_per_launch else 1
-        if args.pmc and world == 1:
-            try:
-                sub_steps, sub_warm = (args.steps, args.warmup) if args.steps <= 40 else (16, 8)
-                traffic_by_nv, traffic_source = pmc_traffic(args.workload, fuse_kernel, sub_steps, sub_warm)
-            except Exception as e:
-                traffic_by_nv, traffic_source = None, "pmc passes failed: %s" % str(e)[:160]
-        if traffic_by_nv:
-            top = max(traffic_by_nv)                      # views per launch of the largest instance (0: a run-time-view kernel)
-            traffic = traffic_by_nv[top]
-            if top == 0 or not mix:
-                per_view = traffic / max(views_per_launch if top == 0 else top, 1)
-                traffic_timed = per_view * k_views
-            else:
-                traffic_timed = sum(cnt * (traffic_by_nv[nv] if nv in traffic_by_nv else traffic * nv / top) for nv, cnt in mix.items())
-        if traffic is None:
-            # not measured in this run: the committed PMC summary of an earlier round, for the kernel instance that ran
-            note = traffic_source
-            tpath = os.path.join(ROOT, "profiles", "fusion_traffic.json")
-            if os.path.exists(tpath):
-                try:
-                    tkey = "%s:%s" % (args.workload, fuse_kernel) + ("_x8" if views_per_launch > 6 else "_pair" if views_per_launch > 1.5 else "")
-                    entry = json.load(open(tpath)).get(tkey)
-                    if entry:
-                        traffic = entry.get("hbm_bytes_per_launch")
-                        vpl_entry = 8 if tkey.endswith("_x8") else 2 if tkey.endswith("_pair") else 1
-                        traffic_timed = traffic / vpl_entry * k_views
-                        traffic_source = ("profiles/fusion_traffic.json [%s] (committed PMC passes of an EARLIER round; `--pmc` measures it in the run%s)"
-                                          % (tkey, "; this run's passes: " + note if note else ""))
-                except Exception:
-                    traffic = None
-            if traffic is None and note:
-                traffic_source = note
         out = {
             "metric": ("views/sec fused (1080p, 19 classes, 1M-tri mesh)" if args.workload == "cfg2" else
                        "views/sec fused (%s: %dx%d, %d classes, %d triangles%s)" % (args.workload, W, H, C, F,
@@ -823,57 +791,133 @@ def main():
                        "rank0": {"compute_ms": round(compute_ms, 3), "exchange_ms": round(exchange_ms, 3),
                                  "exchange_exposed_ms": round(exposed_ms, 3)},
                        "timed_region_ms": round(1e3 * dt, 3),
-                       "host_syncs_in_timed_region": 1 if (comm is not None or dist is None) else 3 + (parts if ranged else 1),
-                       "get_ms": round(get_ms, 2), "get_first_ms": round(get_first_ms, 2), "annotated_primitives": annotated},
+                       "host_syncs_in_timed_region": 1 if (comm is not None or dist is None) else 3 + (parts if ranged else 1)},
+        }
+        if args.full:
+            out["config"].update({"get_ms": round(get_ms, 2), "get_first_ms": round(get_first_ms, 2), "annotated_primitives": annotated})
+            fuse_kernel = _lib.last_fuse_kernel()
+            k_ms, k_regions, k_launches, k_views = prof_read(device, _lib.PROF_FUSE_SCATTER)
+            entered = ctypes.c_uint64(0)       # regions of the dominant kernel the timed loop went through, bracketed or not
+            _lib.check(_lib.lib().smesh_profile_regions(device, _lib.PROF_FUSE_SCATTER, ctypes.byref(entered)))
+            k_entered = int(entered.value)
+            hist_ms, hist_regions, _, _ = prof_read(device, _lib.PROF_FUSE_HIST)
+            raster_ms, raster_regions, _, _ = prof_read(device, _lib.PROF_RASTER)
+            # idx + probs + accumulator read-modify-write of the T primitives touched
+            bytes_per_view = 4 * N + 4 * N * C + 8 * C * T_mean
+            # what a triangle-order kernel has to move at least: the index plane, the class vectors of the VISIBLE pixels only,
+            # the per-triangle records, the touched accumulator rows both ways
+            needed_per_view = 4 * N + 4 * C * NV_mean + 16 * F + 8 * C * T_mean
+            t_launch = k_ms * 1e-3 / max(k_launches, 1)                  # average duration of one launch of the dominant kernel
+            views_per_launch = k_views / max(k_launches, 1)
+            # which launches those were: a call of n views is cut into launches of 8 / 4 / 2 / 1 views, largest first (the library's
+            # rule, smesh_fuse_views); cross-checked against the library's own counters
+            mix = {}
+            if B > 1 and prof_mask and not ranged:
+                cap = 8     # smesh_aggregator_max_fused_views (Mul with 41 .. 48 classes: 2 -- not a bench workload)
+                cap = min(cap, int(os.environ.get("SMESH_FUSE_VIEWS", "8")))
+                # the calls whose fusion launches were bracketed: those of the serialised leg, or of every timed region
+                first_call, end_call, times = ((args.warmup, args.warmup + leg_views, 1) if serial_leg else (args.warmup, total_views, args.repeats))
+                for call, i in enumerate(range(first_call, end_call, B)):
+                    if call % prof_every:
+                        continue           # (not one of the bracketed calls)
+                    left = min(i + B, end_call) - i
+                    while left:
+                        nv = 1
+                        while nv * 2 <= min(cap, left):
+                            nv *= 2
+                        mix[nv] = mix.get(nv, 0) + times
+                        left -= nv
+                if sum(mix.values()) != k_launches or sum(k * v for k, v in mix.items()) != k_views:
+                    mix = {}
+            timed = k_launches > 0 and k_ms > 0     # (N > 1 with the exchange under the fusion: the fusion launches are not bracketed)
+            achieved = bytes_per_view * k_views / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            achieved_needed = needed_per_view * k_views / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            # roofline.traffic: HBM bytes per launch from the PMC counters, for the instance that fuses the most views per launch;
+            # frac_traffic: the counter bytes of ALL the timed launches (each instance's own bytes x how often it was timed; an
+            # instance the counter passes did not see: the largest one's bytes scaled by views) over the time those launches took --
+            # round 4 divided the eight-view instance's bytes by the mean duration of an {8, 8, 4} mix
+            traffic, traffic_source, traffic_by_nv, traffic_timed = None, None, None, None
+            vpl_int = int(round(views_per_launch)) if views_per_launch else 1
+            if args.pmc and world == 1:
+                try:
+                    sub_steps, sub_warm = (args.steps, args.warmup) if args.steps <= 40 else (16, 8)
+                    traffic_by_nv, traffic_source = pmc_traffic(args.workload, fuse_kernel, sub_steps, sub_warm)
+                except Exception as e:
+                    traffic_by_nv, traffic_source = None, "pmc passes failed: %s" % str(e)[:160]
+            if traffic_by_nv:
+                top = max(traffic_by_nv)                      # views per launch of the largest instance (0: a run-time-view kernel)
+                traffic = traffic_by_nv[top]
+                if top == 0 or not mix:
+                    per_view = traffic / max(views_per_launch if top == 0 else top, 1)
+                    traffic_timed = per_view * k_views
+                else:
+                    traffic_timed = sum(cnt * (traffic_by_nv[nv] if nv in traffic_by_nv else traffic * nv / top) for nv, cnt in mix.items())
+            if traffic is None:
+                # not measured in this run: the committed PMC summary of an earlier round, for the kernel instance that ran
+                note = traffic_source
+                tpath = os.path.join(ROOT, "profiles", "fusion_traffic.json")
+                if os.path.exists(tpath):
+                    try:
+                        tkey = "%s:%s" % (args.workload, fuse_kernel) + ("_x8" if views_per_launch > 6 else "_pair" if views_per_launch > 1.5 else "")
+                        entry = json.load(open(tpath)).get(tkey)
+                        if entry:
+                            traffic = entry.get("hbm_bytes_per_launch")
+                            vpl_entry = 8 if tkey.endswith("_x8") else 2 if tkey.endswith("_pair") else 1
+                            traffic_timed = traffic / vpl_entry * k_views
+                            traffic_source = ("profiles/fusion_traffic.json [%s] (committed PMC passes of an EARLIER round; `--pmc` measures it in the run%s)"
+                                              % (tkey, "; this run's passes: " + note if note else ""))
+                    except Exception:
+                        traffic = None
+                if traffic is None and note:
+                    traffic_source = note
             # frac_needed first: the fraction by the bytes the kernel HAS to move (visible pixels' class vectors, records, touched
             # rows once per launch); `frac` is SURVEY.md 8(d)'s formula, which also charges the class vectors of background
             # pixels and a row round trip per view that the kernel does not perform -- it flatters
-            "roofline": {"frac_needed": round(achieved_needed / HBM_PEAK_GBS, 4) if timed else None,
-                         "kernel": KERNEL_NOTES.get(fuse_kernel, fuse_kernel),
-                         "note": (("N > 1 with the exchange under the fusion: the fusion launches are not bracketed with events here (an event pair "
-                                   "around each of exchange_parts x groups launches costs what the overlap saves); the kernel's roofline is the "
-                                   "N = 1 line's") if ranged else
-                                  ("kernel durations from a SERIALISED leg of this run (group pipeline off, %d views right after the timed regions, every "
-                                   "fusion launch bracketed with HIP events on the library stream): in the timed regions the rasteriser of the next group "
-                                   "runs beside each fusion launch, whose duration is then not the kernel's own.  us_per_view <= ms_per_step still holds."
-                                   % leg_views) if serial_leg else None),
-                         "bound": "hbm",
-                         "achieved": round(achieved, 1) if timed else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4) if timed else None, "traffic": traffic, "traffic_source": traffic_source,
-                         "frac_traffic": (round(traffic_timed / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if (traffic_timed and timed) else None),
-                         "traffic_by_views_per_launch": ({str(k): v for k, v in sorted(traffic_by_nv.items(), reverse=True)} if traffic_by_nv else None),
-                         "algorithmic_bytes_per_view": int(bytes_per_view),
-                         "algorithmic_bytes_per_launch": int(bytes_per_view * views_per_launch),
-                         "needed_bytes_per_view": int(needed_per_view),
-                         "views_per_launch": (int(views_per_launch) if views_per_launch == int(views_per_launch)
-                                              else round(views_per_launch, 3)),
-                         "launches_by_views": {str(k): v for k, v in sorted(mix.items(), reverse=True)} or None,
-                         "avg_launch_us": round(1e6 * t_launch, 2) if timed else None,
-                         "us_per_view": round(1e3 * k_ms / max(k_views, 1), 3) if timed else None,
-                         "launches_timed": k_launches, "views_timed": k_views, "regions_timed": k_regions,
-                         "regions_in_timed_loop": k_entered,
-                         "distinct_primitives_per_view": int(T_mean), "visible_pixels_per_view": int(NV_mean),
-                         "other_kernels_us_per_view": ({"histogram+pixel_weights": round(1e3 * hist_ms / max(args.steps, 1), 2),
-                                                        "raster": round(1e3 * raster_ms / max(raster_regions, 1) / max(1, min(B, 8)), 2)}
-                                                       if hist_regions or raster_regions else None)},
-        }
-        if world == 1 and not args.no_host_path:
-            # side legs: reported beside the headline, never allowed to take it down
-            try:
-                out["host_path"] = host_path(renderer, agg, cams, W, H, C, device, views=6 if args.workload != "cfg5" else 2)
-            except Exception as e:
-                out["host_path"] = {"error": str(e)[:200]}
-            if not texels:
+            out["roofline"] = {"frac_needed": round(achieved_needed / HBM_PEAK_GBS, 4) if timed else None,
+                               "kernel": KERNEL_NOTES.get(fuse_kernel, fuse_kernel),
+                               "note": (("N > 1 with the exchange under the fusion: the fusion launches are not bracketed with events here (an event pair "
+                                         "around each of exchange_parts x groups launches costs what the overlap saves); the kernel's roofline is the "
+                                         "N = 1 line's") if ranged else
+                                        ("kernel durations from a SERIALISED leg of this run (group pipeline off, %d views right after the timed regions, every "
+                                         "fusion launch bracketed with HIP events on the library stream): in the timed regions the rasteriser of the next group "
+                                         "runs beside each fusion launch, whose duration is then not the kernel's own.  us_per_view <= ms_per_step still holds."
+                                         % leg_views) if serial_leg else None),
+                               "bound": "hbm",
+                               "achieved": round(achieved, 1) if timed else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4) if timed else None, "traffic": traffic, "traffic_source": traffic_source,
+                               "frac_traffic": (round(traffic_timed / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if (traffic_timed and timed) else None),
+                               "traffic_by_views_per_launch": ({str(k): v for k, v in sorted(traffic_by_nv.items(), reverse=True)} if traffic_by_nv else None),
+                               "algorithmic_bytes_per_view": int(bytes_per_view),
+                               "algorithmic_bytes_per_launch": int(bytes_per_view * views_per_launch),
+                               "needed_bytes_per_view": int(needed_per_view),
+                               "views_per_launch": (int(views_per_launch) if views_per_launch == int(views_per_launch)
+                                                    else round(views_per_launch, 3)),
+                               "launches_by_views": {str(k): v for k, v in sorted(mix.items(), reverse=True)} or None,
+                               "avg_launch_us": round(1e6 * t_launch, 2) if timed else None,
+                               "us_per_view": round(1e3 * k_ms / max(k_views, 1), 3) if timed else None,
+                               "launches_timed": k_launches, "views_timed": k_views, "regions_timed": k_regions,
+                               "regions_in_timed_loop": k_entered,
+                               "distinct_primitives_per_view": int(T_mean), "visible_pixels_per_view": int(NV_mean),
+                               "other_kernels_us_per_view": ({"histogram+pixel_weights": round(1e3 * hist_ms / max(args.steps, 1), 2),
+                                                              "raster": round(1e3 * raster_ms / max(raster_regions, 1) / max(1, min(B, 8)), 2)}
+                                                             if hist_regions or raster_regions else None)}
+            if world == 1 and not args.no_host_path:
+                # side legs: reported beside the headline, never allowed to take it down
                 try:
-                    out["foreign_images"] = foreign_images(renderer, P, cams, probs, W, H, C, T_mean, device,
-                                                           views=8 if args.workload != "cfg5" else 4)
+                    out["host_path"] = host_path(renderer, agg, cams, W, H, C, device, views=6 if args.workload != "cfg5" else 2)
                 except Exception as e:
-                    out["foreign_images"] = {"error": str(e)[:200]}
-        if world == 1 and ((args.workload == "cfg2" and not args.no_cpu_baseline) or args.cpu_baseline):
-            try:
-                out["cpu_baseline"] = cpu_baseline(args.workload)
-            except Exception as e:      # (the headline line is printed whatever happens to the CPU leg)
-                out["cpu_baseline"] = {"value": None, "unit": "views/s", "cores": 0, "kind": "port", "sample": "failed: " + str(e)[:200]}
+                    out["host_path"] = {"error": str(e)[:200]}
+                if not texels:
+                    try:
+                        out["foreign_images"] = foreign_images(renderer, P, cams, probs, W, H, C, T_mean, device,
+                                                               views=8 if args.workload != "cfg5" else 4)
+                    except Exception as e:
+                        out["foreign_images"] = {"error": str(e)[:200]}
+            if world == 1 and ((args.workload == "cfg2" and not args.no_cpu_baseline) or args.cpu_baseline):
+                try:
+                    out["cpu_baseline"] = cpu_baseline(args.workload)
+                except Exception as e:      # (the headline line is printed whatever happens to the CPU leg)
+                    out["cpu_baseline"] = {"value": None, "unit": "views/s", "cores": 0, "kind": "port", "sample": "failed: " + str(e)[:200]}
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

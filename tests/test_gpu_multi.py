@@ -274,7 +274,7 @@ def test_bench_under_the_drivers_launcher_world_one(variant):
         env.pop(k, None)
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "16", "--warmup", "8",
-                          "--workload", "cfg1", "--no-host-path"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                          "--workload", "cfg1", "--no-host-path", "--full"], env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')][-1]
     out = json.loads(line)
@@ -290,6 +290,58 @@ def test_bench_under_the_drivers_launcher_world_one(variant):
     assert cfg["compute_ms"] > 0 and cfg["exchange_exposed_ms"] >= 0 and cfg["exchange_ms"] >= 0
     assert cfg["compute_ms"] + cfg["exchange_exposed_ms"] <= cfg["timed_region_ms"] * 1.05
     assert out["roofline"]["regions_timed"] == 0 and out["roofline"]["note"]      # (no event pairs around the cut fusion launches: see the note)
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_what_they_fused(sm, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W`: ONE timed region of exactly K steps, the headline fields and nothing measured beside
+    them; `--dump-outputs DIR` writes the get() rows of the last region (float32, their row indices as float64), the same in two runs
+    and equal to a fusion of the same K views in this process; `--full` adds the repeated regions and the roofline."""
+    import json
+    import subprocess
+    import sys
+    from semantic_meshes_amd import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    K, W0 = 12, 4
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W0), "--workload", "cfg1"]
+
+    def run(*extra):
+        res = subprocess.run(base + list(extra), env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(lines) == 1, res.stdout[-2000:]
+        return json.loads(lines[0])
+
+    dumps = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dumps:
+        out = run("--dump-outputs", d)
+        cfg = out["config"]
+        assert out["steps"] == K and out["warmup"] == W0 and out["unit"] == "views/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert cfg["repeats"] == 1 and len(cfg["region_ms"]) == 1
+        assert abs(out["ms_per_step"] * K - cfg["timed_region_ms"]) < 2e-3
+        assert abs(out["value"] - K / (cfg["timed_region_ms"] * 1e-3)) < 0.01 * out["value"]
+        assert not {"roofline", "cpu_baseline", "host_path", "foreign_images"} & set(out)
+    got = [(np.load(os.path.join(d, "fused.npy")), np.load(os.path.join(d, "fused_rows.npy"))) for d in dumps]
+    for fused, rows in got:
+        assert fused.dtype == np.float32 and rows.dtype == np.float64 and fused.shape == (10000, 5) and rows.shape == (10000,)
+    assert np.array_equal(got[0][1], got[1][1])
+    assert_fused_close(got[1][0], got[0][0], rtol=1e-6)
+    # the same K views (views W0 .. W0 + K - 1 of a ring of K + W0) fused here
+    c = synth.CONFIGS["cfg1"]
+    mesh = synth.grid_mesh(c["a"], c["b"])
+    ring = max(c["views"], K + W0)
+    ids = list(range(W0, W0 + K))
+    agg = sm.fusion.MeshAggregator(len(mesh.faces), c["classes"])
+    agg.fuse_views(sm.render.triangles(mesh), [synth.ring_camera(k, ring, c["width"], c["height"]) for k in ids],
+                   [synth.device_probs(c["width"], c["height"], c["classes"], synth.probs_seed(1, k), 0.0, 0) for k in ids])
+    want = agg.get()[got[0][1].astype(np.int64)]
+    assert (want.sum(axis=1) > 0.5).sum() > 1000
+    assert_fused_close(got[0][0], want, rtol=1e-5)
+    full = run("--full", "--no-pmc")
+    assert full["config"]["repeats"] == 25 and len(full["config"]["region_ms"]) == 25
+    assert full["roofline"]["views_timed"] > 0 and "host_path" in full
 
 
 @pytest.mark.parametrize("C,res", [(19, (320, 240)), (19, (333, 257)), (5, (37, 29)), (40, (320, 240)), (150, (320, 240))])

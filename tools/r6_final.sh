@@ -5,26 +5,26 @@
 # with two ranks started by the script itself.  Summaries are copied into profiles/r06_* afterwards.
 root=${GRAFT_REPO_ROOT:-/root/repo}; cd $root
 out=gpurun_out/r6f_final; mkdir -p $out
-python bench.py > $out/bench.json 2> $out/bench.err
-python bench.py --steps 20 --warmup 5 > $out/bench_steps20_warmup5.json 2> $out/bench20.err
+python bench.py --full > $out/bench.json 2> $out/bench.err
+python bench.py --full --steps 20 --warmup 5 > $out/bench_steps20_warmup5.json 2> $out/bench20.err
 for mode in "" "--no-group-pipeline"; do
   tag=$([ -z "$mode" ] && echo pipelined || echo serial)
-  ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof_$tag -o bench -- python $root/bench.py --no-cpu-baseline --no-host-path --no-pmc --repeats 3 $mode > $root/$out/bench_under_rocprof_$tag.json 2> $root/$out/rocprof_$tag.err )
+  ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof_$tag -o bench -- python $root/bench.py --full --no-cpu-baseline --no-host-path --no-pmc --repeats 3 $mode > $root/$out/bench_under_rocprof_$tag.json 2> $root/$out/rocprof_$tag.err )
   find $out/prof_$tag -name "*kernel_stats.csv" -exec cp {} $out/bench_kernel_stats_$tag.csv \;
   rm -rf $out/prof_$tag
 done
 bash tools/r6_pmc_workload.sh cfg2 r6f_final/pmc_cfg2 > $out/pmc_raster_cfg2.txt 2>&1
 for w in cfg4 cfg4t cfg5; do
-  timeout 1500 python bench.py --workload $w > $out/bench_$w.json 2> $out/$w.err
-  ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof_$w -o bench -- python $root/bench.py --workload $w --no-cpu-baseline --no-host-path --no-pmc --repeats 3 --no-group-pipeline > $root/$out/bench_${w}_serial.json 2> $root/$out/${w}_serial.err )
+  timeout 1500 python bench.py --full --workload $w > $out/bench_$w.json 2> $out/$w.err
+  ( cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/prof_$w -o bench -- python $root/bench.py --full --workload $w --no-cpu-baseline --no-host-path --no-pmc --repeats 3 --no-group-pipeline > $root/$out/bench_${w}_serial.json 2> $root/$out/${w}_serial.err )
   find $out/prof_$w -name "*kernel_stats.csv" -exec cp {} $out/bench_${w}_kernel_stats.csv \;
   rm -rf $out/prof_$w
 done
 python tools/mesh_density_sweep.py 2>&1 | grep -v amdgpu.ids > $out/mesh_density_sweep.txt
 python tools/close_view_bench.py 2>&1 | grep -v amdgpu.ids > $out/close_views.txt
 python tools/two_thread_harness.py 64 2>&1 | grep -v amdgpu.ids > $out/two_thread_harness.txt
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --steps 20 --warmup 5 --no-host-path > $out/launched_world1.json 2> $out/launched.err
-SMESH_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 > $out/self_launched_world2_gloo.json 2> $out/self_launched.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-host-path > $out/launched_world1.json 2> $out/launched.err
+SMESH_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 5 > $out/self_launched_world2_gloo.json 2> $out/self_launched.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r6f_final/*.json')):

@@ -5,7 +5,7 @@ root=${GRAFT_REPO_ROOT:-/root/repo}; out=$root/gpurun_out/$tag; mkdir -p $out
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  ( cd $root && env $envs timeout 600 python bench.py --workload $w --steps 200 --warmup 10 --repeats 5 --no-cpu-baseline --no-host-path --no-pmc > $out/bench$i.json 2> $out/bench$i.err )
+  ( cd $root && env $envs timeout 600 python bench.py --full --workload $w --steps 200 --warmup 10 --repeats 5 --no-cpu-baseline --no-host-path --no-pmc > $out/bench$i.json 2> $out/bench$i.err )
   OUT=$out I=$i ENVS="$envs" python - <<'PY'
 import os, json
 out, i = os.environ['OUT'], os.environ['I']

@@ -3,7 +3,7 @@
 root=${GRAFT_REPO_ROOT:-/root/repo}; cd $root
 for v in "$@"; do
   envs=$(echo "$v" | tr ' ' '\n' | grep = | grep -v '^--' | tr '\n' ' '); flags=$(echo "$v" | tr ' ' '\n' | grep '^--' | tr '\n' ' ')
-  env $envs python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --no-pmc $flags 2>/dev/null | python -c "
+  env $envs python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-host-path --no-pmc $flags 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{\"metric\"'):
