@@ -8,7 +8,7 @@ import os
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("SMESH_LIB_PATH") or os.path.join(_HERE, "csrc", "libsmesh_hip.so")   # (SMESH_LIB_PATH: a development build, e.g. `make ABLATION=1` in a copy of csrc/)
+LIB_PATH = os.environ.get("SMESH_LIB_PATH") or os.path.join(_HERE, "csrc", "libsmesh_hip.so")   # (SMESH_LIB_PATH: a development build, e.g. a copy of csrc/ built with other flags)
 
 OK, ERR_INVALID, ERR_RUNTIME, ERR_NODEVICE = 0, 1, 2, 3
 MEM_HOST, MEM_DEVICE = 0, 1

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -98,17 +99,11 @@ struct Scratch {
 
 inline uint64_t div_up(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
-// Development ablations ("what does the kernel cost without its atomics / its stores / its class-vector loads": WRONG results)
-// exist only in builds with -DSMESH_ABLATION (make ABLATION=1, tools/*ablation*.sh).  In the product build SMESH_ABL() is the
-// constant 0 -- the branches are compiled out of the kernels -- and the SMESH_DBG / SMESH_FDBG / SMESH_RDBG / SMESH_REC_DBG
-// environment variables are not read (tests/test_abi.py looks for their names in the shared library).
-#ifdef SMESH_ABLATION
-#define SMESH_ABL(bits) (bits)
-#define SMESH_ABL_ENV(name) (getenv(name) ? atoi(getenv(name)) : 0)
-#else
-#define SMESH_ABL(bits) 0
-#define SMESH_ABL_ENV(name) 0
-#endif
+// An integer setting from the environment (atoi), `def` when the variable is unset.
+inline int env_int(const char* name, int def) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : def;
+}
 
 // Per-triangle record the rasteriser leaves for the triangle-order fusion (smesh_fuse_view):
 //   kind 1 (small): bounding box at (x0, y0) of at most 8 x 8 pixels; bit (dx * 8 + dy) of `mask` is set when
@@ -139,7 +134,6 @@ struct TriFuseArgs {
   uint32_t big_capacity;
   uint32_t tri_blocks;        // blocks 0 .. tri_blocks-1 walk the triangles, the next big_blocks the big-triangle queue, the rest (k_fuse_tri with `mid`) the lists of medium triangles
   uint32_t big_blocks;
-  int dbg;                    // development ablation (SMESH_FDBG): 1 stop after pass 1, 2 no stores, 4 no row loads, 8 no probs loads
   const uint32_t* prim_id;    // [F] primitive id of triangle f when the renderer re-ordered its triangles (null: id == f)
   // texel primitives (k_fuse_texel) only
   const uint32_t* tex_first;  // [F] first texel id of each triangle
@@ -155,8 +149,6 @@ struct TriFuseArgs {
   uint32_t blk_first;
   uint32_t f_lo, f_hi;
   uint32_t lds_pad;           // host side only: dynamic LDS of the eight-view k_fuse_tri launch (caps its workgroups per CU beside the rasteriser, fusion_multi8.hip)
-  uint32_t xcd_chunk = 0;     // k_fuse_tri_wide: nonzero = the triangle blocks are dealt to the XCDs (block b runs on XCD b % 8) in runs of xcd_chunk
-                              // consecutive blocks (an experiment knob, SMESH_WIDE_XCD); 0 = blocks in dispatch order
 };
 
 // What k_fuse_tri needs to know about ONE of the views it fuses in a launch (the per-view part of TriFuseArgs), and NV of them.

@@ -212,7 +212,7 @@ __device__ __forceinline__ void fuse_mid_entries(const TriFuseArgs& a, const Tri
         if ((c & 15) == l16) { if (c < 16) m0 = t; else if (c < 32) m1 = t; else m2 = t; }
       }
     }
-    if (on && ntot && !(SMESH_ABL(a.dbg) & 2)) {
+    if (on && ntot) {
       float* __restrict__ row = a.acc + (uint64_t)pid * C;
       if (l16 < C && m0 != 0.0f) unsafeAtomicAdd(&row[l16], m0);
       if (l16 + 16 < C && m1 != 0.0f) unsafeAtomicAdd(&row[l16 + 16], m1);

@@ -8,9 +8,9 @@
 //                                                  when the caller's layout is not already contiguous)
 //   Fusion.h:79-104 + Fusion.cu:47-49,67-69,79-82 get() functor chain               -> k_finalize_tile
 //
-// Data layout in HBM: accumulator float32[P][S] with the row stride S = C rounded up to 16 floats, so that
-// every primitive's row starts on a 64-byte boundary (C = 19 -> one 128-byte line per row); the padding
-// stays zero.  get()/get_raw() return dense [P][C].  Per-view histogram uint32[P], zero between add() calls.
+// Data layout in HBM: accumulator float32[P][C], dense rows (padding rows to whole cache lines was measured SLOWER,
+// tools/flush_replay.hip: memory-side atomics cost per line touched, and dense neighbours share lines).
+// Per-view histogram uint32[P], zero between add() calls.
 //
 // The scatter-add is HBM-bound (no MFMA): per view it must read 4*N (indices) + 4*N*C (probs) bytes and
 // read-modify-write 2*4*C*T accumulator bytes (T = distinct primitives touched).  Measured on MI355X
@@ -157,18 +157,16 @@ struct ScatterArgs {
   const float* weights;   // may be null
   const float* pw;        // per-pixel weight image from k_pixel_weights; null = every weight is 1
   uint32_t* count;        // per-view histogram; null when images_equal_weight == 0
-  float* acc;             // [P][S]
+  float* acc;             // [P][C]
   uint64_t N;
   uint32_t P;
   uint32_t C;
-  uint32_t S;             // accumulator row stride in floats
   uint32_t W, H;
   uint32_t strips_y;      // strips per image column
   uint32_t nstrips;
   uint32_t strips_per_xcd;  // ceil(nstrips / 8)
   uint32_t strips_per_wave; // scatter kernel: contiguous strips walked by one persistent wave
   int vec_ok;             // every full strip's column segments start 16-byte aligned
-  int dbg;                // development ablation switches (SMESH_DBG): 2 = no global atomics
   float iew;
 };
 
@@ -230,7 +228,6 @@ __global__ __launch_bounds__(kWave) void k_hist_strip(ScatterArgs a) {
       q = L.child[q];
     }
   }
-  if (SMESH_ABL(a.dbg) & 2) return;
   // (sorting the groups by primitive id first, as the scatter kernel does, was measured slower here:
   // 19.1 vs 15.4 us -- the network costs more than the better-coalesced 4-byte atomics save)
   if (r.root) atomicAdd(&a.count[v], n);
@@ -288,12 +285,6 @@ struct PrefetchVecs {  // float4 registers holding the next strip's probs (0 = n
 };
 
 __device__ __forceinline__ void pin(f4& v) { asm volatile("" : "+v"(v)); }
-template <bool NT>
-__device__ __forceinline__ f4 load_stream(const f4* p) {
-  // NT: streamed-once data should not displace the accumulator rows from the memory-side cache
-  if constexpr (NT) return __builtin_nontemporal_load(p);
-  else return *p;
-}
 __device__ __forceinline__ void pin(float& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void pin(uint32_t& v) { asm volatile("" : "+v"(v)); }
 
@@ -331,7 +322,7 @@ __device__ __forceinline__ uint32_t wave_sort(uint32_t key, int l) {
   return key;
 }
 
-template <int CT, int KIND, bool NT>
+template <int CT, int KIND>
 __global__ __launch_bounds__(kWave) void k_scatter_strip(ScatterArgs a) {
   constexpr int KV = PrefetchVecs<CT>::value;
   constexpr int CH = Chunk<CT>::value;
@@ -410,7 +401,7 @@ __global__ __launch_bounds__(kWave) void k_scatter_strip(ScatterArgs a) {
       // a partial (edge) strip is parked with dword loads instead; prefetch a harmless in-bounds address
       const f4* p0 = base4 + (is_fast(g0) ? strip_vec0(g0) : 0);
 #pragma unroll
-      for (int k = 0; k < KV; k++) r[k] = load_stream<NT>(p0 + (is_fast(g0) ? voff[k] : 0u));
+      for (int k = 0; k < KV; k++) r[k] = p0[is_fast(g0) ? voff[k] : 0u];
     }
     (void)g0;
   }
@@ -451,7 +442,7 @@ __global__ __launch_bounds__(kWave) void k_scatter_strip(ScatterArgs a) {
 #pragma unroll
         for (int k = 0; k < 8; k++) {
           const int q = base + l + k * kWave;
-          t8[k] = load_stream<NT>(base4 + src_index(g, q < nvec ? q : nvec - 1));
+          t8[k] = base4[src_index(g, q < nvec ? q : nvec - 1)];
         }
 #pragma unroll
         for (int k = 0; k < 8; k++) pin(t8[k]);
@@ -480,7 +471,7 @@ __global__ __launch_bounds__(kWave) void k_scatter_strip(ScatterArgs a) {
         const bool f1 = is_fast(g1);
         const f4* p1 = base4 + (f1 ? strip_vec0(g1) : 0);
 #pragma unroll
-        for (int k = 0; k < KV; k++) r[k] = load_stream<NT>(p1 + (f1 ? voff[k] : 0u));
+        for (int k = 0; k < KV; k++) r[k] = p1[f1 ? voff[k] : 0u];
       }
       v_next = a.idx[pixel_of(g1)];
       pw_next = a.pw ? a.pw[pixel_of(g1)] : 1.0f;
@@ -609,7 +600,7 @@ __global__ __launch_bounds__(kWave) void k_scatter_strip(ScatterArgs a) {
     // ---- 5. order the strip's groups by primitive id (bitonic network, key = prim << 6 | root lane):
     // neighbouring primitives then sit on neighbouring lanes and share cache lines in one atomic instruction
     {
-      const bool sortable = a.P <= (1u << 26) && !(SMESH_ABL(a.dbg) & 1);
+      const bool sortable = a.P <= (1u << 26);
       if (rr.root) F.sprim[rr.gidx] = (sortable ? (v << 6) : ((uint32_t)rr.gidx << 6)) | (uint32_t)l;   // compact the keys
       wave_sync();
       uint32_t key = l < rr.G ? F.sprim[l] : 0xFFFFFFFFu;
@@ -631,23 +622,21 @@ __global__ __launch_bounds__(kWave) void k_scatter_strip(ScatterArgs a) {
       }
       pin(v_next);
       pin(pw_next);
-      if (!(SMESH_ABL(a.dbg) & 2)) {
-        if (rows_per_pass) {
-          // lane -> (row slot, class): 64 / C sorted groups per pass, C consecutive lanes per accumulator row
-          if (f_active) {
-            for (int si = f_slot; si < rr.G; si += rows_per_pass) {
-              const float x = sp[(int)F.sorder[si] * C + f_c];
-              if (x != 0.0f) unsafeAtomicAdd(&a.acc[(uint64_t)F.sprim[si] * a.S + f_c], x);
-            }
+      if (rows_per_pass) {
+        // lane -> (row slot, class): 64 / C sorted groups per pass, C consecutive lanes per accumulator row
+        if (f_active) {
+          for (int si = f_slot; si < rr.G; si += rows_per_pass) {
+            const float x = sp[(int)F.sorder[si] * C + f_c];
+            if (x != 0.0f) unsafeAtomicAdd(&a.acc[(uint64_t)F.sprim[si] * C + f_c], x);
           }
-        } else {
-          const int total = rr.G * C;
-          for (int e = l; e < total; e += kWave) {
-            const int si = e / C;
-            const int c = e - si * C;
-            const float x = sp[(int)F.sorder[si] * C + c];
-            if (x != 0.0f) unsafeAtomicAdd(&a.acc[(uint64_t)F.sprim[si] * a.S + c], x);
-          }
+        }
+      } else {
+        const int total = rr.G * C;
+        for (int e = l; e < total; e += kWave) {
+          const int si = e / C;
+          const int c = e - si * C;
+          const float x = sp[(int)F.sorder[si] * C + c];
+          if (x != 0.0f) unsafeAtomicAdd(&a.acc[(uint64_t)F.sprim[si] * C + c], x);
         }
       }
     }
@@ -1159,12 +1148,7 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_wide(TriFuseArgs a, TriViews
   __shared__ ViewState S;
   const int l = threadIdx.x;
   const uint32_t C = a.C;
-  uint32_t blk = blockIdx.x;
-  if (a.xcd_chunk) {                   // (TriFuseArgs::xcd_chunk: runs of that many consecutive triangle blocks per XCD)
-    const uint32_t sq = blk >> 3, q = sq / a.xcd_chunk;
-    blk = (q * 8u + (blk & 7u)) * a.xcd_chunk + (sq - q * a.xcd_chunk);
-    if (blk >= a.tri_blocks) return;   // block-uniform
-  }
+  const uint32_t blk = blockIdx.x;
   const uint64_t f0 = ((uint64_t)a.blk_first + blk) * kWave;   // (blk_first: fusion by triangle range; 0 otherwise)
   const uint64_t f = f0 + l;
   const uint32_t pid = (a.prim_id && f < a.F) ? a.prim_id[f] : (uint32_t)f;   // primitive id (index image value, accumulator row)
@@ -1211,7 +1195,7 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_wide(TriFuseArgs a, TriViews
     S.hi[v][l] = (uint32_t)(win[v] >> 32);
   }
   unsigned long long vis = __ballot(any_win != 0ull);
-  if (vis == 0ull || (SMESH_ABL(a.dbg) & 1)) return;
+  if (vis == 0ull) return;
   wave_sync();
 
   // From here on the wave works on a few triangles' rows at a time; a triangle's pixel sets are read from its owner lane's LDS
@@ -1232,7 +1216,7 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_wide(TriFuseArgs a, TriViews
     }
 #pragma unroll
     for (int b = 0; b < B; b++)
-      if (t[b] >= 0 && !(SMESH_ABL(a.dbg) & 4)) load_wide<NCH>(a.acc + (uint64_t)rowid[b] * C, C, l, ac[b]);
+      if (t[b] >= 0) load_wide<NCH>(a.acc + (uint64_t)rowid[b] * C, C, l, ac[b]);
     if constexpr (KIND != SMESH_AGG_MUL) {
       // Sum / Summax: every triangle of the batch is a STREAM of pixels -- its views in order, its pixels of a view in image order --
       // and a round takes the next pixel of every stream whatever view it belongs to.  (Round 4 walked the views in lock step:
@@ -1281,7 +1265,7 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_wide(TriFuseArgs a, TriViews
           if (have[b]) {
             const uint64_t pix = pix_of(org[b], __ffsll((long long)pm[b]) - 1, Hs[b]);
             pm[b] &= pm[b] - 1ull;
-            if (!(SMESH_ABL(a.dbg) & 8)) load_wide<NCH>(pr[b] + pix * C, C, l, p[b]);
+            load_wide<NCH>(pr[b] + pix * C, C, l, p[b]);
             if (wg[b]) wt[b] = wg[b][pix];
           }
         }
@@ -1332,7 +1316,7 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_wide(TriFuseArgs a, TriViews
           if (have[b]) {
             const uint64_t pix = pix_of(org[b], __ffsll((long long)pm[b]) - 1, Hv);
             pm[b] &= pm[b] - 1ull;
-            if (!(SMESH_ABL(a.dbg) & 8)) load_wide<NCH>(probs + pix * C, C, l, p[b]);
+            load_wide<NCH>(probs + pix * C, C, l, p[b]);
             if (weights) wt[b] = weights[pix];
           }
         }
@@ -1379,7 +1363,7 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_wide(TriFuseArgs a, TriViews
     }
 #pragma unroll
     for (int b = 0; b < B; b++)
-      if (t[b] >= 0 && !(SMESH_ABL(a.dbg) & 2)) store_wide<NCH>(a.acc + (uint64_t)rowid[b] * C, C, l, ac[b]);
+      if (t[b] >= 0) store_wide<NCH>(a.acc + (uint64_t)rowid[b] * C, C, l, ac[b]);
   }
 }
 
@@ -1414,12 +1398,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(7, 8))) v
   __shared__ WideList S;
   const int l = threadIdx.x;
   const uint32_t C = a.C;
-  uint32_t blk = blockIdx.x;
-  if (a.xcd_chunk) {
-    const uint32_t sq = blk >> 3, q = sq / a.xcd_chunk;
-    blk = (q * 8u + (blk & 7u)) * a.xcd_chunk + (sq - q * a.xcd_chunk);
-    if (blk >= a.tri_blocks) return;   // block-uniform
-  }
+  const uint32_t blk = blockIdx.x;
   const uint64_t f0 = ((uint64_t)a.blk_first + blk) * kWave;
   const uint64_t f = f0 + l;
   const uint32_t pid = (a.prim_id && f < a.F) ? a.prim_id[f] : (uint32_t)f;
@@ -1475,7 +1454,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(7, 8))) v
 #pragma unroll
       for (int v = 0; v < 8; v++) cnt += (uint32_t)__popcll(win[v]);
       vis = __ballot(cnt != 0u);
-      if (vis == 0ull || (SMESH_ABL(a.dbg) & 1)) return;
+      if (vis == 0ull) return;
       inc = wave_scan_incl_u(cnt);
       exc = inc - cnt;
       wave_sync();                     // (S.view is in LDS)
@@ -1517,10 +1496,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(7, 8))) v
       const uint64_t pix = ex & 0x1FFFFFFFu;
       const float* probs = uniform_ptr(S.view[v].probs);
       const float* weights = uniform_ptr(S.view[v].weights);
-      if (!(SMESH_ABL(a.dbg) & 8)) load_wide<NCH>(probs + pix * C, C, l, p[k]);
+      load_wide<NCH>(probs + pix * C, C, l, p[k]);
       w[k] = __uint_as_float(ew) * (weights ? weights[pix] : 1.0f);
       start[k] = rid[k] != prev_issued;
-      if (start[k] && !(SMESH_ABL(a.dbg) & 4)) load_wide<NCH>(a.acc + (uint64_t)rid[k] * C, C, l, rw[k]);
+      if (start[k]) load_wide<NCH>(a.acc + (uint64_t)rid[k] * C, C, l, rw[k]);
       prev_issued = rid[k];
     };
 #pragma unroll
@@ -1532,7 +1511,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(7, 8))) v
         const uint32_t i = i0 + (uint32_t)k;
         if (i < n) {
           if (start[k]) {
-            if (cur != 0xFFFFFFFFu && !(SMESH_ABL(a.dbg) & 2)) store_wide<NCH>(a.acc + (uint64_t)cur * C, C, l, ac);
+            if (cur != 0xFFFFFFFFu) store_wide<NCH>(a.acc + (uint64_t)cur * C, C, l, ac);
             cur = rid[k];
 #pragma unroll
             for (int c = 0; c < NCH; c++) ac[c] = rw[k][c];
@@ -1542,7 +1521,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(7, 8))) v
         }
       }
     }
-    if (cur != 0xFFFFFFFFu && !(SMESH_ABL(a.dbg) & 2)) store_wide<NCH>(a.acc + (uint64_t)cur * C, C, l, ac);
+    if (cur != 0xFFFFFFFFu) store_wide<NCH>(a.acc + (uint64_t)cur * C, C, l, ac);
     if (e1 >= 64 || (vis >> e1) == 0ull) break;
     base += n;
     s = e1;
@@ -1914,13 +1893,13 @@ __global__ void k_scatter_flat(ScatterArgs a, const float* __restrict__ wpix, co
   const float w = wpix[i];
   if (w == 0.0f) return;
   if (KIND == SMESH_AGG_SUMMAX && amax[i] != c) return;
-  unsafeAtomicAdd(&a.acc[(uint64_t)a.idx[i] * a.S + c], contribution<KIND>(a.probs[e], w));
+  unsafeAtomicAdd(&a.acc[(uint64_t)a.idx[i] * a.C + c], contribution<KIND>(a.probs[e], w));
 }
 
 // Mul on the generic path: one float64 atomic per (pixel, class) into the aggregator's scratch rows (all zero between calls), then
 // every row that received terms folds them into its (hi, lo) pair (k_fold_rows) -- "Mul state", fuse_tri.inc.hpp.  Float32 atomics on
 // the hi plane (rounds 1-3) missed 1e-5 on get() by two orders of magnitude; this path is what is left when the image records do
-// not apply (padded rows, SMESH_ADD_RECORDS=0, SMESH_FUSE=strip), so it is sized for exactness, not speed.
+// not apply (SMESH_ADD_RECORDS=0, SMESH_FUSE=strip), so it is sized for exactness, not speed.
 __global__ void k_scatter_flat_mul(ScatterArgs a, const float* __restrict__ wpix, double* __restrict__ acc_d) {
   const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.N * a.C) return;
@@ -1931,15 +1910,15 @@ __global__ void k_scatter_flat_mul(ScatterArgs a, const float* __restrict__ wpix
   unsafeAtomicAdd(&acc_d[(uint64_t)a.idx[i] * a.C + c], (double)contribution<SMESH_AGG_MUL>(a.probs[e], w));
 }
 __global__ void k_fold_rows(float* __restrict__ acc, float* __restrict__ acc_lo, double* __restrict__ acc_d, const uint32_t* __restrict__ count,
-                            uint64_t P, uint32_t C, uint32_t S) {
+                            uint64_t P, uint32_t C) {
   const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= P || (count && count[v] == 0u)) return;     // (count: this view's histogram, when there is one)
   double* drow = acc_d + v * C;
   bool any = false;
   for (uint32_t c = 0; c < C; c++) any = any || drow[c] != 0.0;
   if (!any) return;
-  float* hi = acc + v * S;
-  float* lo = acc_lo + v * S;
+  float* hi = acc + v * C;
+  float* lo = acc_lo + v * C;
   float m = -INFINITY;
   for (uint32_t c = 0; c < C; c++) { const float h = hi[c]; if (h > m && h < INFINITY) m = h; }
   const float centre = m > -INFINITY ? m : 0.0f;
@@ -1952,7 +1931,6 @@ __global__ void k_fold_rows(float* __restrict__ acc, float* __restrict__ acc_lo,
 
 // ------------------------------------------------------------------------------------------------
 // get(): load -> [Mul: / max element] -> L1 normalise -> NaN/Inf -> 0   (Fusion.h:79-104)
-// Reads padded rows [P][S], writes dense [P][C].
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float nan_inf_to_zero(float v) { return (isnan(v) || isinf(v)) ? 0.0f : v; }
 
@@ -1974,29 +1952,23 @@ __device__ __forceinline__ void finalize_row(float* row, int C) {
 // thread-per-row kernel with uncoalesced accesses: 0.19 TB/s at C = 300.)
 template <int KIND>
 __global__ __launch_bounds__(256) void k_finalize_tile(const float* __restrict__ acc, const float* __restrict__ acc_lo, float* __restrict__ out,
-                                                       uint64_t P, int C, int S, int TP) {
+                                                       uint64_t P, int C, int TP) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* sp = reinterpret_cast<float*>(smem);
   const int t = threadIdx.x;
   const uint64_t r0 = (uint64_t)blockIdx.x * TP;
   const int nrows = (int)((P - r0) < (uint64_t)TP ? (P - r0) : (uint64_t)TP);
   const int nfl = nrows * C;
-  const float* __restrict__ src = acc + r0 * (uint64_t)S;
+  const float* __restrict__ src = acc + r0 * (uint64_t)C;
   float* __restrict__ dst = out + r0 * (uint64_t)C;
-  if (S == C) {        // dense rows (the layout in use): the tile is one contiguous run, no division per float
-    if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-      const float4* src4 = reinterpret_cast<const float4*>(src);
-      float4* sp4w = reinterpret_cast<float4*>(sp);
-      for (int e = t; e < (nfl >> 2); e += 256) sp4w[e] = src4[e];
-      for (int e = (nfl & ~3) + t; e < nfl; e += 256) sp[e] = src[e];
-    } else {
-      for (int e = t; e < nfl; e += 256) sp[e] = src[e];
-    }
+  // the tile is one contiguous run of dense rows
+  if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    const float4* src4 = reinterpret_cast<const float4*>(src);
+    float4* sp4w = reinterpret_cast<float4*>(sp);
+    for (int e = t; e < (nfl >> 2); e += 256) sp4w[e] = src4[e];
+    for (int e = (nfl & ~3) + t; e < nfl; e += 256) sp[e] = src[e];
   } else {
-    for (int e = t; e < nfl; e += 256) {
-      const int rr = e / C, c = e - rr * C;
-      sp[e] = src[(uint64_t)rr * S + c];
-    }
+    for (int e = t; e < nfl; e += 256) sp[e] = src[e];
   }
   if (KIND == SMESH_AGG_MUL && acc_lo) {
     // Mul ("Mul state", fuse_tri.inc.hpp): a row is hi + lo.  The lo tile sits behind the hi tile in LDS; the row's thread centres
@@ -2004,11 +1976,8 @@ __global__ __launch_bounds__(256) void k_finalize_tile(const float* __restrict__
     // plane -- without writing the state back (get() used to run that kernel over the whole accumulator first: a thread per row,
     // 0.11-0.15 TB/s).
     float* sl = sp + (((size_t)TP * C + 3) & ~(size_t)3);
-    const float* __restrict__ lsrc = acc_lo + r0 * (uint64_t)S;
-    for (int e = t; e < nfl; e += 256) {
-      const int rr = S == C ? 0 : e / C;
-      sl[e] = S == C ? lsrc[e] : lsrc[(uint64_t)rr * S + (e - rr * C)];
-    }
+    const float* __restrict__ lsrc = acc_lo + r0 * (uint64_t)C;
+    for (int e = t; e < nfl; e += 256) sl[e] = lsrc[e];
     __syncthreads();
     if (t < nrows) {
       float* hi = sp + t * C;
@@ -2033,10 +2002,10 @@ __global__ __launch_bounds__(256) void k_finalize_tile(const float* __restrict__
 }
 
 template <int KIND>
-__global__ void k_finalize_rows(const float* __restrict__ acc, float* __restrict__ out, uint64_t P, int C, int S) {
+__global__ void k_finalize_rows(const float* __restrict__ acc, float* __restrict__ out, uint64_t P, int C) {
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
-  const float* src = acc + p * S;
+  const float* src = acc + p * C;
   float* dst = out + p * C;
   for (int c = 0; c < C; c++) dst[c] = src[c];
   finalize_row<KIND>(dst, C);
@@ -2070,13 +2039,6 @@ __global__ __launch_bounds__(256) void k_gather_annotations(const uint32_t* __re
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-// Dense rows: padding rows to whole cache lines was measured SLOWER (tools/flush_replay.hip: memory-side
-// atomics cost per line touched, and dense neighbours share lines), so the stride is C.
-inline uint32_t row_stride(uint32_t C) {
-  static const int pad = getenv("SMESH_ROW_PAD") ? atoi(getenv("SMESH_ROW_PAD")) : 0;   // experiment knob
-  return pad > 1 ? (uint32_t)((C + pad - 1) / pad * pad) : C;
-}
-
 // the strip path keeps 64 pixel rows of C floats in LDS (<= 64 KiB without opting into more: C <= 250)
 
 inline size_t strip_lds_bytes(uint32_t C) {
@@ -2111,9 +2073,7 @@ int launch_strip(const ScatterArgs& a0, int num_cus, hipStream_t st) {
   ScatterArgs a = a0;
   const size_t lds = strip_lds_bytes(a.C);
   // persistent waves: as many as the LDS lets a CU hold (at most 32), each walking a contiguous strip range
-  static const int env_wpc = getenv("SMESH_WAVES_PER_CU") ? atoi(getenv("SMESH_WAVES_PER_CU")) : 0;
   int waves_per_cu = (int)std::min<size_t>(16, (160 * 1024) / lds);   // measured best on cfg2 (8 strips per wave)
-  if (env_wpc > 0) waves_per_cu = env_wpc;
   if (waves_per_cu < 1) waves_per_cu = 1;
   uint32_t waves = (uint32_t)num_cus * (uint32_t)waves_per_cu;
   waves = (waves + 7u) & ~7u;
@@ -2123,18 +2083,11 @@ int launch_strip(const ScatterArgs& a0, int num_cus, hipStream_t st) {
   const dim3 grid(waves), block(kWave);
   // class counts of the benchmark configs get compile-time loops; everything else runs the same
   // kernel with a run-time C (the reference needs a rebuild with -DCLASSES_NUMS for each count)
-  if (SMESH_ABL(a.dbg) & 32) {
-    switch (a.C) {
-      case 19: hipLaunchKernelGGL((k_scatter_strip<19, KIND, true>), grid, block, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_scatter_strip<0, KIND, true>), grid, block, lds, st, a); break;
-    }
-  } else {
-    switch (a.C) {
-      case 5:  hipLaunchKernelGGL((k_scatter_strip<5, KIND, false>), grid, block, lds, st, a); break;
-      case 19: hipLaunchKernelGGL((k_scatter_strip<19, KIND, false>), grid, block, lds, st, a); break;
-      case 40: hipLaunchKernelGGL((k_scatter_strip<40, KIND, false>), grid, block, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_scatter_strip<0, KIND, false>), grid, block, lds, st, a); break;
-    }
+  switch (a.C) {
+    case 5:  hipLaunchKernelGGL((k_scatter_strip<5, KIND>), grid, block, lds, st, a); break;
+    case 19: hipLaunchKernelGGL((k_scatter_strip<19, KIND>), grid, block, lds, st, a); break;
+    case 40: hipLaunchKernelGGL((k_scatter_strip<40, KIND>), grid, block, lds, st, a); break;
+    default: hipLaunchKernelGGL((k_scatter_strip<0, KIND>), grid, block, lds, st, a); break;
   }
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
@@ -2153,11 +2106,11 @@ int launch_hist(const ScatterArgs& a, hipStream_t st) {
 // hi plane alone -- what leaves the library as "the raw accumulator").  Runs ahead of the fusion kernels that only know the hi
 // plane, in get(), and before the raw accumulator is read or all-reduced.
 namespace {
-__global__ void k_mul_normalise(float* __restrict__ acc, float* __restrict__ acc_lo, uint64_t P, uint32_t C, uint32_t S, int fold) {
+__global__ void k_mul_normalise(float* __restrict__ acc, float* __restrict__ acc_lo, uint64_t P, uint32_t C, int fold) {
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= P) return;
-  float* __restrict__ hi = acc + p * S;
-  float* __restrict__ lo = acc_lo + p * S;
+  float* __restrict__ hi = acc + p * C;
+  float* __restrict__ lo = acc_lo + p * C;
   double m = -INFINITY;
   for (uint32_t c = 0; c < C; c++) { const double t = (double)hi[c] + (double)lo[c]; if (t > m && t < INFINITY) m = t; }
   if (!(m > -INFINITY)) m = 0.0;
@@ -2176,9 +2129,8 @@ struct smesh_aggregator {
   uint32_t C = 0;
   int kind = 0;
   float iew = 0.5f;
-  uint32_t S = 0;             // accumulator row stride in floats (C rounded up to 16)
-  float* acc = nullptr;       // float32[P*S]
-  float* acc_lo = nullptr;    // Mul only: float32[P*S], a row's value is acc + acc_lo (fuse_tri.inc.hpp, "Mul state")
+  float* acc = nullptr;       // float32[P*C]
+  float* acc_lo = nullptr;    // Mul only: float32[P*C], a row's value is acc + acc_lo (fuse_tri.inc.hpp, "Mul state")
   double* acc_d = nullptr;    // Mul with texel renderers only (allocated on first use): float64[P*C], one view's terms of the texels of
                               // big triangles, all zero between launches (k_fuse_texel_big)
   uint32_t* count = nullptr;  // uint32[P], all zero between add() calls
@@ -2219,7 +2171,7 @@ namespace {
 int mul_normalise(smesh_aggregator* a, bool fold) {
   if (a->kind != SMESH_AGG_MUL || a->P == 0) return SMESH_OK;
   hipLaunchKernelGGL(k_mul_normalise, dim3((uint32_t)div_up(a->P, 256)), dim3(256), 0, a->ctx->stream, a->acc, a->acc_lo,
-                     a->P, a->C, a->S, fold ? 1 : 0);
+                     a->P, a->C, fold ? 1 : 0);
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }
@@ -2239,9 +2191,15 @@ size_t idx_itemsize(int dt) { return (dt == SMESH_IDX_U64 || dt == SMESH_IDX_I64
 // scatter at cfg2's geometry C = 19 0.149 / 0.122, 32 0.196 / 0.391.  Round 3 (passes M / R: one atomic per (primitive, strip) group,
 // asynchronous add): 2 0.053 / 0.093, 5 0.053 / 0.063, 13 0.066 / 0.105, 19 0.075 / 0.110, 27 0.108 / 0.144, 32 0.121 / 0.374,
 // 48 0.157, 64 0.294, 150 0.717 (tools/generic_add_sweep.py, profiles/r03_foreign_images_class_sweep.txt): the records win at every
-// class count, and they are deterministic with the reference's order of additions.  SMESH_ADD_RECORDS_MIN_C moves the threshold,
-// SMESH_ADD_RECORDS=0 turns the records off.
+// class count, and they are deterministic with the reference's order of additions.
 constexpr uint32_t kAddRecordsMinC = 0;
+
+// Does add() on a foreign image of C classes take the records?  Test hooks: SMESH_ADD_RECORDS=0 turns them off,
+// SMESH_ADD_RECORDS_MIN_C moves the threshold (read per call: tests move it at run time).
+bool add_records(uint32_t C) {
+  static const bool off = env_int("SMESH_ADD_RECORDS", 1) == 0;
+  return !off && C >= (uint32_t)env_int("SMESH_ADD_RECORDS_MIN_C", (int)kAddRecordsMinC);
+}
 
 // Core of add() once every buffer is in device memory.
 int add_device(smesh_aggregator* a, const void* d_idx, int idx_dtype, const int64_t is[2],
@@ -2290,11 +2248,8 @@ int add_device(smesh_aggregator* a, const void* d_idx, int idx_dtype, const int6
   // ---- triangle-order fusion on records built from the image (image_records.hip) ------------------
   // Every accumulator row gets one owner and the reference's order of additions: deterministic, Sum / Summax bit-equal to the
   // single-threaded float32 reference loop, and faster than the atomic scatter-add below, which remains for what the triangle-order
-  // kernels do not take (padded rows, SMESH_FUSE=strip, SMESH_ADD_RECORDS=0).
-  static const bool records_off = getenv("SMESH_ADD_RECORDS") && atoi(getenv("SMESH_ADD_RECORDS")) == 0;
-  const char* min_c_env = getenv("SMESH_ADD_RECORDS_MIN_C");      // (read per call: tests and tools move the threshold at run time)
-  const uint32_t records_min_c = min_c_env ? (uint32_t)atoi(min_c_env) : kAddRecordsMinC;
-  if (!records_off && C >= records_min_c && a->P > 0 && W <= 65535 && H <= 65535 && smesh_aggregator_can_fuse_triangles(a, a->P)) {
+  // kernels do not take (SMESH_FUSE=strip, SMESH_ADD_RECORDS=0).
+  if (add_records(C) && a->P > 0 && W <= 65535 && H <= 65535 && smesh_aggregator_can_fuse_triangles(a, a->P)) {
     ImageRecords& rec = a->rec;
     {
       ProfScope prof(ctx, SMESH_PROF_FUSE_HIST);
@@ -2315,9 +2270,8 @@ int add_device(smesh_aggregator* a, const void* d_idx, int idx_dtype, const int6
   args.idx = idx; args.probs = probs; args.weights = weights; args.pw = nullptr;
   const bool need_hist = a->iew != 0.0f;
   args.count = need_hist ? a->count : nullptr;
-  args.acc = a->acc; args.N = N; args.P = (uint32_t)a->P; args.C = C; args.S = a->S; args.iew = a->iew;
+  args.acc = a->acc; args.N = N; args.P = (uint32_t)a->P; args.C = C; args.iew = a->iew;
   args.W = (uint32_t)W; args.H = (uint32_t)H;
-  args.dbg = SMESH_ABL_ENV("SMESH_DBG");
   set_tiling(args);
 
   // ---- F1 histogram (skipped when the weight does not depend on it) -------------------------
@@ -2366,7 +2320,7 @@ int add_device(smesh_aggregator* a, const void* d_idx, int idx_dtype, const int6
         SMESH_TRY(ensure_acc_d(a));
         hipLaunchKernelGGL(k_pixel_weight<SMESH_AGG_MUL>, g1, b, 0, st, args, wpix, amax);
         hipLaunchKernelGGL(k_scatter_flat_mul, g2, b, 0, st, args, wpix, a->acc_d);
-        hipLaunchKernelGGL(k_fold_rows, dim3((uint32_t)div_up(a->P, 256)), b, 0, st, a->acc, a->acc_lo, a->acc_d, args.count, a->P, C, a->S);
+        hipLaunchKernelGGL(k_fold_rows, dim3((uint32_t)div_up(a->P, 256)), b, 0, st, a->acc, a->acc_lo, a->acc_d, args.count, a->P, C);
         break;
     }
     SMESH_HIP(hipGetLastError());
@@ -2424,20 +2378,25 @@ int smesh_aggregator_add_device_contig(smesh_aggregator* a, const uint32_t* d_id
   return add_device(a, d_idx, SMESH_IDX_U32, is, d_probs, ps, d_w, is, W, H);
 }
 
+// SMESH_FUSE=strip (test hook): the atomic scatter-add instead of the triangle-order fusion.
+static bool fuse_strip_forced() {
+  static const bool on = [] { const char* e = getenv("SMESH_FUSE"); return e && std::string(e) == "strip"; }();
+  return on;
+}
+
 // Triangle-order fusion entry used by raster.hip's smesh_fuse_view; see k_fuse_tri.
 bool smesh_aggregator_can_fuse_triangles(smesh_aggregator* a, uint64_t F) {
-  static const bool off = getenv("SMESH_FUSE") && std::string(getenv("SMESH_FUSE")) == "strip";
-  return !off && a->P == F && a->S == a->C && a->C <= 64u * (uint32_t)kSliceAny;   // 64 lanes x kSliceAny classes per row
+  return !fuse_strip_forced() && a->P == F && a->C <= 64u * (uint32_t)kSliceAny;   // 64 lanes x kSliceAny classes per row
 }
 
 // Largest class count the LDS-block kernel k_fuse_tri takes (a 64-slot instance needs 292 VGPRs and is no faster than
 // k_fuse_tri_any: C = 64 0.311 vs 0.292 ms/view; 48 slots: C = 48 0.184 vs 0.252).
-static const uint32_t kFuseTriMaxC = getenv("SMESH_FUSE_TRI_MAXC") ? (uint32_t)std::min(48, std::max(1, atoi(getenv("SMESH_FUSE_TRI_MAXC")))) : 48u;   // (experiment knob)
+constexpr uint32_t kFuseTriMaxC = 48;
 
 // Which kernel smesh_aggregator_fuse_triangles dispatches for this aggregator (reporting only).
 static bool fuse_wide_enabled() {
-  static const bool off = getenv("SMESH_FUSE_WIDE") && atoi(getenv("SMESH_FUSE_WIDE")) == 0;
-  return !off;
+  static const bool on = env_int("SMESH_FUSE_WIDE", 1) != 0;
+  return on;
 }
 const char* smesh_aggregator_fuse_kernel_name(smesh_aggregator* a, bool reordered) {
   if (a->C <= kFuseTriMaxC) return "k_fuse_tri";
@@ -2455,7 +2414,7 @@ bool smesh_aggregator_can_fuse_pair(smesh_aggregator* a) { return smesh_aggregat
 // 149 VGPRs at C = 19, 206 at C = 40 -- the occupancy of the two-view instance or one wave less), 2 up to kFuseTriMaxC (the 48-slot
 // instance has no registers left), else 1.  Instances exist for 1, 2, 4 and 8 views.
 int smesh_aggregator_max_fused_views(smesh_aggregator* a) {
-  static const int cap = getenv("SMESH_FUSE_VIEWS") ? std::max(1, atoi(getenv("SMESH_FUSE_VIEWS"))) : 8;
+  static const int cap = std::max(1, env_int("SMESH_FUSE_VIEWS", 8));
   int m = a->C <= 40u ? 8 : (a->C <= (uint32_t)kFuseTriMaxC ? 2 : 1);
   if (a->C > (uint32_t)kFuseTriMaxC) m = 8;   // k_fuse_tri_any / k_fuse_tri_wide: any count up to eight
   // 41 .. 48: four or eight views go through k_fuse_tri_any (0.124-0.133 vs 0.138-0.146 ms per view at cfg2's geometry), one or two
@@ -2476,8 +2435,7 @@ bool smesh_aggregator_fuses_small_views_by_mask(smesh_aggregator* a) {
 // output of a network seen as (W,H,C), colorize_cityscapes_mesh.py:65-67 -- instead of a gathered copy?  k_fuse_tri (C <= 48)
 // addresses every pixel's vector on its own; the wide-row kernels keep their dense layout.
 bool smesh_aggregator_takes_strided_probs(smesh_aggregator* a, int64_t ps0, int64_t ps1, int nviews) {
-  static const bool off = getenv("SMESH_STRIDED_PROBS") && atoi(getenv("SMESH_STRIDED_PROBS")) == 0;
-  if (off || ps0 <= 0 || ps1 <= 0 || ps0 > 0xFFFFFFFFll || ps1 > 0xFFFFFFFFll) return false;
+  if (ps0 <= 0 || ps1 <= 0 || ps0 > 0xFFFFFFFFll || ps1 > 0xFFFFFFFFll) return false;
   return a->C <= kFuseTriMaxC && !(a->C > 40u && nviews > 2);
 }
 
@@ -2491,18 +2449,18 @@ void smesh_fuse_part_rows(uint64_t F, int part, int nparts, uint64_t* f_lo, uint
   *f_hi = std::min(F, 64 * (B * (uint64_t)(part + 1) / (uint64_t)nparts));
 }
 
-// Sum rows of 128 .. 255 classes: the pixel-list kernel (k_fuse_tri_wide_list; SMESH_WIDE_LIST=0: k_fuse_tri_wide as until round 5).
+// Sum rows of 128 .. 255 classes: the pixel-list kernel (k_fuse_tri_wide_list; SMESH_WIDE_LIST=0: k_fuse_tri_wide).
 // false: not launched.  Where it is used and where not is measured (cfg2's mesh and resolution, eight views per call, ms per view, old /
 // list kernel; profiles/r06_wide_rows_sweep.txt): Sum C = 128 0.405 / 0.381, 150 0.467 / 0.406, 192 0.438 / 0.407, 240 0.454 / 0.439 --
 // 256 (rows of whole aligned lines) 0.371 / 0.454, 300 0.528 / 0.558, 1024 1.361 / 1.441; Summax (its arg-max needs registers the ring
 // has taken: spills) 150 0.638 / 0.694.  cfg5 (20 M sub-pixel triangles, C = 150): 1 651 / 1 125 us per view.
 template <int KIND>
-static bool launch_fuse_wide_list(int wide_chunks, uint32_t C, dim3 wgrid, hipStream_t st, const TriFuseArgs& t, const TriViews<8>& tv, int nviews) {
-  static const bool off = getenv("SMESH_WIDE_LIST") && atoi(getenv("SMESH_WIDE_LIST")) == 0;
+static bool launch_fuse_wide_list(int wide_chunks, uint32_t C, dim3 grid, hipStream_t st, const TriFuseArgs& t, const TriViews<8>& tv, int nviews) {
+  static const bool off = env_int("SMESH_WIDE_LIST", 1) == 0;
   if constexpr (KIND != SMESH_AGG_SUM) return false;
   else {
     if (off || wide_chunks != 1 || C >= 256u) return false;
-    hipLaunchKernelGGL((k_fuse_tri_wide_list<KIND, 1>), wgrid, dim3(kWave), 0, st, t, tv, nviews);
+    hipLaunchKernelGGL((k_fuse_tri_wide_list<KIND, 1>), grid, dim3(kWave), 0, st, t, tv, nviews);
     return true;
   }
 }
@@ -2541,7 +2499,6 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
     x.ps0 = tv.v[0].ps0; x.ps1 = tv.v[0].ps1;
     x.big_capacity = big_capacity;
     x.tri_blocks = (uint32_t)div_up(F, kWave);
-    { static const int fdbg = SMESH_ABL_ENV("SMESH_FDBG"); x.dbg = fdbg; }
     x.tex_first = nullptr; x.tex_res = nullptr; x.count = nullptr; x.acc_d = nullptr;
     x.prim_id = prim_id;
     x.mid = 0;
@@ -2563,12 +2520,9 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
   uint64_t scratch_stride = N;   // per-view scratch images of the big-triangle waves
   int G = 1;
   const int wide_chunks = (fuse_wide_enabled() && a->C >= 128 && a->C <= 1024) ? (a->C <= 256 ? 1 : a->C <= 512 ? 2 : 4) : 0;   // k_fuse_tri_wide
-  // rows (and their next pixels) in flight per wave: 2 (Sum / Summax at any width: cfg5 views/s with 2 rows and 8 waves per SIMD 509, 4 rows
+  // k_fuse_tri_wide's B (SMESH_FW below), rows (and their next pixels) in flight per wave: 2 (Sum / Summax at any width: cfg5 views/s with 2 rows and 8 waves per SIMD 509, 4 rows
   // and 5 waves 496, 8 rows -- 284 registers, one wave -- 130); Mul with rows of up to 256 classes: 4 (measured in round 4); Mul beyond:
-  // 2 (its per-view partial sums in double over two chunks are 64 more registers -- ADVICE r5: the dispatch used to pick <K, 2, 4>).
-  // SMESH_WIDE_B = 2 / 4 / 8 forces (experiment knob; other values are ignored).
-  static const int wide_b_env = [] { const int v = getenv("SMESH_WIDE_B") ? atoi(getenv("SMESH_WIDE_B")) : 0; return (v == 2 || v == 4 || v == 8) ? v : 0; }();
-  const int wide_b = wide_b_env ? wide_b_env : ((a->kind == SMESH_AGG_MUL && wide_chunks == 1) ? 4 : 2);
+  // 2 (its per-view partial sums in double over two chunks are 64 more registers).
   if (!specialised) {
     while ((((a->C + G - 1) / G + 3u) & ~3u) > (uint32_t)kSliceAny) G *= 2;   // lanes per accumulator row (can_fuse_triangles: G <= 64)
     // the big-triangle waves park per-pixel weights (and arg-max) here
@@ -2583,7 +2537,7 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
     t.blk_first = (uint32_t)(f_lo / tpb);
     t.tri_blocks = (uint32_t)div_up(f_hi - f_lo, tpb);
   }
-  static const uint32_t big_per_cu = getenv("SMESH_BIG_WAVES") ? (uint32_t)std::max(1, atoi(getenv("SMESH_BIG_WAVES"))) : 16u;
+  constexpr uint32_t big_per_cu = 16;
   // one wave per queued big triangle at a time; they exit at once if the queue is empty.  A launch over one of `nparts` triangle
   // ranges takes its share of them (every one of its waves still walks the whole queue and keeps the triangles of its range).
   bool no_big = true;     // every view of the launch PROVEN free of triangles with a box over 8 x 8 (RenderedView::no_big): no tail waves at all
@@ -2596,12 +2550,11 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
   // with part 0.
   uint32_t mid_waves = 0;
   if (specialised) {
-    static const int mid_mode = getenv("SMESH_FUSE_MID") ? atoi(getenv("SMESH_FUSE_MID")) : 1;   // 0: the tail waves take the medium triangles too
     bool listed = true;                              // (records rebuilt from a foreign image carry no list of medium primitives)
     for (int v = 0; v < nviews; v++) listed = listed && views[v].mid_queue;
-    if (mid_mode && listed && a->kind != SMESH_AGG_MUL) {
+    if (listed && a->kind != SMESH_AGG_MUL) {
       t.mid = 1;
-      static const uint32_t mid_per_cu = getenv("SMESH_MID_WAVES") ? (uint32_t)std::max(1, atoi(getenv("SMESH_MID_WAVES"))) : 32u;   // (90 000 triangles at 1080p, ms per view: 8 -> 0.111, 16 -> 0.108, 32 -> 0.104, 64 -> 0.103; cfg2 0.062 throughout)
+      constexpr uint32_t mid_per_cu = 32;   // (90 000 triangles at 1080p, ms per view: 8 -> 0.111, 16 -> 0.108, 32 -> 0.104, 64 -> 0.103; cfg2 0.062 throughout)
       if (part == 0 && !no_big) mid_waves = mid_per_cu * (uint32_t)std::max(1, ctx->num_cus);
     }
   }
@@ -2618,13 +2571,6 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
   }
   const dim3 grid(t.tri_blocks + big_waves + mid_waves), block(kWave);
   const dim3 tgrid(t.tri_blocks), bgrid(big_waves);                        // any-C paths: big triangles in a second launch
-  {   // k_fuse_tri_wide: the triangle blocks dealt to the XCDs in runs of SMESH_WIDE_XCD consecutive blocks (default 0: dispatch order).
-      // Measured at cfg5 (round 6): one run per XCD -- an eighth of the mesh each -- 506 -> 268 views/s: the eighths are not equally
-      // visible in a view and the launch waits for the XCDs that hold the visible ones.
-    static const uint32_t wide_xcd = getenv("SMESH_WIDE_XCD") ? (uint32_t)std::max(0, atoi(getenv("SMESH_WIDE_XCD"))) : 0u;
-    t.xcd_chunk = (wide_chunks && t.tri_blocks >= 64u) ? wide_xcd : 0u;
-  }
-  const dim3 wgrid(t.xcd_chunk ? 8u * (uint32_t)div_up(t.tri_blocks, 8u * t.xcd_chunk) * t.xcd_chunk : t.tri_blocks);
   if (!specialised && part == 0) SMESH_TRY(mul_recentre(a));   // (a pass over ALL rows: never beside the exchange of a finished range)
   {
     ProfScope prof(ctx, SMESH_PROF_FUSE_SCATTER);
@@ -2641,12 +2587,10 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
     }
 #define SMESH_FW(K)                                                                            \
     switch (wide_chunks) {                                                                     \
-      case 1:  if (wide_b == 8) hipLaunchKernelGGL((k_fuse_tri_wide<K, 1, 8>), wgrid, block, 0, st, t, tv, nviews);   \
-               else if (wide_b == 2) hipLaunchKernelGGL((k_fuse_tri_wide<K, 1, 2>), wgrid, block, 0, st, t, tv, nviews); \
-               else hipLaunchKernelGGL((k_fuse_tri_wide<K, 1, 4>), wgrid, block, 0, st, t, tv, nviews); break; \
-      case 2:  if (wide_b >= 4) hipLaunchKernelGGL((k_fuse_tri_wide<K, 2, 4>), wgrid, block, 0, st, t, tv, nviews);   \
-               else hipLaunchKernelGGL((k_fuse_tri_wide<K, 2, 2>), wgrid, block, 0, st, t, tv, nviews); break; \
-      default: hipLaunchKernelGGL((k_fuse_tri_wide<K, 4, 2>), wgrid, block, 0, st, t, tv, nviews); break; \
+      case 1:  if (K == SMESH_AGG_MUL) hipLaunchKernelGGL((k_fuse_tri_wide<K, 1, 4>), tgrid, block, 0, st, t, tv, nviews); \
+               else hipLaunchKernelGGL((k_fuse_tri_wide<K, 1, 2>), tgrid, block, 0, st, t, tv, nviews); break; \
+      case 2:  hipLaunchKernelGGL((k_fuse_tri_wide<K, 2, 2>), tgrid, block, 0, st, t, tv, nviews); break; \
+      default: hipLaunchKernelGGL((k_fuse_tri_wide<K, 4, 2>), tgrid, block, 0, st, t, tv, nviews); break; \
     }
 #define SMESH_FT(K)                                                                           \
     switch (tri_ct) {                                                                         \
@@ -2664,7 +2608,7 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
       case 48: hipLaunchKernelGGL((k_fuse_tri<48, K, false, 1>), grid, block, 0, st, t, tv1); break;   \
       default:                                                                                \
         if (!t.tri_blocks) { }                                                                \
-        else if (wide_chunks && launch_fuse_wide_list<K>(wide_chunks, a->C, wgrid, st, t, tv, nviews)) { }   \
+        else if (wide_chunks && launch_fuse_wide_list<K>(wide_chunks, a->C, tgrid, st, t, tv, nviews)) { }   \
         else if (wide_chunks) { SMESH_FW(K); } else { SMESH_FA(K); }                          \
         if (!no_big) hipLaunchKernelGGL((k_fuse_big_any<K>), bgrid, block, 0, st, t, tv, nviews, pw, amax, scratch_stride); \
         break;                                                                                \
@@ -2688,8 +2632,7 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
 }
 
 bool smesh_aggregator_can_fuse_texels(smesh_aggregator* a, uint64_t P) {
-  static const bool off = getenv("SMESH_FUSE") && std::string(getenv("SMESH_FUSE")) == "strip";
-  return !off && a->P == P && a->S == a->C && a->C <= (uint32_t)kSlice;
+  return !fuse_strip_forced() && a->P == P && a->C <= (uint32_t)kSlice;
 }
 
 // Mul: the double scratch of k_fuse_texel_big, on first use.
@@ -2713,7 +2656,7 @@ int smesh_aggregator_fuse_texels(smesh_aggregator* a, const TriFrag* frags, cons
   t.tri_blocks = (uint32_t)div_up(F, kWave);
   t.big_blocks = 0;
   t.blk_first = 0u; t.f_lo = 0u; t.f_hi = (uint32_t)F;
-  t.dbg = 0; t.prim_id = nullptr; t.lds_pad = 0u;
+  t.prim_id = nullptr; t.lds_pad = 0u;
   SMESH_TRY(ensure_acc_d(a));
   t.tex_first = tex_first; t.tex_res = tex_res; t.count = a->count; t.acc_d = a->acc_d; t.tex_kinds = kinds;
   const dim3 tgrid((uint32_t)div_up(F, kTexelBlock)), bgrid(12u * (uint32_t)std::max(1, ctx->num_cus)), block(kWave), tblock(kTexelBlock);
@@ -2760,7 +2703,7 @@ int smesh_aggregator_fuse_texels_multi(smesh_aggregator* a, uint64_t F, const ui
   t.tri_blocks = (uint32_t)div_up(F, kWave);
   t.big_blocks = 0;
   t.blk_first = 0u; t.f_lo = 0u; t.f_hi = (uint32_t)F;
-  t.dbg = 0; t.prim_id = nullptr; t.lds_pad = 0u;
+  t.prim_id = nullptr; t.lds_pad = 0u;
   SMESH_TRY(ensure_acc_d(a));
   t.tex_first = tex_first; t.tex_res = tex_res; t.count = a->count; t.acc_d = a->acc_d; t.tex_kinds = nullptr;
   const dim3 tgrid((uint32_t)div_up(F, kTexelBlock)), bgrid(12u * (uint32_t)std::max(1, ctx->num_cus)), block(kWave), tblock(kTexelBlock);
@@ -2800,8 +2743,8 @@ int smesh_aggregator_acc(smesh_aggregator* a, float** acc, uint64_t* num_floats,
   SMESH_TRY(smesh_aggregator_join_exchange(a));
   SMESH_TRY(mul_normalise(a, true));
   if (acc) *acc = a->acc;
-  if (num_floats) *num_floats = a->P * a->S;
-  if (row_stride) *row_stride = a->S;
+  if (num_floats) *num_floats = a->P * a->C;
+  if (row_stride) *row_stride = a->C;
   if (rows) *rows = a->P;
   return SMESH_OK;
 }
@@ -2848,25 +2791,25 @@ __global__ void k_mul_rows_from_f64(const double* __restrict__ in, float* __rest
 int smesh_aggregator_exchange_begin(smesh_aggregator* a, uint64_t lo, uint64_t hi, hipStream_t st, void** buf, uint64_t* count, int* is_f64) {
   *buf = nullptr; *count = 0; *is_f64 = 0;
   if (lo > hi || hi > a->P) return fail(SMESH_ERR_INVALID, "bad row range");
-  const uint64_t n = (hi - lo) * a->S;
+  const uint64_t n = (hi - lo) * a->C;
   if (n == 0) return SMESH_OK;
   *count = n;
-  if (a->kind != SMESH_AGG_MUL) { *buf = a->acc + lo * a->S; return SMESH_OK; }
+  if (a->kind != SMESH_AGG_MUL) { *buf = a->acc + lo * a->C; return SMESH_OK; }
   if (a->xchg_stage.bytes < n * 8) {
     SMESH_HIP(hipStreamSynchronize(st));   // growing the staging buffer frees the old one: the previous range's collective must be through
     SMESH_TRY(a->xchg_stage.reserve(n * 8));
   }
-  hipLaunchKernelGGL(k_mul_rows_to_f64, dim3((uint32_t)div_up(n, 256)), dim3(256), 0, st, a->acc + lo * a->S, a->acc_lo + lo * a->S,
+  hipLaunchKernelGGL(k_mul_rows_to_f64, dim3((uint32_t)div_up(n, 256)), dim3(256), 0, st, a->acc + lo * a->C, a->acc_lo + lo * a->C,
                      static_cast<double*>(a->xchg_stage.ptr), n);
   SMESH_HIP(hipGetLastError());
   *buf = a->xchg_stage.ptr; *is_f64 = 1;
   return SMESH_OK;
 }
 int smesh_aggregator_exchange_end(smesh_aggregator* a, uint64_t lo, uint64_t hi, hipStream_t st) {
-  const uint64_t n = (hi - lo) * a->S;
+  const uint64_t n = (hi - lo) * a->C;
   if (n == 0 || a->kind != SMESH_AGG_MUL) return SMESH_OK;
   hipLaunchKernelGGL(k_mul_rows_from_f64, dim3((uint32_t)div_up(n, 256)), dim3(256), 0, st, static_cast<const double*>(a->xchg_stage.ptr),
-                     a->acc + lo * a->S, a->acc_lo + lo * a->S, n);
+                     a->acc + lo * a->C, a->acc_lo + lo * a->C, n);
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }
@@ -2913,8 +2856,8 @@ int smesh_aggregator_create(uint64_t P, uint32_t C, int kind, float iew, int dev
   SMESH_HIP(hipSetDevice(device));
   auto* a = new (std::nothrow) smesh_aggregator();
   if (!a) return fail(SMESH_ERR_RUNTIME, "out of memory");
-  a->ctx = ctx; a->P = P; a->C = C; a->S = row_stride(C); a->kind = kind; a->iew = iew;
-  const size_t acc_bytes = (size_t)P * a->S * 4;
+  a->ctx = ctx; a->P = P; a->C = C; a->kind = kind; a->iew = iew;
+  const size_t acc_bytes = (size_t)P * a->C * 4;
   hipError_t e = dev_malloc(reinterpret_cast<void**>(&a->acc), acc_bytes ? acc_bytes : 16);
   if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&a->count), P ? P * 4 : 16);
   if (e == hipSuccess) e = hipMemsetAsync(a->acc, 0, acc_bytes, ctx->stream);   // Sum/Summax: 0; Mul: log 1 = 0
@@ -2961,8 +2904,8 @@ int smesh_aggregator_reset(smesh_aggregator_t* a) {
   SMESH_HIP(hipSetDevice(a->ctx->device));
   SMESH_TRY(smesh_aggregator_join_exchange(a));
   a->scattered = false;
-  SMESH_HIP(hipMemsetAsync(a->acc, 0, (size_t)a->P * a->S * 4, a->ctx->stream));
-  if (a->acc_lo) SMESH_HIP(hipMemsetAsync(a->acc_lo, 0, (size_t)a->P * a->S * 4, a->ctx->stream));
+  SMESH_HIP(hipMemsetAsync(a->acc, 0, (size_t)a->P * a->C * 4, a->ctx->stream));
+  if (a->acc_lo) SMESH_HIP(hipMemsetAsync(a->acc_lo, 0, (size_t)a->P * a->C * 4, a->ctx->stream));
   return SMESH_OK;
 }
 
@@ -3050,13 +2993,10 @@ int smesh_aggregator_add_many(smesh_aggregator_t* a, uint64_t n, const void* con
   bool grouped;
   {
     std::lock_guard<std::mutex> g(a->mu);
-    static const bool records_off = getenv("SMESH_ADD_RECORDS") && atoi(getenv("SMESH_ADD_RECORDS")) == 0;
-    const char* min_c_env = getenv("SMESH_ADD_RECORDS_MIN_C");
-    const uint32_t records_min_c = min_c_env ? (uint32_t)atoi(min_c_env) : kAddRecordsMinC;
     grouped = n >= 2 && imem == SMESH_MEM_DEVICE && pmem == SMESH_MEM_DEVICE && (!weights || wmem == SMESH_MEM_DEVICE) &&
               (idx_dtype == SMESH_IDX_U32 || idx_dtype == SMESH_IDX_I32) && is[0] == (int64_t)H && is[1] == 1 &&
               ps[0] == (int64_t)(H * a->C) && ps[1] == (int64_t)a->C && ps[2] == 1 && (!weights || (ws[0] == (int64_t)H && ws[1] == 1)) &&
-              !records_off && a->C >= records_min_c && a->P > 0 && W <= 65535 && H <= 65535 && W * H < 0x7FFFFFFFull / 4 &&
+              add_records(a->C) && a->P > 0 && W <= 65535 && H <= 65535 && W * H < 0x7FFFFFFFull / 4 &&
               smesh_aggregator_can_fuse_triangles(a, a->P) && smesh_aggregator_max_fused_views(a) >= 2;
     for (uint64_t i = 0; i < n && grouped; i++) grouped = !(reinterpret_cast<uintptr_t>(probs[i]) & 15);
   }
@@ -3125,8 +3065,8 @@ static int finalize_into(smesh_aggregator* a, float* d_out, uint64_t row_lo = 0,
   row_hi = std::min<uint64_t>(row_hi, a->P);
   if (row_lo >= row_hi) return SMESH_OK;
   const uint64_t P = row_hi - row_lo;
-  float* const acc = a->acc + row_lo * a->S;
-  float* const acc_lo = a->acc_lo ? a->acc_lo + row_lo * a->S : nullptr;
+  float* const acc = a->acc + row_lo * a->C;
+  float* const acc_lo = a->acc_lo ? a->acc_lo + row_lo * a->C : nullptr;
   ProfScope prof(ctx, SMESH_PROF_FINALIZE);
   int TP = tile_pixels(a->C);
   const int C = (int)a->C;
@@ -3139,16 +3079,16 @@ static int finalize_into(smesh_aggregator* a, float* d_out, uint64_t row_lo = 0,
     const size_t lds = (((size_t)TP * C + 3) & ~(size_t)3) * 4 * (mul ? 2 : 1);
     const dim3 g((uint32_t)div_up(P, TP));
     switch (a->kind) {
-      case SMESH_AGG_SUM:    hipLaunchKernelGGL(k_finalize_tile<SMESH_AGG_SUM>, g, dim3(256), lds, ctx->stream, acc, nullptr, d_out, P, C, (int)a->S, TP); break;
-      case SMESH_AGG_SUMMAX: hipLaunchKernelGGL(k_finalize_tile<SMESH_AGG_SUMMAX>, g, dim3(256), lds, ctx->stream, acc, nullptr, d_out, P, C, (int)a->S, TP); break;
-      default:               hipLaunchKernelGGL(k_finalize_tile<SMESH_AGG_MUL>, g, dim3(256), lds, ctx->stream, acc, mul ? acc_lo : nullptr, d_out, P, C, (int)a->S, TP); break;
+      case SMESH_AGG_SUM:    hipLaunchKernelGGL(k_finalize_tile<SMESH_AGG_SUM>, g, dim3(256), lds, ctx->stream, acc, nullptr, d_out, P, C, TP); break;
+      case SMESH_AGG_SUMMAX: hipLaunchKernelGGL(k_finalize_tile<SMESH_AGG_SUMMAX>, g, dim3(256), lds, ctx->stream, acc, nullptr, d_out, P, C, TP); break;
+      default:               hipLaunchKernelGGL(k_finalize_tile<SMESH_AGG_MUL>, g, dim3(256), lds, ctx->stream, acc, mul ? acc_lo : nullptr, d_out, P, C, TP); break;
     }
   } else {
     const dim3 g((uint32_t)div_up(P, 256)), b(256);
     switch (a->kind) {
-      case SMESH_AGG_SUM: hipLaunchKernelGGL(k_finalize_rows<SMESH_AGG_SUM>, g, b, 0, ctx->stream, acc, d_out, P, C, (int)a->S); break;
-      case SMESH_AGG_SUMMAX: hipLaunchKernelGGL(k_finalize_rows<SMESH_AGG_SUMMAX>, g, b, 0, ctx->stream, acc, d_out, P, C, (int)a->S); break;
-      default: hipLaunchKernelGGL(k_finalize_rows<SMESH_AGG_MUL>, g, b, 0, ctx->stream, acc, d_out, P, C, (int)a->S); break;
+      case SMESH_AGG_SUM: hipLaunchKernelGGL(k_finalize_rows<SMESH_AGG_SUM>, g, b, 0, ctx->stream, acc, d_out, P, C); break;
+      case SMESH_AGG_SUMMAX: hipLaunchKernelGGL(k_finalize_rows<SMESH_AGG_SUMMAX>, g, b, 0, ctx->stream, acc, d_out, P, C); break;
+      default: hipLaunchKernelGGL(k_finalize_rows<SMESH_AGG_MUL>, g, b, 0, ctx->stream, acc, d_out, P, C); break;
     }
   }
   SMESH_HIP(hipGetLastError());
@@ -3196,9 +3136,8 @@ static PinnedRing g_rings[64];
 static void copy_ring_prepare(DeviceCtx* ctx) { (void)g_rings[ctx->device & 63].init(); }
 
 static int copy_to_host(DeviceCtx* ctx, void* out, const void* d_src, size_t bytes) {
-  static const bool off = getenv("SMESH_GET_STAGING") && atoi(getenv("SMESH_GET_STAGING")) == 0;
   PinnedRing& ring = g_rings[ctx->device & 63];
-  if (!off && bytes >= (4u << 20)) {
+  if (bytes >= (4u << 20)) {
     // a fresh numpy array is untouched memory: 19 000 first-touch page faults for a cfg2 result cost more than the transfer.  Ask
     // for transparent huge pages on its page-aligned interior (a no-op where THP is off or the range is already populated).
     const uintptr_t lo = (reinterpret_cast<uintptr_t>(out) + (2u << 20) - 1) & ~(uintptr_t)((2u << 20) - 1);
@@ -3211,7 +3150,7 @@ static int copy_to_host(DeviceCtx* ctx, void* out, const void* d_src, size_t byt
     if (hipPointerGetAttributes(&attr, out) == hipSuccess) pinned = attr.type == hipMemoryTypeHost;
     else (void)hipGetLastError();
   }
-  if (off || pinned || bytes < (4u << 20) || !ring.init()) {
+  if (pinned || bytes < (4u << 20) || !ring.init()) {
     SMESH_HIP(hipMemcpyAsync(out, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SMESH_HIP(hipStreamSynchronize(ctx->stream));
     return SMESH_OK;
@@ -3290,9 +3229,7 @@ int smesh_aggregator_get_raw(smesh_aggregator_t* a, float* out, int memkind) {
   const size_t bytes = (size_t)a->P * a->C * 4;
   if (!bytes) return SMESH_OK;
   SMESH_TRY(mul_normalise(a, true));
-  // padded rows [P][S] -> dense [P][C]
-  SMESH_HIP(hipMemcpy2DAsync(out, (size_t)a->C * 4, a->acc, (size_t)a->S * 4, (size_t)a->C * 4, a->P,
-                             memkind == SMESH_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+  SMESH_HIP(hipMemcpyAsync(out, a->acc, bytes, memkind == SMESH_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
   SMESH_HIP(hipStreamSynchronize(ctx->stream));
   return SMESH_OK;
 }
@@ -3307,10 +3244,8 @@ int smesh_aggregator_set_raw(smesh_aggregator_t* a, const float* in, int memkind
   a->scattered = false;   // every row is being overwritten
   const size_t bytes = (size_t)a->P * a->C * 4;
   if (!bytes) return SMESH_OK;
-  if (a->acc_lo) SMESH_HIP(hipMemsetAsync(a->acc_lo, 0, (size_t)a->P * a->S * 4, ctx->stream));
-  // dense [P][C] -> padded rows [P][S]; the padding stays zero
-  SMESH_HIP(hipMemcpy2DAsync(a->acc, (size_t)a->S * 4, in, (size_t)a->C * 4, (size_t)a->C * 4, a->P,
-                             memkind == SMESH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+  if (a->acc_lo) SMESH_HIP(hipMemsetAsync(a->acc_lo, 0, bytes, ctx->stream));
+  SMESH_HIP(hipMemcpyAsync(a->acc, in, bytes, memkind == SMESH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
   SMESH_HIP(hipStreamSynchronize(ctx->stream));
   return SMESH_OK;
 }
@@ -3328,13 +3263,12 @@ static int raw_rows(smesh_aggregator_t* a, uint64_t row_lo, uint64_t row_hi, int
   SMESH_TRY(smesh_aggregator_join_exchange(a));
   SMESH_TRY(smesh_aggregator_refuse_scattered(a, set ? "set_raw_rows()" : "get_raw_rows()"));
   if (row_lo == row_hi) return SMESH_OK;
-  float* rows = (plane ? a->acc_lo : a->acc) + row_lo * a->S;
+  float* rows = (plane ? a->acc_lo : a->acc) + row_lo * a->C;
+  const size_t bytes = (size_t)(row_hi - row_lo) * a->C * 4;
   if (set)
-    SMESH_HIP(hipMemcpy2DAsync(rows, (size_t)a->S * 4, buf, (size_t)a->C * 4, (size_t)a->C * 4, row_hi - row_lo,
-                               memkind == SMESH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    SMESH_HIP(hipMemcpyAsync(rows, buf, bytes, memkind == SMESH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
   else
-    SMESH_HIP(hipMemcpy2DAsync(buf, (size_t)a->C * 4, rows, (size_t)a->S * 4, (size_t)a->C * 4, row_hi - row_lo,
-                               memkind == SMESH_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    SMESH_HIP(hipMemcpyAsync(buf, rows, bytes, memkind == SMESH_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
   SMESH_HIP(hipStreamSynchronize(ctx->stream));
   return SMESH_OK;
 }
@@ -3355,13 +3289,13 @@ int smesh_aggregator_raw_pointer(smesh_aggregator_t* a, void** ptr, uint64_t* n)
   SMESH_TRY(mul_normalise(a, true));
   SMESH_HIP(hipStreamSynchronize(a->ctx->stream));
   *ptr = a->acc;
-  if (n) *n = a->P * a->S;
+  if (n) *n = a->P * a->C;
   return SMESH_OK;
 }
 
 int smesh_aggregator_row_stride(smesh_aggregator_t* a, uint32_t* stride) {
   if (!a || !stride) return fail(SMESH_ERR_INVALID, "NULL argument");
-  *stride = a->S;
+  *stride = a->C;
   return SMESH_OK;
 }
 

@@ -6,7 +6,6 @@
 #include "common.hpp"
 
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 using namespace smesh;
@@ -19,12 +18,11 @@ namespace {
 
 void smesh_launch_fuse_tri_8(int kind, int tri_ct, dim3 grid, hipStream_t st, const TriFuseArgs& t, const TriViews<8>& tv) {
   const dim3 block(kWave);
-  // Group pipeline (the default since round 5; SMESH_GROUP_PIPELINE=0 / smesh_set_option turn it off; raster.hip): the rasteriser of the next group runs beside this launch, and the one-wave
+  // Group pipeline (SMESH_GROUP_PIPELINE=0 / smesh_set_option turn it off; raster.hip): the rasteriser of the next group runs beside this launch, and the one-wave
   // workgroups of this kernel would take every wave slot that frees up.  An LDS pad caps them at five per CU -- alone the kernel
   // loses 2 % that way (it is bound by the memory system, not by occupancy) -- and leaves the rest of the register file to the
-  // rasteriser's waves (NOTES/round2.md).  SMESH_FUSE_LDS_PAD overrides (bytes).
-  static const int pad_env = getenv("SMESH_FUSE_LDS_PAD") ? atoi(getenv("SMESH_FUSE_LDS_PAD")) : -1;
-  const unsigned pad = pad_env >= 0 ? (unsigned)pad_env : t.lds_pad;      // (decided per launch: smesh_aggregator_fuse_triangles)
+  // rasteriser's waves (NOTES/round2.md).
+  const unsigned pad = t.lds_pad;      // (decided per launch: smesh_aggregator_fuse_triangles)
   TriViews<8> vn;
   for (int v = 0; v < 8; v++) vn.v[v] = tv.v[v];
 #define SMESH_FTN(K)                                                                                     \

@@ -4,9 +4,9 @@
 // of the atomic scatter-add: every accumulator row then has one owner, the additions happen in the reference's pixel order
 // (Mesh.h:94-106 run single-threaded) and the result no longer depends on the order in which float atomics land.
 //
-// What the rasteriser leaves per triangle (common.hpp, TriFrag) is rebuilt per PRIMITIVE from the image alone.  Round 3's passes
+// What the rasteriser leaves per triangle (common.hpp, TriFrag) is rebuilt per PRIMITIVE from the image alone.  The moments passes
 // (M, R, E / C' / D: one atomic per (primitive, strip) group, further down) serve every image of 16 .. 16383 pixels a side with fewer
-// than 2^24 pixels; round 2's passes serve the rest and stay behind SMESH_REC_MOMENTS=0:
+// than 2^24 pixels and at most eight primitives per pixel (use_moments); passes A / B serve the rest:
 //   pass A  k_rec_origin   per run of equal indices in a column: ONE 32-bit atomic that leaves the primitive's first pixel in
 //                          (x, y) order -- its smallest x, and the smallest y of that column (atomic max on the complement of
 //                          x << 16 | y: the cleared state, 0, means "no pixel")
@@ -189,7 +189,7 @@ __device__ __forceinline__ unsigned long long shfl64(unsigned long long x, int s
 // column is bit arithmetic on them, and the (at most four) runs of a chain are folded into its root by two pointer-doubling hops --
 // no LDS, no loops over rows.
 __device__ __forceinline__ void rec_moments_block(const uint32_t* __restrict__ idx, uint32_t W, uint32_t H, uint32_t P, uint32_t strips_y,
-                                                  uint32_t nstrips, uint32_t strips_per_xcd, uint32_t tag, int dbg,
+                                                  uint32_t nstrips, uint32_t strips_per_xcd, uint32_t tag,
                                                   unsigned long long* __restrict__ mom, TriFrag* __restrict__ frags,
                                                   uint32_t* __restrict__ big_count) {
   const uint32_t b = blockIdx.x;
@@ -267,12 +267,12 @@ __device__ __forceinline__ void rec_moments_block(const uint32_t* __restrict__ i
     const uint32_t n = wm & 127u, scx = (wm >> 7) & 255u, sty = wm >> 15;
     const unsigned long long pk = (unsigned long long)n | ((unsigned long long)(__umul24(n, x0) + scx) << kMomCountBits) |
                                   ((unsigned long long)(__umul24(n, y0) + sty) << (kMomCountBits + kMomSumBits));
-    if (!(SMESH_ABL(dbg) & 4)) atomicAdd(&mom[v], pk);
+    atomicAdd(&mom[v], pk);
   }
   uint32_t rows = (uint32_t)(sm | (sm >> 32));
   rows = (rows | (rows >> 16)) & 0xFFFFu;
   const int ymin = __builtin_ctz(rows), ymax = 31 - __builtin_clz(rows);
-  if (ymax - ymin < 8 && !(SMESH_ABL(dbg) & 2)) {
+  if (ymax - ymin < 8) {
     unsigned long long mask = 0ull;               // bit dx * 8 + dy (common.hpp, TriFrag); the chain's columns are cx, cx + 1, ...
 #pragma unroll
     for (int j = 0; j < kSX; j++)
@@ -283,10 +283,10 @@ __device__ __forceinline__ void rec_moments_block(const uint32_t* __restrict__ i
 }
 
 __global__ __launch_bounds__(kWave) void k_rec_moments(const uint32_t* __restrict__ idx, uint32_t W, uint32_t H, uint32_t P, uint32_t strips_y,
-                                                       uint32_t nstrips, uint32_t strips_per_xcd, uint32_t tag, int dbg,
+                                                       uint32_t nstrips, uint32_t strips_per_xcd, uint32_t tag,
                                                        unsigned long long* __restrict__ mom, TriFrag* __restrict__ frags,
                                                        uint32_t* __restrict__ big_count) {
-  rec_moments_block(idx, W, H, P, strips_y, nstrips, strips_per_xcd, tag, dbg, mom, frags, big_count);
+  rec_moments_block(idx, W, H, P, strips_y, nstrips, strips_per_xcd, tag, mom, frags, big_count);
 }
 
 // Up to eight images of the same size in ONE launch per pass (smesh_aggregator_add_many): image blockIdx.y with its own record set.
@@ -307,9 +307,9 @@ struct RecGroup {
   RecImage im[8];
 };
 __global__ __launch_bounds__(kWave) void k_rec_moments_group(RecGroup g, uint32_t W, uint32_t H, uint32_t P, uint32_t strips_y, uint32_t nstrips,
-                                                             uint32_t strips_per_xcd, int dbg) {
+                                                             uint32_t strips_per_xcd) {
   const RecImage& r = g.im[blockIdx.y];
-  rec_moments_block(r.idx, W, H, P, strips_y, nstrips, strips_per_xcd, r.tag, dbg, r.mom, r.frags, r.big_count);
+  rec_moments_block(r.idx, W, H, P, strips_y, nstrips, strips_per_xcd, r.tag, r.mom, r.frags, r.big_count);
 }
 
 // Bits of the pixels equal to v in an 8-column x 8-row window at (xs, ys), bit dx * 8 + dy.  The window lies inside the image.
@@ -338,7 +338,7 @@ __device__ __forceinline__ uint4 record_from_window(unsigned long long mask, uin
 }
 
 __device__ __forceinline__ void rec_resolve_block(const uint32_t* __restrict__ idx, uint32_t W, uint32_t H, uint32_t P, uint32_t tag,
-                                                  int dbg, unsigned long long* __restrict__ mom, TriFrag* __restrict__ frags,
+                                                  unsigned long long* __restrict__ mom, TriFrag* __restrict__ frags,
                                                   uint32_t* __restrict__ big_queue, uint32_t* __restrict__ big_count) {
   const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
   if (v >= P) return;
@@ -355,7 +355,7 @@ __device__ __forceinline__ void rec_resolve_block(const uint32_t* __restrict__ i
   // left by the previous call or written by this call's pass M: a stale record never carries this call's tag.)
   // (Compacting the others -- a sixth of cfg2's primitives, spread over every wave -- through LDS so that one wave of the workgroup
   // repairs them was measured slower: 13.8 -> 15.4 us.)
-  if (((raw.y >> 16) == tag && (uint32_t)__popcll(smask) == n) || (SMESH_ABL(dbg) & 1)) return;
+  if ((raw.y >> 16) == tag && (uint32_t)__popcll(smask) == n) return;
   uint4 rec = make_uint4(0u, kPadPending << 16, n, 0u);                      // pending: kind 0, the pixel count parked in the mask
   bool queue = true;
   if (n <= 64u) {
@@ -416,13 +416,13 @@ __device__ __forceinline__ void rec_resolve_block(const uint32_t* __restrict__ i
 }
 
 __global__ __launch_bounds__(kBlock) void k_rec_resolve(const uint32_t* __restrict__ idx, uint32_t W, uint32_t H, uint32_t P, uint32_t tag,
-                                                        int dbg, unsigned long long* __restrict__ mom, TriFrag* __restrict__ frags,
+                                                        unsigned long long* __restrict__ mom, TriFrag* __restrict__ frags,
                                                         uint32_t* __restrict__ big_queue, uint32_t* __restrict__ big_count) {
-  rec_resolve_block(idx, W, H, P, tag, dbg, mom, frags, big_queue, big_count);
+  rec_resolve_block(idx, W, H, P, tag, mom, frags, big_queue, big_count);
 }
-__global__ __launch_bounds__(kBlock) void k_rec_resolve_group(RecGroup g, uint32_t W, uint32_t H, uint32_t P, int dbg) {
+__global__ __launch_bounds__(kBlock) void k_rec_resolve_group(RecGroup g, uint32_t W, uint32_t H, uint32_t P) {
   const RecImage& r = g.im[blockIdx.y];
-  rec_resolve_block(r.idx, W, H, P, r.tag, dbg, r.mom, r.frags, r.big_queue, r.big_count);
+  rec_resolve_block(r.idx, W, H, P, r.tag, r.mom, r.frags, r.big_queue, r.big_count);
 }
 
 // Pixels of the sparse primitives (k_rec_big), in pixel order: Mesh.h:94-106 with one float atomic per class.  One thread per pixel;
@@ -618,8 +618,7 @@ void ImageRecords::release() {
 // sweep over all P primitives (24 bytes each) is not what the call costs: up to eight primitives per pixel (cfg5: 2.3); beyond,
 // passes A / B and their per-pixel clear stay O(pixels).
 static bool use_moments(uint64_t W, uint64_t H, uint64_t P) {
-  static const bool off = getenv("SMESH_REC_MOMENTS") && atoi(getenv("SMESH_REC_MOMENTS")) == 0;
-  return !off && W >= 16 && H >= 16 && W < 16384 && H < 16384 && W * H < (1ull << kMomCountBits) && P <= 8 * W * H;
+  return W >= 16 && H >= 16 && W < 16384 && H < 16384 && W * H < (1ull << kMomCountBits) && P <= 8 * W * H;
 }
 
 int image_records_build(DeviceCtx* ctx, ImageRecords& r, const uint32_t* d_idx, uint64_t W, uint64_t H, uint64_t P) {
@@ -647,13 +646,12 @@ int image_records_build(DeviceCtx* ctx, ImageRecords& r, const uint32_t* d_idx, 
   if (r.moments) {
     // frags may hold the last image's records: pass R rewrites whatever differs
     r.clean = false;
-    static const int dbg = SMESH_ABL_ENV("SMESH_REC_DBG");   // development ablation (timing only: wrong results; -DSMESH_ABLATION builds)
     const uint32_t strips_y = (uint32_t)div_up(H, kTY), nstrips = (uint32_t)div_up(W, kSX) * strips_y;
     const uint32_t strips_per_xcd = (uint32_t)div_up(nstrips, 8);
     hipLaunchKernelGGL(k_rec_moments, dim3(strips_per_xcd * 8), dim3(kWave), 0, st, d_idx, (uint32_t)W, (uint32_t)H, (uint32_t)P, strips_y, nstrips,
-                       strips_per_xcd, r.tag, dbg, r.mom, r.frags, r.big_count);
+                       strips_per_xcd, r.tag, r.mom, r.frags, r.big_count);
     hipLaunchKernelGGL(k_rec_resolve, dim3((uint32_t)div_up(P ? P : 1, kBlock)), dim3(kBlock), 0, st, d_idx, (uint32_t)W, (uint32_t)H, (uint32_t)P,
-                       r.tag, dbg, r.mom, r.frags, r.big_queue, r.big_count);
+                       r.tag, r.mom, r.frags, r.big_queue, r.big_count);
     r.tag ^= 6u;      // 2 <-> 4
     SMESH_HIP(hipGetLastError());
     return SMESH_OK;
@@ -709,14 +707,13 @@ bool image_records_build_group(DeviceCtx* ctx, ImageRecords* const* recs, const 
     g.im[i] = RecImage{d_idx[i], nullptr, nullptr, r.mom, r.frags, r.big4, r.big_queue, r.big_count, r.tag};
     r.tag ^= 6u;      // 2 <-> 4
   }
-  static const int dbg = SMESH_ABL_ENV("SMESH_REC_DBG");
   const uint64_t N = W * H;
   const uint32_t strips_y = (uint32_t)div_up(H, kTY), nstrips = (uint32_t)div_up(W, kSX) * strips_y;
   const uint32_t strips_per_xcd = (uint32_t)div_up(nstrips, 8);
   hipLaunchKernelGGL(k_rec_moments_group, dim3(strips_per_xcd * 8, (uint32_t)n), dim3(kWave), 0, st, g, (uint32_t)W, (uint32_t)H, (uint32_t)P, strips_y,
-                     nstrips, strips_per_xcd, dbg);
+                     nstrips, strips_per_xcd);
   hipLaunchKernelGGL(k_rec_resolve_group, dim3((uint32_t)div_up(P ? P : 1, kBlock), (uint32_t)n), dim3(kBlock), 0, st, g, (uint32_t)W, (uint32_t)H,
-                     (uint32_t)P, dbg);
+                     (uint32_t)P);
   const uint32_t eg = (uint32_t)std::min<uint64_t>(div_up(N, kBlock), (uint64_t)std::max(1, ctx->num_cus / n));
   hipLaunchKernelGGL(k_rec_extent_group, dim3(eg, (uint32_t)n), dim3(kBlock), 0, st, g, N, (uint32_t)H, (uint32_t)P);
   if (hipGetLastError() != hipSuccess) *status = fail(SMESH_ERR_RUNTIME, "image records: group launch failed");

@@ -304,8 +304,6 @@ struct RasterArgs {
                               // triangle renderer in its own face order: k_fuse_tri* read the plane for queued triangles -- big_count[0] -- and
                               // when the masks need checking -- big_count[1]): a view with neither does not write it (8.3 MB per 1080p view).
                               // 2 = each view of a group for itself, 1 = one decision for the group's launch (plane_optional_level)
-  int dbg;                    // development ablation (SMESH_RDBG) of k_raster_frag: 1 = no stores, 2 = setup only, 4 = + coverage,
-                              // 8 = + slot reservation, 16 = grouping without the reservation atomics
 };
 
 // Key image layout: same (W,H) y-fastest order as the output planes.  (A 4 x 4 blocked layout was tried to
@@ -497,7 +495,6 @@ __device__ __forceinline__ unsigned long long shade_key(const RasterArgs& a, uin
 __device__ __forceinline__ void emit(const RasterArgs& a, uint64_t f, const Tri& t, int x, int y) {
   const unsigned long long key = shade_key(a, f, t, x, y);
   if (key == kNullKey) return;
-  if (SMESH_ABL(a.dbg) & 1) { if (key == 12345ull) a.keys[0] = key; return; }
   atomicMin(&a.keys[key_index((uint32_t)x, (uint32_t)y, a.H)], key);
 }
 
@@ -527,14 +524,14 @@ __global__ void k_raster_small(RasterArgs a) {
       push_mid(a, f, bw * bh);
       rec.kind = 2;
       rec.mask = (unsigned long long)(uint32_t)t.x1 | ((unsigned long long)(uint32_t)t.y1 << 16);
-    } else if (!(SMESH_ABL(a.dbg) & 2)) {
+    } else {
       unsigned long long mask = 0ull;
       for (int dx = 0; dx < bw; dx++)
         for (int dy = 0; dy < bh; dy++) {
           const unsigned long long key = shade_key(a, f, t, t.x0 + dx, t.y0 + dy);
           if (key != kNullKey) {
             mask |= 1ull << (dx * 8 + dy);
-            if (!(SMESH_ABL(a.dbg) & 1)) atomicMin(&a.keys[key_index((uint32_t)(t.x0 + dx), (uint32_t)(t.y0 + dy), a.H)], key);
+            atomicMin(&a.keys[key_index((uint32_t)(t.x0 + dx), (uint32_t)(t.y0 + dy), a.H)], key);
           }
         }
       rec.kind = mask ? 1 : 0;
@@ -564,7 +561,7 @@ __global__ __launch_bounds__(256) void k_raster_big(RasterArgs a, uint32_t chunk
           const int y = t.y0 + cy + ty;
           if (y > t.y1) continue;
           const unsigned long long key = shade_piece_key(a, f, pc, x, y);
-          if (key != kNullKey && !(SMESH_ABL(a.dbg) & 1)) atomicMin(&a.keys[key_index((uint32_t)x, (uint32_t)y, a.H)], key);
+          if (key != kNullKey) atomicMin(&a.keys[key_index((uint32_t)x, (uint32_t)y, a.H)], key);
         }
       }
     }
@@ -665,7 +662,7 @@ __device__ __forceinline__ unsigned long long emit_cover(const RasterArgs& a, co
   const Claim4 c = wave_claim_prepare4(T0, n0 | (n1 << 16), n2 | (n3 << 16));
   const uint32_t tot0 = c.tot01 & 0xFFFFu, tot1 = c.tot01 >> 16, tot2 = c.tot23 & 0xFFFFu, tot3 = c.tot23 >> 16;
   uint32_t g0 = 0u, g1 = 0u, g2 = 0u, g3 = 0u;
-  if (!(SMESH_ABL(a.dbg) & 16) && cover != 0ull && lane == c.leader) {   // (ablation bit 16: grouping without the reservations)
+  if (cover != 0ull && lane == c.leader) {
     if (tot0) g0 = atomicAdd(&a.q.count[T0 * kQSub + sub], tot0);
     if (tot1) g1 = atomicAdd(&a.q.count[(T0 + a.q.tiles_y) * kQSub + sub], tot1);
     if (tot2) g2 = atomicAdd(&a.q.count[(T0 + 1u) * kQSub + sub], tot2);
@@ -679,7 +676,6 @@ __device__ __forceinline__ unsigned long long emit_cover(const RasterArgs& a, co
   uint32_t e2 = sq2 + (uint32_t)__shfl((int)g2, c.leader) + (c.pre23 & 0xFFFFu);
   uint32_t e3 = sq3 + (uint32_t)__shfl((int)g3, c.leader) + (c.pre23 >> 16);
   unsigned long long mask = 0ull;
-  if (SMESH_ABL(a.dbg) & 8) cover = 0ull;   // ablation: setup + coverage + slot reservation, no depth / stores
   for (unsigned long long m = cover; m; m &= m - 1ull) {
     const int bit = __ffsll((long long)m) - 1;
     const int dx = bit >> 3, dy = bit & 7;
@@ -703,7 +699,6 @@ __device__ __forceinline__ unsigned long long emit_cover(const RasterArgs& a, co
     const uint32_t e = hy ? (hx ? e3 : e2) : (hx ? e1 : e0);
     const uint32_t lim = (hy ? (hx ? sq3 : sq2) : (hx ? sq1 : sq0)) + a.q.cap;
     e0 += (!hx && !hy) ? 1u : 0u; e1 += (hx && !hy) ? 1u : 0u; e2 += (!hx && hy) ? 1u : 0u; e3 += (hx && hy) ? 1u : 0u;
-    if (SMESH_ABL(a.dbg) & 1) continue;
     // pixel inside its tile: (x mod 32) * 64 + (y mod 64)
     const uint16_t pin = (uint16_t)((((uint32_t)x & (kQW - 1)) * kQH) | ((uint32_t)y & (kQH - 1)));
     if (e < lim) {
@@ -799,7 +794,7 @@ __device__ __forceinline__ void coop_walk(const RasterArgs& a, const Tri& t, con
       const uint32_t tb = jt == 0 ? sb0 : jt == 1 ? sb1 : jt == 2 ? sb2 : jt == 3 ? sb3 : jt == 4 ? sb4 : sb5;
       const uint32_t slot = tb + (uint32_t)((x - xlo) * hy + (y - ylo));
       const uint32_t tile = (uint32_t)jx * a.q.tiles_y + (uint32_t)jy;
-      if (!in_box || (SMESH_ABL(a.dbg) & 1)) continue;
+      if (!in_box) continue;
       if (slot < a.q.cap) {
         const uint64_t e = ((uint64_t)tile * kQSub + sub) * a.q.cap + slot;
         a.q.key[e] = key;
@@ -852,13 +847,13 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
           constexpr int kSub = kLaneBox / 8;
           CX0 = t.x0 + 8 * (part / kSub); CY0 = t.y0 + 8 * (part % kSub);
           const int sw = min(t.x1 - CX0 + 1, 8), sh = min(t.y1 - CY0 + 1, 8);
-          if (sw > 0 && sh > 0 && !(SMESH_ABL(a.dbg) & 2)) cover = walk_box(t, CX0, CY0, sw, sh);
+          if (sw > 0 && sh > 0) cover = walk_box(t, CX0, CY0, sw, sh);
         }
       } else if (owner) {                                        // (the other lanes of a spread triangle have nothing to do with it)
         if (bw <= kMedium && bh <= kMedium && have == 1) medium = true;   // rasterised below by the whole wave
         else q_huge = true;                                      // rasterised by the tile workgroups it overlaps
       }
-    } else if (owner && !(SMESH_ABL(a.dbg) & 2)) {
+    } else if (owner) {
       small = true;
       cover = walk_box(t, t.x0, t.y0, bw, bh);
     }
@@ -916,7 +911,6 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
     if (q_mid && slot[1] < a.big_capacity) a.big_queue[(uint64_t)a.big_capacity + slot[1]] = (uint32_t)f;
     if (q_huge && slot[2] < a.big_capacity) a.huge_queue[slot[2]] = (uint32_t)f;
   }
-  if (SMESH_ABL(a.dbg) & 4) { if (a.frags && f < a.F && owner) { rec.mask = cover; a.frags[f] = rec; } return; }   // ablation: setup + coverage only
   {
     const unsigned long long mask = emit_cover<kTex>(a, t, f, pid, CX0, CY0, cover, sub);
     if (mask && small) rec.kind = 1;
@@ -936,7 +930,7 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
       // balanced, one view per launch: these triangles join the view's list too (from its far end; count in big_count[5]) and k_raster_medium walks them
       // seven to a wave, a lane per sub-box -- the waves of the middle distance of a view from inside held 64 of them each
       const unsigned long long m = __ballot(lanebox);
-      if (m != 0ull && !(SMESH_ABL(a.dbg) & 1)) {
+      if (m != 0ull) {
         const int leader = __ffsll((long long)m) - 1;
         uint32_t base = 0u;
         if (lane == leader) base = atomicAdd(a.big_count + 5, (uint32_t)__popcll(m));
@@ -947,7 +941,7 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
     }
   }
   if ((int)__popcll(__ballot(lanebox)) < kLaneBoxMin) { medium = medium || lanebox; lanebox = false; }
-  if (__ballot(lanebox) != 0ull && !(SMESH_ABL(a.dbg) & 1)) {
+  if (__ballot(lanebox) != 0ull) {
     constexpr int kSub = kLaneBox / 8;
     for (int k = 0; k < kSub * kSub; k++) {
       const int X0 = t.x0 + 8 * (k / kSub), Y0 = t.y0 + 8 * (k % kSub);
@@ -971,7 +965,7 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
       // balanced: the triangle joins the view's list instead (one reservation per wave), k_raster_medium walks the list with the
       // whole chip -- a view from inside the scene has all its medium triangles in a few waves (the near part of the mesh)
       const unsigned long long m = __ballot(medium);
-      if (m != 0ull && !(SMESH_ABL(a.dbg) & 1)) {
+      if (m != 0ull) {
         const int leader = __ffsll((long long)m) - 1;
         uint32_t base = 0u;
         if (lane == leader) base = atomicAdd(a.big_count + 4, (uint32_t)__popcll(m));
@@ -981,7 +975,7 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
       return;
     }
   }
-  if (medium && !(SMESH_ABL(a.dbg) & 1)) coop_reserve(a, t, sub, rb);     // all reservations of the wave first: one memory round trip
+  if (medium) coop_reserve(a, t, sub, rb);     // all reservations of the wave first: one memory round trip
   unsigned long long todo = __ballot(medium);
   while (todo) {
     const int src = __ffsll((long long)todo) - 1;
@@ -1574,31 +1568,31 @@ RasterPath raster_path() {
 
 // May a fuse_view(s) call leave out the index plane of a view that has no queued triangles and no overflow (RasterArgs::idx_optional)?
 // Only where the tile resolve clears the losers out of the records' masks itself: triangle primitives in the caller's face order,
-// fragment-queue path.  SMESH_RASTER_SKIP_PLANE=0 turns it off.
+// fragment-queue path.
 bool plane_optional_allowed(const smesh_renderer* r) {
-  static const bool off = getenv("SMESH_RASTER_SKIP_PLANE") && atoi(getenv("SMESH_RASTER_SKIP_PLANE")) == 0;
-  return !off && !r->texels && !r->prim_id && raster_path() == RasterPath::Frag;
+  return !r->texels && !r->prim_id && raster_path() == RasterPath::Frag;
 }
 
 // RasterArgs::idx_optional for a fuse_view(s) call of this renderer into this aggregator: 0 = the planes are read (not the triangle-order
 // kernels), 1 = they are read only for queued triangles and masks that need checking -- one decision per raster launch (view_needs_planes),
 // 2 = the same, each view for itself: aggregators whose EVERY triangle-order launch is k_fuse_tri (smesh_aggregator_fuses_small_views_by_mask:
 // not the name of the kernel -- 41 .. 48 classes go to k_fuse_tri_any when a launch holds more than two views, which is what the first
-// attempt at level 2 tripped over: seeds 553071 / 702926 of tools/soup_sweep.py, C = 47 / 48).  SMESH_PLANE_LEVEL=1 forces level 1.
+// attempt at level 2 tripped over: seeds 553071 / 702926 of tools/soup_sweep.py, C = 47 / 48).
 int plane_optional_level(smesh_renderer* r, smesh_aggregator* a) {
   if (r->texels || !smesh_aggregator_can_fuse_triangles(a, r->F)) return 0;
-  static const int forced = getenv("SMESH_PLANE_LEVEL") ? atoi(getenv("SMESH_PLANE_LEVEL")) : 0;
-  if (forced == 1) return 1;
   return smesh_aggregator_fuses_small_views_by_mask(a) ? 2 : 1;
 }
 
-// Consecutive triangle blocks per run of an XCD (xcd_block).  SMESH_RASTER_XCD=n sets it; 0: blocks take consecutive triangles in
-// dispatch order, as until round 5.  cfg2, eight views per launch (profiles/r06_raster_experiments.txt): k_raster_frag_group fetches
-// 149.6 MB with 0, 79.1 MB with 8 (x 2: gfx950's FETCH_SIZE unit) -- 562 -> 422 MB of traffic per launch -- and takes 195 -> 191 us; runs of
-// 2 / 32 / 128: 195.5 / 201 / 211 us.
-uint32_t raster_xcd_run() {
-  static const uint32_t run = getenv("SMESH_RASTER_XCD") ? (uint32_t)std::max(0, atoi(getenv("SMESH_RASTER_XCD"))) : 8u;
-  return run;
+// Consecutive triangle blocks per run of an XCD (xcd_block) in launches of 64 blocks and more (smaller ones: blocks take consecutive
+// triangles in dispatch order).  cfg2, eight views per launch (profiles/r06_raster_experiments.txt): k_raster_frag_group fetches
+// 149.6 MB in dispatch order, 79.1 MB with runs of 8 (x 2: gfx950's FETCH_SIZE unit) -- 562 -> 422 MB of traffic per launch -- and takes
+// 195 -> 191 us; runs of 2 / 32 / 128: 195.5 / 201 / 211 us.
+constexpr uint32_t kRasterXcdRun = 8;
+
+// SMESH_FRAG_CAP (test hook): the capacity of a sub-queue, 0 when unset.
+uint64_t frag_cap_forced() {
+  const char* e = getenv("SMESH_FRAG_CAP");
+  return e ? std::max<uint64_t>(1, (uint64_t)atoll(e)) : 0u;
 }
 
 // Per-tile fragment queues (kQSub sub-queues each).  Capacity per tile: 16 fragments per pixel of the tile
@@ -1608,9 +1602,9 @@ uint32_t raster_xcd_run() {
 bool ensure_queues(smesh_renderer* r, smesh_renderer::ViewScratch& vs, uint64_t W, uint64_t H, hipStream_t st, int* status) {
   *status = SMESH_OK;
   const uint64_t tiles_x = div_up(W, kQW), tiles_y = div_up(H, kQH), ntiles = tiles_x * tiles_y;
-  uint64_t cap = 16ull * kQPixels / kQSub;   // per sub-queue
-  if (const char* e = getenv("SMESH_FRAG_CAP")) cap = std::max<uint64_t>(1, (uint64_t)atoll(e));
-  else {
+  uint64_t cap = frag_cap_forced();   // per sub-queue
+  if (!cap) {
+    cap = 16ull * kQPixels / kQSub;
     const uint64_t budget = 8ull << 30;
     if (ntiles * kQSub * cap * 10 > budget) cap = budget / (ntiles * kQSub * 10);
     if (cap < 256) return false;
@@ -1680,7 +1674,7 @@ double depth_spread(const smesh_renderer* r, const smesh_camera_t* cam) {
 // beyond 24 pixels) 0.100 / 0.122, 90 000 (half of them within 8) 0.092 / 0.100.  The views of a group fill the chip with waves of 32
 // or 64 triangles: 40 000 triangles 0.080 / 0.085 per view, 90 000 0.077 / 0.113.
 bool want_spread(const smesh_renderer* r, const smesh_camera_t* cam, int nviews) {
-  static const int knob = getenv("SMESH_RASTER_SPREAD") ? atoi(getenv("SMESH_RASTER_SPREAD")) : -1;
+  static const int knob = env_int("SMESH_RASTER_SPREAD", -1);
   if (knob == 0 || !cam) return false;
   if (knob == 1) return true;
   if (nviews > 1) return false;
@@ -1699,12 +1693,11 @@ RasterArgs raster_args(smesh_renderer* r, smesh_renderer::ViewScratch& vs, int s
   a.huge_queue = vs.huge_queue;
   a.med_queue = vs.med_queue;
   {   // SMESH_RASTER_BALANCE=0 / 1 forces; else for views from inside or close to the scene (depth_spread)
-    static const int knob = getenv("SMESH_RASTER_BALANCE") ? atoi(getenv("SMESH_RASTER_BALANCE")) : -1;
+    static const int knob = env_int("SMESH_RASTER_BALANCE", -1);
     a.balance = (vs.med_queue && (knob >= 0 ? knob != 0 : (cam && depth_spread(r, cam) > 6.0))) ? (nviews > 1 ? 1u : 2u) : 0u;
   }
   a.frags = r->side[side].frags;
   a.kinds = r->side[side].kinds;
-  { static const int rdbg = SMESH_ABL_ENV("SMESH_RDBG"); a.dbg = rdbg; }
   a.q = FragQueues();
   a.idx_optional = 0u;
   a.tpw = 64;   // small meshes: fewer triangles per wave, at least ~kMinWaves waves
@@ -1712,15 +1705,14 @@ RasterArgs raster_args(smesh_renderer* r, smesh_renderer::ViewScratch& vs, int s
   // boxes over 8 x 8 are mostly the ones a lane walks itself, sub-box by sub-box (raster_frag_64), and a round of that costs the same
   // for 16 lanes as for 64 -- 1080p, fuse_views, ms per view: 90 000 triangles 0.086 -> 0.077, 40 000 triangles 0.100 -> 0.081.
   // Coarser meshes need the waves for the cooperative loop (10 000 triangles: 0.084 with 2 048 waves per view, 0.091 with 1 024).
-  static const uint64_t min_waves_env = getenv("SMESH_RASTER_MIN_WAVES") ? (uint64_t)std::max(1, atoi(getenv("SMESH_RASTER_MIN_WAVES"))) : 0u;
   const bool fine = r->F >= 32768u;
-  const uint64_t min_waves = min_waves_env ? min_waves_env : (fine ? 1024u : 2048u);
+  const uint64_t min_waves = fine ? 1024u : 2048u;
   const uint64_t launch_views = fine ? (uint64_t)std::max(1, nviews) : 1u;
   while (a.tpw > 1 && launch_views * r->F / a.tpw < min_waves) a.tpw >>= 1;
   a.groups = 1;  // (frag_groups() decides per launch)
   a.spread = 0u;
   {   // (SMESH_RASTER_WG_PUSH=0 / 1 forces)
-    static const int knob = getenv("SMESH_RASTER_WG_PUSH") ? atoi(getenv("SMESH_RASTER_WG_PUSH")) : -1;
+    static const int knob = env_int("SMESH_RASTER_WG_PUSH", -1);
     a.wg_push = knob >= 0 ? (uint32_t)(knob != 0) : (cam && typical_edge_pixels(r, cam) >= 5.0 ? 1u : 0u);
   }
   if (want_spread(r, cam, nviews)) { a.spread = (uint32_t)kSpread; a.tpw = (uint32_t)kSpreadTris; }
@@ -1732,7 +1724,7 @@ RasterArgs raster_args(smesh_renderer* r, smesh_renderer::ViewScratch& vs, int s
 // meshes of four million triangles and more, when the launch still has four waves for every slot of the chip (1024 SIMDs x 5); else one.
 // SMESH_RASTER_GROUPS=n forces n.
 uint32_t frag_groups(uint64_t F, int views, uint32_t tpw) {
-  static const int knob = getenv("SMESH_RASTER_GROUPS") ? atoi(getenv("SMESH_RASTER_GROUPS")) : 0;
+  static const int knob = env_int("SMESH_RASTER_GROUPS", 0);
   if (tpw != 64u) return 1u;
   if (knob >= 1) return (uint32_t)knob;
   return (F >= 4000000u && (uint64_t)views * div_up(F, 256u) >= 20480u) ? 4u : 1u;
@@ -1770,7 +1762,7 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
       a.q = vs.fq;
       {
         const uint32_t nblocks = (uint32_t)div_up(div_up(r->F, a.tpw), 4);
-        const uint32_t chunk = nblocks >= 64u ? raster_xcd_run() : 0u;
+        const uint32_t chunk = nblocks >= 64u ? kRasterXcdRun : 0u;
         const dim3 grid(chunk ? 8u * xcd_slots(nblocks, chunk) : nblocks);
         switch (raster_mode(a)) {
           case 7:  hipLaunchKernelGGL(k_raster_frag<7>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
@@ -1822,7 +1814,7 @@ hipError_t alloc_scratch(smesh_renderer* r, int i) {
 // Can a W x H view go through fragment queues of a size that kMaxGroup view slots can afford?  (ensure_queues' sizing rule.)
 bool queues_fit_group(uint64_t W, uint64_t H) {
   if (raster_path() != RasterPath::Frag) return false;
-  if (getenv("SMESH_FRAG_CAP")) return true;
+  if (frag_cap_forced()) return true;
   const uint64_t ntiles = div_up(W, kQW) * div_up(H, kQH);
   const uint64_t cap = 16ull * kQPixels / kQSub;
   return ntiles * kQSub * cap * 10 <= (2ull << 30);
@@ -1911,19 +1903,16 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   ProfScope prof(ctx, SMESH_PROF_RASTER, st);
   hipLaunchKernelGGL(k_project_vertices_group, dim3((uint32_t)div_up(r->V, 256)), dim3(256), 0, st, pg);
   SMESH_HIP(hipGetLastError());
-  // (experiment knob: an LDS pad caps the rasteriser's workgroups per CU when it runs beside a fusion launch -- group pipeline)
-  static const unsigned raster_pad = getenv("SMESH_RASTER_LDS_PAD") ? (unsigned)atoi(getenv("SMESH_RASTER_LDS_PAD")) : 0u;
   {
-    rg.chunk = rg.blocks_per_view >= 64u ? raster_xcd_run() : 0u;
+    rg.chunk = rg.blocks_per_view >= 64u ? kRasterXcdRun : 0u;
     const dim3 grid(rg.chunk ? 8u * xcd_slots(rg.blocks_per_view, rg.chunk) * (uint32_t)n : (uint32_t)n * rg.blocks_per_view);
-    const unsigned pad = st == ctx->raster_stream ? raster_pad : 0u;
     switch (raster_mode(rg.view[0])) {     // (one mode per launch: render_group_into made the views agree)
-      case 7:  hipLaunchKernelGGL(k_raster_frag_group<7>, grid, dim3(256), pad, st, rg); break;
-      case 5:  hipLaunchKernelGGL(k_raster_frag_group<5>, grid, dim3(256), pad, st, rg); break;
-      case 4:  hipLaunchKernelGGL(k_raster_frag_group<4>, grid, dim3(256), pad, st, rg); break;
-      case 3:  hipLaunchKernelGGL(k_raster_frag_group<3>, grid, dim3(256), pad, st, rg); break;
-      case 1:  hipLaunchKernelGGL(k_raster_frag_group<1>, grid, dim3(256), pad, st, rg); break;
-      default: hipLaunchKernelGGL(k_raster_frag_group<0>, grid, dim3(256), pad, st, rg); break;
+      case 7:  hipLaunchKernelGGL(k_raster_frag_group<7>, grid, dim3(256), 0, st, rg); break;
+      case 5:  hipLaunchKernelGGL(k_raster_frag_group<5>, grid, dim3(256), 0, st, rg); break;
+      case 4:  hipLaunchKernelGGL(k_raster_frag_group<4>, grid, dim3(256), 0, st, rg); break;
+      case 3:  hipLaunchKernelGGL(k_raster_frag_group<3>, grid, dim3(256), 0, st, rg); break;
+      case 1:  hipLaunchKernelGGL(k_raster_frag_group<1>, grid, dim3(256), 0, st, rg); break;
+      default: hipLaunchKernelGGL(k_raster_frag_group<0>, grid, dim3(256), 0, st, rg); break;
     }
     if ((raster_mode(rg.view[0]) & 3) != 0 && rg.view[0].balance) {
       const uint32_t per_view = std::max(64u, 4u * (uint32_t)std::max(1, ctx->num_cus) / (uint32_t)n);
@@ -2062,14 +2051,10 @@ double box_extent_bound(const smesh_renderer::Bounds& b, const smesh_camera_t* c
 }
 // A box of n pixel centres needs an extent of at least n - 1: no triangle crosses the near plane or has a box of more than kMedium
 // pixels a side (the queue of k_raster_huge stays empty) ...
-double box_extent_bound(const smesh_renderer* r, const smesh_camera_t* cam) {
-  static const bool off = getenv("SMESH_HUGE_ALWAYS") && atoi(getenv("SMESH_HUGE_ALWAYS")) != 0;
-  return off ? INFINITY : box_extent_bound(r->bounds, cam);
-}
-bool no_huge_possible(const smesh_renderer* r, const smesh_camera_t* cam) { return box_extent_bound(r, cam) <= (double)kMedium - 4.0; }
+bool no_huge_possible(const smesh_renderer* r, const smesh_camera_t* cam) { return box_extent_bound(r->bounds, cam) <= (double)kMedium - 4.0; }
 // ... or of more than 8 pixels a side: the big-triangle queue of the view (and with it the list of medium triangles) stays empty -- a
 // mesh of millions of triangles seen from outside (cfg4: 3.5 pixels, cfg5: 5.6; not cfg2: 13 - 24 against boxes that do stay under 8).
-bool no_big_possible(const smesh_renderer* r, const smesh_camera_t* cam) { return box_extent_bound(r, cam) <= 6.5; }
+bool no_big_possible(const smesh_renderer* r, const smesh_camera_t* cam) { return box_extent_bound(r->bounds, cam) <= 6.5; }
 
 int create_common(const float* vertices, uint64_t V, const int32_t* faces, uint64_t F, int device,
                   smesh_renderer** out) {
@@ -2477,7 +2462,7 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
   }
   DeviceCtx* ctx = r->ctx;
   if (smesh_aggregator_ctx(a) != ctx) return fail(SMESH_ERR_INVALID, "renderer and aggregator live on different devices");
-  static const bool pairs_off = getenv("SMESH_FUSE_PAIRS") && atoi(getenv("SMESH_FUSE_PAIRS")) == 0;
+  static const bool pairs_off = env_int("SMESH_FUSE_PAIRS", 1) == 0;
   bool pairable;
   int tri_path;
   {
@@ -2486,13 +2471,12 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
     pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && !r->texels && r->F != 0 && smesh_aggregator_can_fuse_triangles(a, r->F) &&
                smesh_aggregator_can_fuse_pair(a);
   }
-  static const bool raster_pairs_off = getenv("SMESH_RASTER_PAIRS") && atoi(getenv("SMESH_RASTER_PAIRS")) == 0;
-  static const int group_max = getenv("SMESH_RASTER_GROUP") ? std::min(kMaxGroup, std::max(2, atoi(getenv("SMESH_RASTER_GROUP")))) : kMaxGroup;
+  static const bool raster_pairs_off = env_int("SMESH_RASTER_PAIRS", 1) == 0;
   uint64_t i = 0;
   while (i < n) {
     // Rasterise a GROUP of the remaining views with one launch per stage (any renderer, any aggregator, device images), then
     // fuse them two by two where the aggregator has the two-view kernel, else one by one.
-    int gn = (int)std::min<uint64_t>((uint64_t)group_max, n - i);
+    int gn = (int)std::min<uint64_t>((uint64_t)kMaxGroup, n - i);
     bool grouped = !raster_pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0 && r->V != 0 && gn >= 2;
     for (int v = 0; v < gn && grouped; v++) grouped = queues_fit_group(cams[i + v].width, cams[i + v].height);
     if ((!pairable && !grouped) || i + 1 >= n) {
@@ -2557,7 +2541,7 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
       }
     }
     // texel renderers: the views of the group in ONE fusion launch (a triangle's texel rows make one round trip for all of them)
-    static const bool texel_multi_off = getenv("SMESH_TEXEL_MULTI") && atoi(getenv("SMESH_TEXEL_MULTI")) == 0;
+    static const bool texel_multi_off = env_int("SMESH_TEXEL_MULTI", 1) == 0;
     bool texel_multi = false;
     if (grouped && !pairable && r->texels && !texel_multi_off) texel_multi = smesh_aggregator_can_fuse_texels(a, r->num_primitives);
     if (texel_multi) {
@@ -2595,7 +2579,7 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
           rv[v] = RenderedView{sd.frags, sd.big_queue, sd.big_count, static_cast<const uint32_t*>(r->fused[base + j + v].ptr), probs[k],
                                weights ? weights[k] : nullptr, cams[k].width, cams[k].height, 0, 0, true};
           rv[v].no_big = no_big_possible(r, &cams[k]);
-          rv[v].fine = box_extent_bound(r, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
+          rv[v].fine = box_extent_bound(r->bounds, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
         }
         SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv));
         j += nv;
@@ -2619,9 +2603,8 @@ static int fuse_held_part(smesh_renderer* r, smesh_aggregator* a, int part) {
   DeviceCtx* ctx = r->ctx;
   const smesh_renderer::HeldJob& h = r->held;
   const int max_nv = smesh_aggregator_max_fused_views(a);
-  static const int group_max = getenv("SMESH_RASTER_GROUP") ? std::min(kMaxGroup, std::max(2, atoi(getenv("SMESH_RASTER_GROUP")))) : kMaxGroup;
-  for (int i = 0; i < h.n; i += group_max) {
-    const int gn = std::min(group_max, h.n - i);
+  for (int i = 0; i < h.n; i += kMaxGroup) {
+    const int gn = std::min(kMaxGroup, h.n - i);
     ProfScope fuse_region(ctx, SMESH_PROF_FUSE_SCATTER);
     for (int j = 0; j < gn;) {
       int nv = 1;
@@ -2654,11 +2637,10 @@ int smesh_fuse_views_begin(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
   DeviceCtx* ctx = r->ctx;
   if (smesh_aggregator_ctx(a) != ctx) return fail(SMESH_ERR_INVALID, "renderer and aggregator live on different devices");
   const uint64_t P = smesh_aggregator_primitives(a);
-  static const bool ranges_off = getenv("SMESH_FUSE_RANGES") && atoi(getenv("SMESH_FUSE_RANGES")) == 0;
   bool ranged;
   {
     std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
-    ranged = !ranges_off && nparts > 1 && n >= 1 && n <= (uint64_t)kHeld && memkind == SMESH_MEM_DEVICE && !r->texels && r->F != 0 &&
+    ranged = nparts > 1 && n >= 1 && n <= (uint64_t)kHeld && memkind == SMESH_MEM_DEVICE && !r->texels && r->F != 0 &&
              r->V != 0 && r->prim_id == nullptr && smesh_aggregator_can_fuse_triangles(a, r->F);
   }
   for (uint64_t i = 0; i < n && ranged; i++) ranged = queues_fit_group(cams[i].width, cams[i].height);
@@ -2685,9 +2667,8 @@ int smesh_fuse_views_begin(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
   for (uint64_t i = 0; i < n; i++) {
     h.probs[i] = probs[i]; h.weights[i] = weights ? weights[i] : nullptr; h.W[i] = cams[i].width; h.H[i] = cams[i].height;
   }
-  static const int group_max = getenv("SMESH_RASTER_GROUP") ? std::min(kMaxGroup, std::max(2, atoi(getenv("SMESH_RASTER_GROUP")))) : kMaxGroup;
-  for (int i = 0; i < h.n; i += group_max)
-    SMESH_TRY(render_group_into(r, &cams[i], std::min(group_max, h.n - i), ctx->stream, 0, kSlots + i, /*idx_optional: ranged => k_fuse_tri* */ plane_optional_level(r, a)));
+  for (int i = 0; i < h.n; i += kMaxGroup)
+    SMESH_TRY(render_group_into(r, &cams[i], std::min(kMaxGroup, h.n - i), ctx->stream, 0, kSlots + i, /*idx_optional: ranged => k_fuse_tri* */ plane_optional_level(r, a)));
   SMESH_TRY(fuse_held_part(r, a, 0));
   smesh_note_fuse(smesh_aggregator_fuse_kernel_name(a, false), "render-records");
   r->fused_seq += n;
