@@ -118,6 +118,19 @@ SIGNATURES = {
     "smesh_memcpy": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_int, c_int]),
 }
 
+# Label dtypes of include/smesh_labels.h (SMESH_LBL_*), by numpy dtype string
+LBL_CODES = {"uint8": 0, "int8": 1, "uint16": 2, "int16": 3, "uint32": 4, "int32": 5, "uint64": 6, "int64": 7}
+
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_labels.h: the label-image entry points, a product-only
+# extension of the ABI that the CPU oracle does not implement (which is why they are not in SIGNATURES)
+EXT_SIGNATURES = {
+    "smesh_fuse_view_labels": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_void_p, c_int, P(ctypes.c_int64), c_void_p, c_int]),
+    "smesh_fuse_views_labels": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, P(c_void_p), c_int, P(ctypes.c_int64), P(c_void_p), c_int]),
+    "smesh_aggregator_add_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                            c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                            c_void_p, P(ctypes.c_int64), c_int, c_u64, c_u64]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -245,7 +258,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in SIGNATURES.items():
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -1,5 +1,6 @@
 // context.cpp -- device contexts, error strings, memory helpers and the timing hooks of the C ABI.
 #include "common.hpp"
+#include "labels_scratch.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -322,6 +323,8 @@ int smesh_set_option(const char* name, int64_t value) {
 int smesh_get_option(const char* name, int64_t* value) {
   if (!name || !value) return fail(SMESH_ERR_INVALID, "NULL argument");
   if (!strcmp(name, "group_pipeline")) { *value = opt_group_pipeline() ? 1 : 0; return SMESH_OK; }
+  // read-only: up to this class count k_fuse_tri_labels keeps a wave's rows in LDS, beyond it read-modify-writes them in global memory
+  if (!strcmp(name, "labels_lds_max_classes")) { *value = (int64_t)kLabelsLdsMaxC; return SMESH_OK; }
   return fail(SMESH_ERR_INVALID, std::string("unknown option: ") + name);
 }
 

@@ -27,6 +27,7 @@
 //   * lanes then own (group, class) elements, add up the <= 4 run totals of the chain out of LDS and issue
 //     ONE float atomic each: 19 consecutive lanes cover one 128-byte accumulator row = one request.
 #include "common.hpp"
+#include "labels_scratch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -2142,6 +2143,7 @@ struct smesh_aggregator {
   Scratch out_tmp;                       // get(): normalised result before the D2H copy
   ImageRecords rec;                      // add() on an image the library did not render: per-primitive records (image_records.hip)
   ImageRecords rec_many[7];              // add_many(): the record sets of the further images of a group of up to eight (rec is the first)
+  LabelScratch labels;                   // add_labels / fuse_view(s)_labels (fusion_labels.hip): staged and narrowed label planes, one-hot expansion
   // Exchange of row ranges beside the fusion (smesh_allreduce_rows, comm.cpp): ev_part marks the main stream where the range became
   // final, ev_xchg the exchange stream behind the range's collective; xchg_pending: the main stream has not yet waited for ev_xchg.
   hipEvent_t ev_part = nullptr, ev_xchg = nullptr;
@@ -2750,6 +2752,15 @@ int smesh_aggregator_acc(smesh_aggregator* a, float** acc, uint64_t* num_floats,
 }
 uint32_t smesh_aggregator_classes(smesh_aggregator* a) { return a->C; }
 uint64_t smesh_aggregator_primitives(smesh_aggregator* a) { return a->P; }
+LabelScratch& smesh_aggregator_label_scratch(smesh_aggregator* a) { return a->labels; }
+// What the label kernels (fusion_labels.hip) update and with which weights; every out pointer may be null.
+void smesh_aggregator_label_target(smesh_aggregator* a, float** acc, uint64_t* P, uint32_t* C, int* kind, float* iew) {
+  if (acc) *acc = a->acc;
+  if (P) *P = a->P;
+  if (C) *C = a->C;
+  if (kind) *kind = a->kind;
+  if (iew) *iew = a->iew;
+}
 
 // The main stream waits (on the device, not the host) for the collectives that smesh_allreduce_rows put on the exchange stream.
 // Called by every entry point that reads or writes the accumulator on the main stream, with the aggregator and context locked.
@@ -2893,6 +2904,7 @@ int smesh_aggregator_destroy(smesh_aggregator_t* a) {
     s->release();
   a->rec.release();
   for (auto& r : a->rec_many) r.release();
+  a->labels.release();
   delete a;
   return SMESH_OK;
 }

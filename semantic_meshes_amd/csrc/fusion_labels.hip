@@ -1,0 +1,663 @@
+// fusion_labels.hip -- fusion of LABEL images (one class index per pixel) instead of class vectors: the kernels, and the entry points of
+// include/smesh_labels.h.  A translation unit of its own: nothing here is seen by k_fuse_tri or its instance files (fuse_tri.inc.hpp is
+// included for its wave helpers only, read-only).
+//
+// Semantics: what the class-vector path gives for one_hot(labels), tf.one_hot's rule (a label outside [0, C) is the all-zero vector).
+// For a pixel of primitive p with label c in range, Mesh.h:90-106 and Fusion.cu:46-76 come down to
+//     n  = pixels of p in this view's index image (don't-care pixels count)
+//     w0 = iew * (1.0f / (float)n) + (1 - iew) * 1.0f
+//     w  = w0 * weight[pixel]                       (1.0f without a weights image)
+//     acc[p][c] = acc[p][c] + 1.0f * w
+// in image order (x major, y fastest), view after view -- for Sum AND Summax (the arg-max of a one-hot row is its label).  Mul and every
+// renderer / image the triangle-order kernel does not serve get the labels expanded on the device (k_labels_onehot) and take the
+// class-vector path unchanged.
+#include <hip/hip_runtime.h>
+
+#include "common.hpp"
+#include "labels_scratch.hpp"
+#include "../../include/smesh_labels.h"
+
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <type_traits>
+
+using namespace smesh;
+
+// fusion.hip
+struct smesh_aggregator;
+DeviceCtx* smesh_aggregator_ctx(smesh_aggregator* a);
+bool smesh_aggregator_can_fuse_triangles(smesh_aggregator* a, uint64_t F);
+int smesh_aggregator_refuse_scattered(smesh_aggregator* a, const char* what);
+void smesh_aggregator_label_target(smesh_aggregator* a, float** acc, uint64_t* P, uint32_t* C, int* kind, float* iew);
+LabelScratch& smesh_aggregator_label_scratch(smesh_aggregator* a);
+// raster.hip
+struct smesh_renderer;
+DeviceCtx* smesh_renderer_ctx(smesh_renderer* r);
+int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* planes,
+                                     const float* const* weights, int label_bytes);
+int smesh_renderer_add_rendered_labels(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* plane, int label_bytes,
+                                       const float* weights, uint64_t W, uint64_t H, int* done);
+
+namespace {
+
+#include "fuse_tri.inc.hpp"
+
+// (kLabelsLdsMaxC, the class count up to which the main waves keep their rows in LDS: labels_scratch.hpp)
+
+// One view as k_fuse_tri_labels sees it (TriView with a label plane in place of the class vectors).
+struct LabelView {
+  const TriFrag* frags;
+  const uint32_t* idx;
+  const void* labels;         // [W][H] of LT, dense; any value >= C is "don't care"
+  const float* weights;       // may be null
+  const uint32_t* big_queue;
+  const uint32_t* big_len;    // [0] queue length, [1] "check the masks against the index plane" flag of the render
+  uint32_t W, H;
+};
+template <int NV>
+struct LabelViews {
+  LabelView v[NV];
+};
+struct LabelFuseArgs {
+  float* acc;                 // [P][C] dense
+  uint64_t F;
+  uint32_t C;
+  float iew;
+  uint32_t big_capacity;
+  uint32_t tri_blocks;        // blocks 0 .. tri_blocks-1 walk the triangles, the next big_blocks the queues of triangles over 8 x 8 pixels
+  uint32_t big_blocks;
+  uint32_t stride;            // IN_LDS: floats between two rows of the LDS block (C | 1)
+};
+
+// Eight consecutive labels (a column of a triangle's 8 x 8 box: y is the fastest axis) in one load at element alignment.
+typedef uint64_t u64_a1 __attribute__((aligned(1)));
+typedef uint64_t u64_a2 __attribute__((aligned(2)));
+template <typename LT>
+struct LabelRun;
+template <>
+struct LabelRun<uint8_t> {
+  uint64_t q;
+  __device__ __forceinline__ void load(const uint8_t* p) { q = *reinterpret_cast<const u64_a1*>(p); }
+  __device__ __forceinline__ uint32_t pick(uint32_t i) const { return (uint32_t)(q >> (8u * i)) & 0xFFu; }
+};
+template <>
+struct LabelRun<uint16_t> {
+  uint64_t lo, hi;
+  __device__ __forceinline__ void load(const uint16_t* p) {
+    lo = *reinterpret_cast<const u64_a2*>(p);
+    hi = *reinterpret_cast<const u64_a2*>(p + 4);
+  }
+  __device__ __forceinline__ uint32_t pick(uint32_t i) const { return (uint32_t)((i < 4u ? lo : hi) >> (16u * (i & 3u))) & 0xFFFFu; }
+};
+
+// Triangles with a box over 8 x 8 pixels in some view of the launch: one wave per queued triangle for ALL its views, first view first,
+// so that no other wave touches its row (the main waves leave such triangles alone).  Lanes go over the box of each view (the record's
+// box, or the 8 x 8 box of a view in which the triangle is small) and test the index plane -- every view of the launch, which is why
+// the raster launch ahead of this kernel writes all planes as soon as one view has a queued triangle (raster.hip, kLabelsPlaneLevel).
+// IN_LDS: a view's hits go to a C-float LDS histogram by LDS float adds, which lane c then adds to element c of the row; else by
+// float atomics to the row itself.  Either way a tree / atomic order: the 1e-5 path, like fuse_box.
+template <typename LT, int NV, bool IN_LDS>
+__device__ __forceinline__ void fuse_big_labels(const LabelFuseArgs& a, const LabelViews<NV>& vw, uint32_t worker, uint32_t nworkers,
+                                                float* __restrict__ hist) {
+  uint32_t len[NV], total = 0u;
+#pragma unroll
+  for (int v = 0; v < NV; v++) { len[v] = min(*vw.v[v].big_len, a.big_capacity); total += len[v]; }
+  const int l = threadIdx.x;
+  const uint32_t C = a.C;
+  // (the walk over the concatenated queues is fuse_big_triangles': `chunk` entries per step, one per lane; a triangle queued by several
+  // views is taken from the queue of the first of them)
+  const uint32_t chunk = max(1u, min((uint32_t)kWave, total / max(nworkers, 1u)));
+  const uint32_t steps = (total + chunk - 1u) / chunk;
+  for (uint32_t step = worker; step < steps; step += nworkers) {
+    const uint32_t q = (uint32_t)l < chunk ? (uint32_t)l * steps + step : total;
+    uint32_t fi = 0u;
+    bool take = false;
+    {
+      uint32_t qq = q;
+      bool located = q >= total;
+      int jsel = -1;
+#pragma unroll
+      for (int j = 0; j < NV; j++) {
+        if (!located) {
+          if (qq < len[j]) { fi = vw.v[j].big_queue[qq]; jsel = j; located = true; }
+          else qq -= len[j];
+        }
+      }
+      if (jsel >= 0 && fi < a.F) {
+        bool mine = false, earlier = false;
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+          if (i <= jsel) {
+            const bool counts = vw.v[i].frags[fi].kind == 2;
+            if (i < jsel) earlier = earlier || counts;
+            else mine = counts;
+          }
+        }
+        take = mine && !earlier;
+      }
+    }
+    unsigned long long todo = __ballot(take);
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fi, src);   // wave-uniform; row = triangle (no re-ordered meshes here)
+      float* __restrict__ row = a.acc + (uint64_t)f * C;
+#pragma unroll
+      for (int j = 0; j < NV; j++) {
+        const TriFrag rec = vw.v[j].frags[f];
+        if (rec.kind == 0) continue;
+        const uint32_t W = vw.v[j].W, H = vw.v[j].H;
+        const int x0 = rec.x0, y0 = rec.y0;
+        int x1, y1;
+        if (rec.kind == 2) { x1 = (int)(rec.mask & 0xFFFFu); y1 = (int)((rec.mask >> 16) & 0xFFFFu); }
+        else { x1 = x0 + 7; y1 = y0 + 7; }
+        x1 = min(x1, (int)W - 1); y1 = min(y1, (int)H - 1);
+        if (x1 < x0 || y1 < y0) continue;
+        const uint32_t bh = (uint32_t)(y1 - y0 + 1);
+        const uint32_t npx = (uint32_t)(x1 - x0 + 1) * bh;
+        const uint32_t* __restrict__ idx = vw.v[j].idx;
+        auto pix_of = [&](uint32_t i) -> uint64_t { return (uint64_t)((uint32_t)x0 + i / bh) * H + ((uint32_t)y0 + i % bh); };
+        uint32_t cnt = 0;
+        for (uint32_t i = l; i < npx; i += kWave) cnt += idx[pix_of(i)] == f ? 1u : 0u;
+        const uint32_t n = wave_sum_u(cnt);
+        if (n == 0) continue;
+        const float w0 = a.iew * (1.0f / (float)n) + (1 - a.iew) * 1.0f;
+        const LT* __restrict__ lab = static_cast<const LT*>(vw.v[j].labels);
+        const float* __restrict__ wts = vw.v[j].weights;
+        if (IN_LDS) {
+          for (uint32_t c = l; c < C; c += kWave) hist[c] = 0.0f;
+          wave_sync();
+        }
+        for (uint32_t i = l; i < npx; i += kWave) {
+          const uint64_t pix = pix_of(i);
+          if (idx[pix] != f) continue;
+          const uint32_t c = (uint32_t)lab[pix];
+          if (c >= C) continue;
+          const float w = w0 * (wts ? wts[pix] : 1.0f);
+          if (IN_LDS) __hip_atomic_fetch_add(&hist[c], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          else unsafeAtomicAdd(&row[c], w);
+        }
+        if (IN_LDS) {
+          wave_sync();
+          for (uint32_t c = l; c < C; c += kWave) {
+            const float h = hist[c];
+            if (h != 0.0f) row[c] = row[c] + h;
+          }
+          wave_sync();   // the histogram is cleared for this wave's next view
+        }
+      }
+    }
+  }
+}
+
+// NV views (1, 2, 4 or 8) of label planes into the accumulator in ONE launch, in order.  Lane = triangle, wave = 64 consecutive rows, as
+// k_fuse_tri; the class count is a run-time value.  IN_LDS: the wave's 64 x C block is streamed into LDS with 16-byte loads (rows
+// `stride` floats apart) and a visible pixel is ONE LDS read-modify-write at row[label] -- in pixel order, view 0 first, so the float32
+// additions are the oracle's -- and the block goes back once for all views.  !IN_LDS: the same read-modify-write on the row in global
+// memory (its one owner is this lane).  Labels: a triangle's <= 8 x 8 box is up to eight runs of <= 8 consecutive labels; the runs of
+// a view are loaded together, one load each, and the labels picked out of them.
+template <typename LT, int NV, bool IN_LDS>
+__global__ __launch_bounds__(kWave) void k_fuse_tri_labels(LabelFuseArgs a, LabelViews<NV> vw) {
+  extern __shared__ __attribute__((aligned(16))) float srow[];
+  const int l = threadIdx.x;
+  const uint32_t C = a.C;
+  if (blockIdx.x >= a.tri_blocks) {
+    fuse_big_labels<LT, NV, IN_LDS>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks, srow);
+    return;
+  }
+  const uint64_t f0 = (uint64_t)blockIdx.x * kWave;
+  const uint64_t f = f0 + l;
+  // per view: box origin (x0 | y0 << 16) and the mask of this triangle's VISIBLE pixels inside its <= 8 x 8 box
+  uint32_t org[NV];
+  unsigned long long msk[NV];
+  bool big = false;   // a box over 8 x 8 in some view: the triangle is a tail wave's for all its views, and so is its row
+#pragma unroll
+  for (int v = 0; v < NV; v++) { org[v] = 0u; msk[v] = 0ull; }
+  if (f < a.F) {
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      const TriFrag rec = vw.v[v].frags[f];
+      org[v] = (uint32_t)rec.x0 | ((uint32_t)rec.y0 << 16);
+      msk[v] = rec.kind == 1 ? rec.mask : 0ull;
+      big = big || rec.kind == 2;
+    }
+  }
+  if (big) {
+#pragma unroll
+    for (int v = 0; v < NV; v++) msk[v] = 0ull;
+  }
+  // the masks of a view whose render says they need checking (fragment-queue overflow, direct rasteriser) are checked against that
+  // view's index plane, which such a view always writes (k_fuse_tri's pass 1)
+#pragma unroll
+  for (int v = 0; v < NV; v++) {
+    if (vw.v[v].big_len[1] == 0u) continue;
+    const uint32_t* __restrict__ idx = vw.v[v].idx;
+    unsigned long long m = msk[v], win = 0ull;
+    while (m) {
+      const int k = __ffsll((long long)m) - 1;
+      m &= m - 1ull;
+      const uint64_t pix = (uint64_t)((org[v] & 0xFFFFu) + (uint32_t)(k >> 3)) * vw.v[v].H + (org[v] >> 16) + (uint32_t)(k & 7);
+      if (idx[pix] == (uint32_t)f) win |= 1ull << k;
+    }
+    msk[v] = win;
+  }
+  unsigned long long any_win = 0ull;
+#pragma unroll
+  for (int v = 0; v < NV; v++) any_win |= msk[v];
+  if (__ballot(any_win != 0ull) == 0ull) return;   // nothing of these 64 triangles is visible: rows untouched
+
+  const uint32_t S = a.stride;
+  const int nrows = (int)min((uint64_t)kWave, a.F - f0);
+  float* __restrict__ blk = a.acc + f0 * C;
+  const uint32_t nq = (uint32_t)kWave * C / 4u;   // float4 of a full block (64 * C floats: a multiple of four, 256-byte aligned)
+  if (IN_LDS) {
+    if (nrows == kWave) {
+      const f4* b4 = reinterpret_cast<const f4*>(blk);
+      for (uint32_t q0 = 0; q0 < nq; q0 += 4u * kWave) {
+        f4 t[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) t[j] = b4[min(q0 + (uint32_t)j * kWave + (uint32_t)l, nq - 1u)];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const uint32_t q = q0 + (uint32_t)j * kWave + (uint32_t)l;
+          if (q < nq) {
+            uint32_t r = q * 4u / C, c = q * 4u - r * C;
+            const float e[4] = {t[j].x, t[j].y, t[j].z, t[j].w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+              srow[r * S + c] = e[k];
+              if (++c == C) { c = 0u; r++; }
+            }
+          }
+        }
+      }
+    } else {
+      for (uint32_t q = l; q < (uint32_t)nrows * C; q += kWave) { const uint32_t r = q / C; srow[r * S + (q - r * C)] = blk[q]; }
+    }
+    wave_sync();
+  }
+
+  auto fuse_pixels = [&](auto* row) {
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+      const unsigned long long m = msk[v];
+      if (m == 0ull) continue;
+      const uint32_t nv = (uint32_t)__popcll(m);   // this primitive's pixels in this view: the histogram entry of Mesh.h:90-93
+      const float image_weight = 1.0f / ((float)nv);                           // Mesh.h:100
+      const float pixel_w = 1.0f;                                              // :101
+      const float w0 = a.iew * image_weight + (1 - a.iew) * pixel_w;           // :102
+      const uint32_t x0 = org[v] & 0xFFFFu, y0 = org[v] >> 16, H = vw.v[v].H;
+      const uint64_t last_run = (uint64_t)vw.v[v].W * H - 8u;   // (a run is clamped into the plane: the host refuses planes under 8 pixels)
+      const LT* __restrict__ lab = static_cast<const LT*>(vw.v[v].labels);
+      const float* __restrict__ wts = vw.v[v].weights;
+      LabelRun<LT> run[8];
+      uint32_t shift[8];
+#pragma unroll
+      for (int dx = 0; dx < 8; dx++) {
+        shift[dx] = 0u;
+        if ((m >> (dx * 8)) & 0xFFull) {
+          const uint64_t s = (uint64_t)(x0 + (uint32_t)dx) * H + y0;
+          const uint64_t sc = min(s, last_run);
+          shift[dx] = (uint32_t)(s - sc);
+          run[dx].load(lab + sc);
+        }
+      }
+#pragma unroll
+      for (int dx = 0; dx < 8; dx++) {
+        uint32_t col = (uint32_t)(m >> (dx * 8)) & 0xFFu;
+        while (col) {
+          const uint32_t dy = (uint32_t)__ffs((int)col) - 1u;
+          col &= col - 1u;
+          const uint32_t c = run[dx].pick(dy + shift[dx]);
+          const float wt = wts ? wts[(uint64_t)(x0 + (uint32_t)dx) * H + y0 + dy] : 1.0f;
+          const float w = w0 * wt;                                             // :103
+          if (c < C) row[c] = row[c] + 1.0f * w;
+        }
+      }
+    }
+  };
+  if (IN_LDS) {
+    fuse_pixels(srow + (uint32_t)l * S);
+  } else {
+    if (any_win) fuse_pixels(a.acc + f * C);   // (any_win: f < F and the triangle is nobody else's)
+    return;
+  }
+  wave_sync();
+  if (nrows != kWave || __ballot(big) != 0ull) {
+    // some of these 64 rows belong to queued triangles, which the tail waves of this launch update meanwhile (or the block is the
+    // mesh's last, partial one): every lane that added something stores its own row
+    if (any_win) {
+      float* __restrict__ mine = a.acc + f * C;
+      for (uint32_t c = 0; c < C; c++) mine[c] = srow[(uint32_t)l * S + c];
+    }
+    return;
+  }
+  f4* b4 = reinterpret_cast<f4*>(blk);
+  for (uint32_t q = l; q < nq; q += kWave) {
+    uint32_t r = q * 4u / C, c = q * 4u - r * C;
+    float e[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      e[k] = srow[r * S + c];
+      if (++c == C) { c = 0u; r++; }
+    }
+    f4 t;
+    t.x = e[0]; t.y = e[1]; t.z = e[2]; t.w = e[3];
+    b4[q] = t;
+  }
+}
+
+// Any accepted label image -> the dense (W,H) plane the fusion reads: every value outside [0, C) becomes the all-ones code.
+template <typename T, typename OUT>
+__global__ __launch_bounds__(256) void k_labels_narrow(const T* __restrict__ in, int64_t s0, int64_t s1, OUT* __restrict__ out, uint64_t N,
+                                                       uint32_t H, uint32_t C) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const uint64_t x = i / H, y = i - x * H;
+  const T v = in[x * (uint64_t)s0 + y * (uint64_t)s1];
+  bool ok = (uint64_t)v < (uint64_t)C;
+  if (std::is_signed<T>::value) ok = ok && !(v < (T)0);
+  out[i] = ok ? (OUT)v : (OUT)~(OUT)0;
+}
+
+// The fallback's expansion: a narrow label plane -> dense float32 (W,H,C) class vectors (tf.one_hot: all zero for a label >= C).
+template <typename LT>
+__global__ __launch_bounds__(256) void k_labels_onehot(const LT* __restrict__ lab, float* __restrict__ out, uint64_t total, uint32_t C) {
+  const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const uint64_t i = e / C;
+  out[e] = (uint32_t)lab[i] == (uint32_t)(e - i * C) ? 1.0f : 0.0f;
+}
+
+constexpr int kGroup = 8;   // views whose planes share the aggregator's label scratch (labels_scratch.hpp): a group of smesh_fuse_views
+
+size_t label_itemsize(int dt) { return (size_t)1 << (dt >> 1); }
+
+template <typename OUT>
+void launch_narrow(const void* src, int dt, const int64_t s[2], OUT* out, uint64_t N, uint32_t H, uint32_t C, hipStream_t st) {
+  const dim3 g((uint32_t)div_up(N, 256)), b(256);
+  switch (dt) {
+#define SMESH_NARROW(T) hipLaunchKernelGGL((k_labels_narrow<T, OUT>), g, b, 0, st, static_cast<const T*>(src), s[0], s[1], out, N, H, C); break
+    case SMESH_LBL_U8:  SMESH_NARROW(uint8_t);
+    case SMESH_LBL_I8:  SMESH_NARROW(int8_t);
+    case SMESH_LBL_U16: SMESH_NARROW(uint16_t);
+    case SMESH_LBL_I16: SMESH_NARROW(int16_t);
+    case SMESH_LBL_U32: SMESH_NARROW(uint32_t);
+    case SMESH_LBL_I32: SMESH_NARROW(int32_t);
+    case SMESH_LBL_U64: SMESH_NARROW(uint64_t);
+    default:            SMESH_NARROW(int64_t);
+#undef SMESH_NARROW
+  }
+}
+
+// (smesh_aggregator_create refuses more than 65535 classes; a uint16 plane -- 65535 = don't care -- could not name them all)
+int check_label_classes(uint32_t C) {
+  return C <= 65535u ? SMESH_OK : fail(SMESH_ERR_INVALID, "label images need an aggregator of at most 65535 classes");
+}
+
+int check_label_args(int dt, const int64_t s[2]) {
+  if (dt < 0 || dt > SMESH_LBL_I64) return fail(SMESH_ERR_INVALID, "bad label dtype");
+  if (s && (s[0] < 0 || s[1] < 0)) return fail(SMESH_ERR_INVALID, "labels: negative strides are not supported");
+  return SMESH_OK;
+}
+
+// Is the image its own plane (a dense uint8 / uint16 image in device memory)?  Then narrow_plane needs no scratch for it.
+bool plane_in_place(int dt, const int64_t* strides, int mem, uint64_t W, uint64_t H) {
+  const bool is_dense = !strides || ((strides[0] == (int64_t)H || W == 1) && (strides[1] == 1 || H == 1));
+  return mem == SMESH_MEM_DEVICE && (dt == SMESH_LBL_U8 || dt == SMESH_LBL_U16) && is_dense;
+}
+
+// The dense narrow plane of one label image, in device memory: the image itself where it is one already (dense uint8 / uint16 on the
+// device: the kernels treat label >= C as don't-care), else slot `slot` of the plane scratch (`slot_bytes` apart), filled on the main
+// stream -- a host image is staged first (*staged = true: the caller waits for the copies before it returns).
+int narrow_plane(DeviceCtx* ctx, LabelScratch& ls, int slot, size_t slot_bytes, size_t stage_bytes, const void* src, int dt, const int64_t* strides,
+                 int mem, uint64_t W, uint64_t H, uint32_t C, const void** plane, int* label_bytes, bool* staged) {
+  const uint64_t N = W * H;
+  const int64_t dense[2] = {(int64_t)H, 1};
+  const int64_t* s = strides ? strides : dense;
+  const bool is_dense = (s[0] == (int64_t)H || W == 1) && (s[1] == 1 || H == 1);
+  const bool narrow = dt == SMESH_LBL_U8 || dt == SMESH_LBL_U16;
+  const int out_bytes = narrow ? (int)label_itemsize(dt) : (C <= 255u ? 1 : 2);
+  *label_bytes = out_bytes;
+  if (mem == SMESH_MEM_DEVICE && narrow && is_dense) { *plane = src; return SMESH_OK; }   // (plane_in_place: no scratch was reserved)
+  char* out = static_cast<char*>(ls.plane.ptr) + (size_t)slot * slot_bytes;
+  if (mem == SMESH_MEM_HOST) {
+    *staged = true;
+    if (narrow && is_dense) {
+      SMESH_HIP(hipMemcpyAsync(out, src, N * (size_t)out_bytes, hipMemcpyHostToDevice, ctx->stream));
+      *plane = out;
+      return SMESH_OK;
+    }
+    const size_t span = (1 + (W - 1) * (uint64_t)s[0] + (H - 1) * (uint64_t)s[1]) * label_itemsize(dt);
+    char* stage = static_cast<char*>(ls.stage.ptr) + (size_t)slot * stage_bytes;
+    SMESH_HIP(hipMemcpyAsync(stage, src, span, hipMemcpyHostToDevice, ctx->stream));
+    src = stage;
+  }
+  if (out_bytes == 1) launch_narrow<uint8_t>(src, dt, s, reinterpret_cast<uint8_t*>(out), N, (uint32_t)H, C, ctx->stream);
+  else launch_narrow<uint16_t>(src, dt, s, reinterpret_cast<uint16_t*>(out), N, (uint32_t)H, C, ctx->stream);
+  SMESH_HIP(hipGetLastError());
+  *plane = out;
+  return SMESH_OK;
+}
+
+size_t stage_span_bytes(int dt, const int64_t* strides, uint64_t W, uint64_t H) {
+  const int64_t dense[2] = {(int64_t)H, 1};
+  const int64_t* s = strides ? strides : dense;
+  return ((1 + (W - 1) * (uint64_t)s[0] + (H - 1) * (uint64_t)s[1]) * label_itemsize(dt) + 255) & ~(size_t)255;
+}
+
+}  // namespace
+
+// ---- what raster.hip calls --------------------------------------------------------------------------------------------------
+
+// Do label views of an image of N pixels, rendered by a triangle renderer of F triangles in the caller's face order, take
+// k_fuse_tri_labels for this aggregator?  Sum / Summax only (Mul is defined on one-hot input -- log 0 = -inf for every class but one --
+// and takes the class-vector path), rows in triangle order, a plane of at least one run of eight labels.
+bool smesh_labels_native(smesh_aggregator* a, uint64_t F, uint64_t N) {
+  int kind;
+  smesh_aggregator_label_target(a, nullptr, nullptr, nullptr, &kind, nullptr);
+  return kind != SMESH_AGG_MUL && F != 0 && N >= 8 && smesh_aggregator_can_fuse_triangles(a, F);
+}
+
+// views[v].labels: dense narrow planes of `label_bytes` (1 or 2) bytes per pixel in device memory.  `nviews` = 1, 2, 4 or 8.
+int smesh_labels_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int label_bytes) {
+  DeviceCtx* ctx = smesh_aggregator_ctx(a);
+  hipStream_t st = ctx->stream;
+  if (F == 0) return SMESH_OK;
+  SMESH_TRY(smesh_aggregator_refuse_scattered(a, "fuse_view_labels()"));
+  if (nviews != 1 && nviews != 2 && nviews != 4 && nviews != 8) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: unsupported view count");
+  if (label_bytes != 1 && label_bytes != 2) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: label planes are uint8 or uint16");
+  LabelFuseArgs t;
+  uint64_t P;
+  int kind;
+  smesh_aggregator_label_target(a, &t.acc, &P, &t.C, &kind, &t.iew);
+  if (kind == SMESH_AGG_MUL || P != F) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: Sum / Summax over the renderer's triangles only");
+  LabelViews<8> tv;
+  bool no_big = true;   // every view PROVEN free of triangles over 8 x 8 pixels (RenderedView::no_big): no tail waves at all
+  for (int v = 0; v < 8; v++) {
+    const RenderedView& rv = views[v < nviews ? v : 0];
+    if (rv.W * rv.H < 8 || !rv.labels) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: label plane missing or under 8 pixels");
+    tv.v[v] = LabelView{rv.frags, rv.idx, rv.labels, rv.weights, rv.big_queue, rv.big_len, (uint32_t)rv.W, (uint32_t)rv.H};
+    no_big = no_big && rv.no_big;
+  }
+  const bool in_lds = t.C <= kLabelsLdsMaxC;
+  t.F = F;
+  t.big_capacity = big_capacity;
+  t.tri_blocks = (uint32_t)div_up(F, kWave);
+  t.big_blocks = no_big ? 0u : 16u * (uint32_t)std::max(1, ctx->num_cus);
+  t.stride = t.C | 1u;
+  const size_t lds = in_lds ? (size_t)kWave * t.stride * 4 : 0;
+  const dim3 grid(t.tri_blocks + t.big_blocks), block(kWave);
+  ProfScope prof(ctx, SMESH_PROF_FUSE_SCATTER);
+  prof_note(ctx, SMESH_PROF_FUSE_SCATTER, 1, (uint64_t)nviews);
+#define SMESH_FL(LT, NV)                                                                                        \
+  {                                                                                                             \
+    LabelViews<NV> w;                                                                                           \
+    for (int v = 0; v < NV; v++) w.v[v] = tv.v[v];                                                              \
+    if (in_lds) hipLaunchKernelGGL((k_fuse_tri_labels<LT, NV, true>), grid, block, lds, st, t, w);              \
+    else hipLaunchKernelGGL((k_fuse_tri_labels<LT, NV, false>), grid, block, 0, st, t, w);                      \
+  }
+#define SMESH_FLV(LT)                                     \
+  switch (nviews) {                                       \
+    case 1: SMESH_FL(LT, 1) break;                        \
+    case 2: SMESH_FL(LT, 2) break;                        \
+    case 4: SMESH_FL(LT, 4) break;                        \
+    default: SMESH_FL(LT, 8) break;                       \
+  }
+  if (label_bytes == 1) { SMESH_FLV(uint8_t) } else { SMESH_FLV(uint16_t) }
+#undef SMESH_FLV
+#undef SMESH_FL
+  SMESH_HIP(hipGetLastError());
+  return SMESH_OK;
+}
+
+// The fallback's class vectors: one_hot of a narrow device plane as dense float32 (W,H,C) in the aggregator's label scratch, on the
+// main stream.  One buffer: whoever reads it is queued on that stream before the next expansion.
+int smesh_labels_expand(smesh_aggregator* a, const void* plane, int label_bytes, uint64_t N, const float** probs) {
+  DeviceCtx* ctx = smesh_aggregator_ctx(a);
+  LabelScratch& ls = smesh_aggregator_label_scratch(a);
+  uint32_t C;
+  smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
+  const uint64_t total = N * C;
+  SMESH_TRY(ls.onehot.reserve(std::max<uint64_t>(total * 4, 16)));
+  float* out = static_cast<float*>(ls.onehot.ptr);
+  if (total) {
+    const dim3 g((uint32_t)div_up(total, 256)), b(256);
+    if (label_bytes == 1) hipLaunchKernelGGL(k_labels_onehot<uint8_t>, g, b, 0, ctx->stream, static_cast<const uint8_t*>(plane), out, total, C);
+    else hipLaunchKernelGGL(k_labels_onehot<uint16_t>, g, b, 0, ctx->stream, static_cast<const uint16_t*>(plane), out, total, C);
+    SMESH_HIP(hipGetLastError());
+  }
+  *probs = out;
+  return SMESH_OK;
+}
+
+// ---- include/smesh_labels.h -----------------------------------------------------------------------------------------------------
+extern "C" {
+
+int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
+                            int label_dtype, const int64_t label_strides[2], const float* const* weights, int memkind) {
+  if (!r || !a || (n && (!cams || !labels))) return fail(SMESH_ERR_INVALID, "NULL argument");
+  SMESH_TRY(check_label_args(label_dtype, label_strides));
+  if (memkind != SMESH_MEM_HOST && memkind != SMESH_MEM_DEVICE) return fail(SMESH_ERR_INVALID, "bad memory kind");
+  for (uint64_t i = 0; i < n; i++) {
+    if (!labels[i]) return fail(SMESH_ERR_INVALID, "NULL label image");
+    if (cams[i].width == 0 || cams[i].height == 0 || cams[i].width > 65536 || cams[i].height > 65536)
+      return fail(SMESH_ERR_INVALID, "camera resolution must be in [1, 65536]");
+  }
+  DeviceCtx* ctx = smesh_renderer_ctx(r);
+  if (smesh_aggregator_ctx(a) != ctx) return fail(SMESH_ERR_INVALID, "renderer and aggregator live on different devices");
+  uint32_t C;
+  smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
+  SMESH_TRY(check_label_classes(C));
+  LabelScratch& ls = smesh_aggregator_label_scratch(a);
+  std::lock_guard<std::mutex> g(ls.mu);
+  // groups of up to eight views: their planes (and staged host images and weights) share the scratch, which the next group's copies
+  // and narrowing kernels overwrite behind this group's fusion on the main stream
+  for (uint64_t i = 0; i < n; i += kGroup) {
+    const int m = (int)std::min<uint64_t>(kGroup, n - i);
+    size_t slot_bytes = 0, stage_bytes = 0, w_bytes = 0;
+    for (int v = 0; v < m; v++) {
+      const uint64_t N = cams[i + v].width * cams[i + v].height;
+      slot_bytes = std::max<size_t>(slot_bytes, (N * 2 + 255) & ~(size_t)255);
+      stage_bytes = std::max(stage_bytes, stage_span_bytes(label_dtype, label_strides, cams[i + v].width, cams[i + v].height));
+      w_bytes = std::max<size_t>(w_bytes, (N * 4 + 255) & ~(size_t)255);
+    }
+    const void* planes[kGroup];
+    const float* wts[kGroup];
+    int label_bytes = 1;
+    bool staged = false;
+    {
+      std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+      SMESH_HIP(hipSetDevice(ctx->device));
+      bool in_place = true;   // nothing to narrow: no plane scratch
+      for (int v = 0; v < m; v++) in_place = in_place && plane_in_place(label_dtype, label_strides, memkind, cams[i + v].width, cams[i + v].height);
+      if (!in_place) SMESH_TRY(ls.plane.reserve(slot_bytes * (size_t)m));
+      if (memkind == SMESH_MEM_HOST) {
+        SMESH_TRY(ls.stage.reserve(stage_bytes * (size_t)m));
+        if (weights) SMESH_TRY(ls.w.reserve(w_bytes * (size_t)m));
+      }
+      for (int v = 0; v < m; v++) {
+        const uint64_t W = cams[i + v].width, H = cams[i + v].height;
+        SMESH_TRY(narrow_plane(ctx, ls, v, slot_bytes, stage_bytes, labels[i + v], label_dtype, label_strides, memkind, W, H, C, &planes[v],
+                               &label_bytes, &staged));
+        wts[v] = weights ? weights[i + v] : nullptr;
+        if (wts[v] && memkind == SMESH_MEM_HOST) {
+          float* d = reinterpret_cast<float*>(static_cast<char*>(ls.w.ptr) + (size_t)v * w_bytes);
+          SMESH_HIP(hipMemcpyAsync(d, wts[v], W * H * 4, hipMemcpyHostToDevice, ctx->stream));
+          wts[v] = d;
+          staged = true;
+        }
+      }
+      if (staged) SMESH_HIP(hipStreamSynchronize(ctx->stream));   // the caller may reuse its host arrays once we return
+    }
+    SMESH_TRY(smesh_renderer_fuse_views_labels(r, a, &cams[i], (uint64_t)m, planes, weights ? wts : nullptr, label_bytes));
+  }
+  return SMESH_OK;
+}
+
+int smesh_fuse_view_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const void* labels, int label_dtype,
+                           const int64_t label_strides[2], const float* weights, int memkind) {
+  if (!cam) return fail(SMESH_ERR_INVALID, "NULL argument");
+  return smesh_fuse_views_labels(r, a, cam, 1, &labels, label_dtype, label_strides, weights ? &weights : nullptr, memkind);
+}
+
+int smesh_aggregator_add_labels(smesh_aggregator_t* a, smesh_renderer_t* r, const void* indices, int idx_dtype, const int64_t idx_strides[2],
+                                int idx_mem, const void* labels, int label_dtype, const int64_t label_strides[2], int label_mem,
+                                const float* weights, const int64_t w_strides[2], int w_mem, uint64_t W, uint64_t H) {
+  if (!a || !indices || !labels) return fail(SMESH_ERR_INVALID, "NULL argument");
+  if (idx_dtype < 0 || idx_dtype > 3) return fail(SMESH_ERR_INVALID, "bad index dtype");
+  SMESH_TRY(check_label_args(label_dtype, label_strides));
+  if ((idx_strides && (idx_strides[0] < 0 || idx_strides[1] < 0)) || (weights && w_strides && (w_strides[0] < 0 || w_strides[1] < 0)))
+    return fail(SMESH_ERR_INVALID, "negative strides are not supported");
+  if (W == 0 || H == 0) return SMESH_OK;
+  if (W > 65536 || H > 65536 || W * H >= 0x7FFFFFFFull / 4) return fail(SMESH_ERR_INVALID, "image too large");
+  DeviceCtx* ctx = smesh_aggregator_ctx(a);
+  if (r && smesh_renderer_ctx(r) != ctx) r = nullptr;
+  uint32_t C;
+  smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
+  const uint64_t N = W * H;
+  const int64_t dense[2] = {(int64_t)H, 1};
+  const int64_t* is = idx_strides ? idx_strides : dense;
+  const int64_t* ws = w_strides ? w_strides : dense;
+  SMESH_TRY(check_label_classes(C));
+  LabelScratch& ls = smesh_aggregator_label_scratch(a);
+  std::lock_guard<std::mutex> g(ls.mu);
+  const void* plane = nullptr;
+  const float* d_w = weights;
+  int label_bytes = 1;
+  bool staged = false;
+  const bool w_dense = !weights || (ws[0] == (int64_t)H && ws[1] == 1);
+  const bool rendered = r && idx_mem == SMESH_MEM_DEVICE && idx_dtype == SMESH_IDX_U32 && is[0] == (int64_t)H && is[1] == 1 && w_dense;
+  {
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    SMESH_HIP(hipSetDevice(ctx->device));
+    if (!plane_in_place(label_dtype, label_strides, label_mem, W, H)) SMESH_TRY(ls.plane.reserve((N * 2 + 255) & ~(size_t)255));
+    if (label_mem == SMESH_MEM_HOST) SMESH_TRY(ls.stage.reserve(stage_span_bytes(label_dtype, label_strides, W, H)));
+    SMESH_TRY(narrow_plane(ctx, ls, 0, (N * 2 + 255) & ~(size_t)255, 0, labels, label_dtype, label_strides, label_mem, W, H, C, &plane, &label_bytes, &staged));
+    if (rendered && weights && w_mem == SMESH_MEM_HOST) {   // (the triangle-order kernel wants the weights where the plane is)
+      SMESH_TRY(ls.w.reserve(N * 4));
+      SMESH_HIP(hipMemcpyAsync(ls.w.ptr, weights, N * 4, hipMemcpyHostToDevice, ctx->stream));
+      d_w = static_cast<const float*>(ls.w.ptr);
+      staged = true;
+    }
+    if (staged) SMESH_HIP(hipStreamSynchronize(ctx->stream));   // host images are consumed before the call returns
+  }
+  if (rendered) {
+    int done = 0;
+    SMESH_TRY(smesh_renderer_add_rendered_labels(a, r, static_cast<const uint32_t*>(indices), plane, label_bytes, d_w, W, H, &done));
+    if (done) return SMESH_OK;
+  }
+  // everything else: the labels expanded on the device, then the class-vector path unchanged (asynchronous for device images)
+  const float* probs = nullptr;
+  {
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    SMESH_HIP(hipSetDevice(ctx->device));
+    SMESH_TRY(smesh_labels_expand(a, plane, label_bytes, N, &probs));
+  }
+  const int64_t ps[3] = {(int64_t)(H * C), (int64_t)C, 1};
+  return smesh_aggregator_add_async(a, indices, idx_dtype, is, idx_mem, probs, ps, SMESH_MEM_DEVICE, weights, ws, w_mem, W, H);
+}
+
+}  // extern "C"

@@ -60,6 +60,10 @@ uint32_t smesh_aggregator_classes(smesh_aggregator* a);
 std::mutex& smesh_aggregator_mutex(smesh_aggregator* a);
 Scratch& smesh_aggregator_stage_probs(smesh_aggregator* a);
 Scratch& smesh_aggregator_stage_w(smesh_aggregator* a);
+// fusion_labels.hip: label views (include/smesh_labels.h)
+bool smesh_labels_native(smesh_aggregator* a, uint64_t F, uint64_t N);
+int smesh_labels_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int label_bytes);
+int smesh_labels_expand(smesh_aggregator* a, const void* plane, int label_bytes, uint64_t N, const float** probs);
 
 namespace {
 
@@ -2154,14 +2158,37 @@ static thread_local const char* g_last_fuse_kernel = "none";
 static thread_local const char* g_last_add_path = "none";   // "render-records" (the rasteriser's per-triangle records), or what add_device reports
 void smesh_note_fuse(const char* kernel, const char* path) { g_last_fuse_kernel = kernel; g_last_add_path = path; }
 
+// Do label views of this renderer into this aggregator take k_fuse_tri_labels (fusion_labels.hip)?  Triangle primitives in the caller's
+// face order (the kernel knows no prim_id table), Sum / Summax.  Everything else: labels expanded on the device, class-vector path.
+static bool labels_native(smesh_renderer* r, smesh_aggregator* a, uint64_t N) {
+  return !r->texels && !r->prim_id && smesh_labels_native(a, r->F, N);
+}
+
+// RasterArgs::idx_optional (see plane_optional_level) for the raster launch ahead of k_fuse_tri_labels.  Its main waves read a view's index plane only to check
+// masks the render flags (big_len[1]), but its tail waves SCAN the plane of every view of the launch for a queued triangle -- the views
+// in which it is small included: there is no by-mask path in that kernel.  So it is NOT a k_fuse_tri-like reader (level 2, each view
+// for itself) but level 1: one decision per raster launch, all planes as soon as one view has queued triangles or flagged masks.
+constexpr int kLabelsPlaneLevel = 1;
+
 // The fusion half of smesh_fuse_view / smesh_aggregator_add_rendered: `d_idx` is the index plane of the render
 // whose per-triangle records sit in r->side[slot].
+// (`label_bytes` != 0: `probs` is no class-vector image but a dense label plane of that many bytes per pixel in DEVICE memory)
 static int fuse_rendered(smesh_renderer* r, smesh_aggregator* a, int slot, const uint32_t* d_idx, const float* probs,
-                         const float* weights, int memkind, uint64_t W, uint64_t H, int64_t ps0 = 0, int64_t ps1 = 0) {
+                         const float* weights, int memkind, uint64_t W, uint64_t H, int64_t ps0 = 0, int64_t ps1 = 0, int label_bytes = 0) {
   DeviceCtx* ctx = r->ctx;
   const uint64_t N = W * H;
   const float* d_probs = probs;
   const float* d_w = weights;
+  if (label_bytes) {
+    if (labels_native(r, a, N)) {
+      RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H, 0, 0, true};
+      rv.labels = probs;
+      SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, label_bytes));
+      smesh_note_fuse("k_fuse_tri_labels", "render-records");
+      return SMESH_OK;
+    }
+    SMESH_TRY(smesh_labels_expand(a, probs, label_bytes, N, &d_probs));
+  }
   if (memkind == SMESH_MEM_HOST) {
     const uint32_t C = smesh_aggregator_classes(a);
     Scratch& sp = smesh_aggregator_stage_probs(a);
@@ -2416,8 +2443,8 @@ int smesh_renderer_render(smesh_renderer_t* r, const smesh_camera_t* cam, uint32
 
 // One iteration of the driver loop (colorize_cityscapes_mesh.py:54-67): render + add, indices never leave HBM.
 // Asynchronous for DEVICE probs: they must stay valid until smesh_synchronize().
-int smesh_fuse_view(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const float* probs,
-                    const float* weights, int memkind) {
+static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const float* probs,
+                          const float* weights, int memkind, int label_bytes) {
   if (!r || !a || !probs) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(check_camera(cam));
   DeviceCtx* ctx = r->ctx;
@@ -2442,19 +2469,27 @@ int smesh_fuse_view(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_came
   uint32_t* d_idx = static_cast<uint32_t*>(r->fused[slot].ptr);
   r->last_idx[slot] = nullptr; r->rec_valid[slot] = false;   // the records of a render_device() on this side are being overwritten
   // (the fusion only consumes the index plane -- and the triangle-order kernels not even that, where the view has no queued triangles)
-  const int tri_path = plane_optional_level(r, a);
+  // (a label view: k_fuse_tri_labels follows the raster launch, or -- labels expanded -- the class-vector kernels as ever)
+  const int tri_path = (label_bytes && labels_native(r, a, N)) ? kLabelsPlaneLevel : plane_optional_level(r, a);
   SMESH_TRY(render_into(r, cam, d_idx, /*d_depth=*/nullptr, ctx->stream, slot, tri_path));
-  SMESH_TRY(fuse_rendered(r, a, slot, d_idx, probs, weights, memkind, W, H));
+  SMESH_TRY(fuse_rendered(r, a, slot, d_idx, probs, weights, memkind, W, H, 0, 0, label_bytes));
   r->fused_seq++;
   return SMESH_OK;
+}
+
+int smesh_fuse_view(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const float* probs,
+                    const float* weights, int memkind) {
+  return fuse_view_impl(r, a, cam, probs, weights, memkind, 0);
 }
 
 // A batch of views: smesh_fuse_view for each of them, in order -- except that, with device-resident class vectors, up to
 // kMaxGroup views share each rasteriser launch, and two consecutive views of a triangle renderer are fused by ONE launch
 // (k_fuse_tri<.., 2>: every 64-row accumulator block makes one round trip for both views; same additions in the same order
 // as two calls).  Asynchronous like smesh_fuse_view.
-int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n,
-                     const float* const* probs, const float* const* weights, int memkind) {
+// (`label_bytes` != 0: label views -- probs[i] are dense label planes in DEVICE memory, fused by k_fuse_tri_labels; the caller has made
+// sure that labels_native() holds for every view)
+static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n,
+                           const float* const* probs, const float* const* weights, int memkind, int label_bytes) {
   if (!r || !a || (n && (!cams || !probs))) return fail(SMESH_ERR_INVALID, "NULL argument");
   for (uint64_t i = 0; i < n; i++) {
     SMESH_TRY(check_camera(&cams[i]));
@@ -2470,6 +2505,10 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
     tri_path = plane_optional_level(r, a);   // (fuse_rendered / the group's fusion take k_fuse_tri*: RasterArgs::idx_optional)
     pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && !r->texels && r->F != 0 && smesh_aggregator_can_fuse_triangles(a, r->F) &&
                smesh_aggregator_can_fuse_pair(a);
+    if (label_bytes) {   // k_fuse_tri_labels follows every raster launch of this call: any class count, up to eight views per launch
+      tri_path = kLabelsPlaneLevel;
+      pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0;
+    }
   }
   static const bool raster_pairs_off = env_int("SMESH_RASTER_PAIRS", 1) == 0;
   uint64_t i = 0;
@@ -2480,7 +2519,7 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
     bool grouped = !raster_pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0 && r->V != 0 && gn >= 2;
     for (int v = 0; v < gn && grouped; v++) grouped = queues_fit_group(cams[i + v].width, cams[i + v].height);
     if ((!pairable && !grouped) || i + 1 >= n) {
-      SMESH_TRY(smesh_fuse_view(r, a, &cams[i], probs[i], weights ? weights[i] : nullptr, memkind));
+      SMESH_TRY(fuse_view_impl(r, a, &cams[i], probs[i], weights ? weights[i] : nullptr, memkind, label_bytes));
       i += 1;
       continue;
     }
@@ -2561,13 +2600,14 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
     for (int j = 0; j < gn && !pairable && !texel_multi; j++) {   // class counts beyond k_fuse_tri, foreign primitive counts
       const uint64_t k = i + (uint64_t)j;
       SMESH_TRY(fuse_rendered(r, a, base + j, static_cast<const uint32_t*>(r->fused[base + j].ptr), probs[k], weights ? weights[k] : nullptr,
-                              SMESH_MEM_DEVICE, cams[k].width, cams[k].height));
+                              SMESH_MEM_DEVICE, cams[k].width, cams[k].height, 0, 0, label_bytes));
     }
     // the fusion launches of a group are back to back: one timed region for all of them (smesh_profile_*: a HIP event pair around a
     // single launch adds the dispatch latency that back-to-back launches hide)
     if (pairable) {
       ProfScope fuse_region(ctx, SMESH_PROF_FUSE_SCATTER);
-      const int max_nv = smesh_aggregator_max_fused_views(a);
+      static const int label_views_cap = std::max(1, env_int("SMESH_FUSE_VIEWS", 8));
+      const int max_nv = label_bytes ? std::min(8, label_views_cap) : smesh_aggregator_max_fused_views(a);
       for (int j = 0; j < gn;) {
         // the largest of 8 / 4 / 2 / 1 views that fits what is left of the group and what the kernel takes for this class count
         int nv = 1;
@@ -2580,12 +2620,14 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
                                weights ? weights[k] : nullptr, cams[k].width, cams[k].height, 0, 0, true};
           rv[v].no_big = no_big_possible(r, &cams[k]);
           rv[v].fine = box_extent_bound(r->bounds, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
+          if (label_bytes) { rv[v].labels = probs[k]; rv[v].probs = nullptr; }
         }
-        SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv));
+        if (label_bytes) SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, label_bytes));
+        else SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv));
         j += nv;
       }
     }
-    if (pairable) smesh_note_fuse(smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
+    if (pairable) smesh_note_fuse(label_bytes ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
     if (grouped && group_pipeline) SMESH_HIP(hipEventRecord(r->ev_bank_consumed[base / kMaxGroup], ctx->stream));
     r->fused_seq += (uint64_t)gn;
     i += (uint64_t)gn;
@@ -2593,7 +2635,54 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
   return SMESH_OK;
 }
 
+int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n,
+                     const float* const* probs, const float* const* weights, int memkind) {
+  return fuse_views_impl(r, a, cams, n, probs, weights, memkind, 0);
+}
+
 }  // extern "C"
+
+// ---- label views (include/smesh_labels.h; the entry points are fusion_labels.hip's) ---------------------------------------------------
+DeviceCtx* smesh_renderer_ctx(smesh_renderer* r) { return r->ctx; }
+
+// smesh_fuse_views for `n` label views whose dense narrow planes (`label_bytes` = 1 or 2 per pixel) and weights are in DEVICE memory.
+// Where k_fuse_tri_labels serves the renderer and the aggregator: the group pipeline and the eight-view grouping of smesh_fuse_views,
+// the planes riding in the views' slots.  Else view by view: labels expanded on the device, smesh_fuse_view's path.
+int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* planes,
+                                     const float* const* weights, int label_bytes) {
+  bool native = true;
+  {
+    std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+    for (uint64_t i = 0; i < n; i++) native = native && labels_native(r, a, cams[i].width * cams[i].height);
+  }
+  const float* const* p = reinterpret_cast<const float* const*>(planes);
+  if (native) return fuse_views_impl(r, a, cams, n, p, weights, SMESH_MEM_DEVICE, label_bytes);
+  for (uint64_t i = 0; i < n; i++) SMESH_TRY(fuse_view_impl(r, a, &cams[i], p[i], weights ? weights[i] : nullptr, SMESH_MEM_DEVICE, label_bytes));
+  return SMESH_OK;
+}
+
+// smesh_aggregator_add_rendered for a label plane: *done = 1 if `idx_dev` is the untouched output of one of r's latest
+// smesh_renderer_render_device() calls and the view was fused from that render's records (k_fuse_tri_labels, or -- labels expanded --
+// the triangle / texel kernels of the class-vector path); *done = 0: nothing happened.
+int smesh_renderer_add_rendered_labels(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* plane, int label_bytes,
+                                       const float* weights, uint64_t W, uint64_t H, int* done) {
+  *done = 0;
+  DeviceCtx* ctx = r->ctx;
+  if (smesh_aggregator_ctx(a) != ctx || W == 0 || H == 0) return SMESH_OK;
+  std::lock_guard<std::mutex> g(r->mu);
+  std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  SMESH_TRY(smesh_aggregator_join_exchange(a));
+  int side = -1;
+  for (int sd = 0; sd < kRecordSides; sd++)
+    if (idx_dev == r->last_idx[sd] && W == r->last_W[sd] && H == r->last_H[sd]) side = sd;
+  if (side < 0 || !((!r->texels && smesh_aggregator_can_fuse_triangles(a, r->F)) || (r->texels && smesh_aggregator_can_fuse_texels(a, r->num_primitives))))
+    return SMESH_OK;
+  SMESH_HIP(hipSetDevice(ctx->device));
+  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(plane), weights, SMESH_MEM_DEVICE, W, H, 0, 0, label_bytes));
+  *done = 1;
+  return SMESH_OK;
+}
 
 // ---- sharded jobs: a rank's last views fused by triangle range (smesh.h) -----------------------------------
 // One launch per (group of up to eight held views, part): the records of all held views stay in side[kSlots ...], their index

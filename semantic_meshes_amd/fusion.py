@@ -22,6 +22,29 @@ def _c64(vals):
     return (ctypes.c_int64 * len(vals))(*vals)
 
 
+def narrow_labels(labels, classes):
+    """The host-side narrowing rule of the label entry points: an integer label image (any of uint8 / int8 / uint16 / int16 / uint32 /
+    int32 / uint64 / int64, any shape) as the dense plane the fusion reads -- uint8 when `classes` <= 255, else uint16 -- with every
+    value outside [0, classes), negative ones included, replaced by the all-ones "don't care" code (255 / 65535: tf.one_hot's all-zero
+    vector).  Only this plane crosses PCIe."""
+    a = np.asarray(labels)
+    classes = int(classes)
+    if a.dtype.name not in _lib.LBL_CODES:
+        raise ValueError("label image dtype must be one of %s, got %s" % ("/".join(_lib.LBL_CODES), a.dtype))
+    if not 0 < classes <= 65535:
+        raise ValueError("classes must be in [1, 65535]")
+    out = np.dtype(np.uint8 if classes <= 255 else np.uint16)
+    # one pass in the image's own width: seen as unsigned, a negative label is a huge one, so "outside [0, classes)" is `>= classes`
+    u = a.view(np.dtype("u%d" % a.dtype.itemsize))
+    limit = classes if a.dtype.kind == "u" else min(classes, np.iinfo(a.dtype).max + 1)
+    code = np.iinfo(out).max
+    if limit > np.iinfo(u.dtype).max:          # every value the image can hold is a class
+        return np.ascontiguousarray(u.astype(out, copy=False))
+    if out.itemsize > u.itemsize:              # (int8 labels, more than 255 classes: the code does not fit the image's width)
+        return np.where(u < u.dtype.type(limit), u.astype(out), out.type(code))
+    return np.ascontiguousarray(np.where(u < u.dtype.type(limit), u, u.dtype.type(code)).astype(out, copy=False))
+
+
 GROUP_VIEWS = 8                                                     # views per deferred group (= the library's views per launch)
 DEFER_VIEWS = os.environ.get("SMESH_DEFER_VIEWS", "1") != "0"       # default of MeshAggregator.defer
 
@@ -58,7 +81,7 @@ class _MeshAggregator:
         # share their rasteriser launches and each accumulator row makes one round trip for all of them: the batch entry point's
         # throughput behind the reference's per-view loop (colorize_cityscapes_mesh.py:54-67).  Same sums in the same order.  The group
         # is handed over on the eighth view, at anything else that uses the aggregator (`_h`), at `flush()`, at `_lib.synchronize()`.
-        self._pending = []      # [(renderer, CameraPOD, W, H, probs array, weights array or None)]
+        self._pending = []      # [(renderer, CameraPOD, W, H, probs array -- or label plane --, weights array or None, is a label view)]
         self._pending_lock = threading.RLock()
         self.defer = DEFER_VIEWS
         with _aggregators_lock:
@@ -84,6 +107,10 @@ class _MeshAggregator:
             wptr = None
             if todo[0][5] is not None:
                 wptr = (ctypes.c_void_p * n)(*[t[5].ptr for t in todo])
+            if todo[0][6]:     # a group of label views (all-labels or all-probs, one label dtype: _defer)
+                _lib.check(_lib.lib().smesh_fuse_views_labels(renderer._h, self._handle, pods, n, pptr, _lib.LBL_CODES[todo[0][4].dtype.name],
+                                                              None, wptr, _lib.MEM_DEVICE))
+                return
             _lib.check(_lib.lib().smesh_fuse_views(renderer._h, self._handle, pods, n, pptr, wptr, _lib.MEM_DEVICE))
             # (the class vectors are this library's own arrays: freed behind its streams, no completion token needed)
 
@@ -101,14 +128,26 @@ class _MeshAggregator:
                   and weights_image.dtype == np.float32 and weights_image.shape == (W, H) and weights_image.strides == (H, 1))
         return ok
 
-    def _defer(self, renderer, pod, W, H, probs_image, weights_image):
+    def _deferrable_labels(self, label_image, weights_image, W, H):
+        """`_deferrable` for a label view: this library's own dense uint8 / uint16 device plane, never exported."""
+        if not self.defer:
+            return False
+        ok = (type(label_image) is DeviceArray and not label_image._exported and label_image.device == self.device
+              and label_image.dtype in (np.uint8, np.uint16) and label_image.shape == (W, H) and label_image.strides == (H, 1))
+        if ok and weights_image is not None:
+            ok = (type(weights_image) is DeviceArray and not weights_image._exported and weights_image.device == self.device
+                  and weights_image.dtype == np.float32 and weights_image.shape == (W, H) and weights_image.strides == (H, 1))
+        return ok
+
+    def _defer(self, renderer, pod, W, H, probs_image, weights_image, labels=False):
         with self._pending_lock:
             if self._pending:
                 first = self._pending[0]
-                # one group = one renderer, one image size, weights for all views or for none
-                if first[0] is not renderer or (first[2], first[3]) != (W, H) or (first[5] is None) != (weights_image is None):
+                # one group = one renderer, one image size, weights for all views or for none, class vectors or labels (of one dtype)
+                if (first[0] is not renderer or (first[2], first[3]) != (W, H) or (first[5] is None) != (weights_image is None)
+                        or first[6] != labels or (labels and first[4].dtype != probs_image.dtype)):
                     self.flush()
-            self._pending.append((renderer, pod, W, H, probs_image, weights_image))
+            self._pending.append((renderer, pod, W, H, probs_image, weights_image, labels))
             if len(self._pending) >= GROUP_VIEWS:
                 self.flush()
 
@@ -233,6 +272,138 @@ class _MeshAggregator:
         release_to(self.device, streams)
         self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if pmem == _lib.MEM_DEVICE else None,
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
+
+    # ---- label images (include/smesh_labels.h): what the reference's colorize_mesh.py:39-67 fuses after tf.one_hot -----------------
+    def _describe_labels(self, label_image, W, H, what, streams):
+        """(pointer, memkind, dtype code, element strides, keep-alive) of a (W,H) label image; a host image is narrowed first."""
+        lp, lmem, lshape, ldt, lstr, keep = describe(label_image, 2, what, self.device, streams)
+        if ldt.name not in _lib.LBL_CODES:
+            raise ValueError("%s dtype must be one of %s, got %s" % (what, "/".join(_lib.LBL_CODES), ldt))
+        if (W, H) != (None, None) and tuple(lshape) != (W, H):
+            raise ValueError("%s must be (W,H) = %s, got %s" % (what, (W, H), tuple(lshape)))
+        if lmem == _lib.MEM_HOST and not (ldt == np.uint8 or (ldt == np.uint16 and self.classes > 255)):
+            # (a uint8 image -- or a uint16 one that cannot be made narrower -- crosses PCIe as it is: the kernels treat label >= C
+            # as don't-care, and the library narrows a strided one on the device)
+            keep = narrow_labels(np.asarray(keep), self.classes)      # (describe() left a numpy array: only the narrow plane crosses PCIe)
+            lp, lmem, lshape, ldt, lstr, keep = describe(keep, 2, what, self.device, streams)
+        return lp, lmem, _lib.LBL_CODES[ldt.name], lstr, keep, tuple(lshape)
+
+    def _describe_weights(self, weights_image, streams):
+        wp, wmem, wshape, wdt, wstr, k2 = describe(weights_image, 2, "weights image", self.device, streams)
+        if wdt != np.float32:
+            if wmem == _lib.MEM_HOST and wdt.kind == "f":
+                wp, wmem, wshape, wdt, wstr, k2 = describe(np.asarray(weights_image, dtype=np.float32), 2, "weights image", self.device, streams)
+            else:
+                raise ValueError("weights image must be float32, got %s" % wdt)
+        return wp, wmem, tuple(wshape), wstr, k2
+
+    def add_labels(self, primitive_image, label_image, weights_image=None):
+        """`add(primitive_image, one_hot(label_image), weights_image)` without the one-hot: `label_image` is (W,H) of uint8 / int8 /
+        uint16 / int16 / uint32 / int32 / uint64 / int64 -- a class index per pixel, host numpy or device array, any non-negative strides
+        (a mask decoded as (H,W) and passed as its transposed view is fine).  `one_hot` is tf.one_hot: a label outside [0, classes),
+        negative values included, is the all-zero "don't care" vector.  On the untouched index plane of `render()` (lazy or not) of a
+        triangle renderer and a Sum / Summax aggregator the view takes the label kernel (one addition per visible pixel); everything
+        else expands the labels on the device and takes add()'s path.  Equal to the one-hot call for finite weights (with a non-finite
+        weight that call computes 0 * inf = NaN for the pixel's other classes; this one does not)."""
+        if type(primitive_image).__name__ == "PyCapsule":
+            from . import dlpack
+            own = dlpack.own_capsule_owner(primitive_image)
+            if own is not None:
+                primitive_image = own
+        if (getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
+                and self._deferrable_labels(label_image, weights_image, *primitive_image.shape)):
+            pend = primitive_image._pending      # (render()'s plane, not rasterised yet: the view joins the group, see add())
+            if pend.W and pend.H:
+                self._defer(pend.renderer, pend.pod, pend.W, pend.H, label_image, weights_image, labels=True)
+            return
+        streams = []
+        ishape = tuple(getattr(primitive_image, "shape", ()))
+        if len(ishape) != 2:
+            ishape = tuple(np.shape(primitive_image))
+        # (the label image is checked before the index plane is looked at: a refused call leaves a lazy plane lazy)
+        lp, lmem, lcode, lstr, k1, lshape = self._describe_labels(label_image, None, None, "label image", streams)
+        wdesc = None if weights_image is None else self._describe_weights(weights_image, streams)
+        if len(ishape) == 2 and (ishape != lshape or (wdesc is not None and wdesc[2] != ishape)):
+            raise ValueError("Primitive image %s, label image %s and weights image %s must have the same width and height"
+                             % (ishape, lshape, None if wdesc is None else wdesc[2]))
+        ip, imem, ishape, idt, istr, k0 = describe(primitive_image, 2, "primitive image", self.device, streams)
+        if idt not in _IDX_CODES:
+            raise ValueError("primitive image dtype must be one of uint32/int32/uint64/int64, got %s" % idt)
+        if tuple(ishape) != lshape or (wdesc is not None and wdesc[2] != tuple(ishape)):
+            raise ValueError("Primitive image %s, label image %s and weights image %s must have the same width and height"
+                             % (tuple(ishape), lshape, None if wdesc is None else wdesc[2]))
+        W, H = ishape
+        if W == 0 or H == 0:
+            return
+        rb = getattr(primitive_image, "_rendered_by", None)
+        if not (rb is not None and not primitive_image._exported and getattr(rb, "_h", None) is not None and rb._h.value
+                and rb.device == self.device):
+            rb = None
+        wp, wmem, wstr, k2 = (None, _lib.MEM_HOST, None, None) if wdesc is None else (wdesc[0], wdesc[1], wdesc[3], wdesc[4])
+        _lib.check(_lib.lib().smesh_aggregator_add_labels(
+            self._h, None if rb is None else rb._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
+            ctypes.c_void_p(lp), lcode, _c64(lstr), lmem,
+            None if wp is None else ctypes.c_void_p(wp), None if wstr is None else _c64(wstr), wmem, W, H))
+        release_to(self.device, streams)
+        self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if lmem == _lib.MEM_DEVICE else None,
+                    k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
+
+    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None):
+        """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels)."""
+        W, H = camera.resolution
+        if (W > 0 and H > 0 and W <= 65536 and H <= 65536 and W * H < 0x7FFFFFFF // 4 and renderer.device == self.device
+                and self._deferrable_labels(label_image, weights_image, W, H)):
+            self._defer(renderer, _lib.CameraPOD.from_buffer_copy(camera._pod), W, H, label_image, weights_image, labels=True)
+            return
+        streams = []
+        lp, lmem, lcode, lstr, k1, _ = self._describe_labels(label_image, W, H, "label image", streams)
+        wp, k2 = None, None
+        if weights_image is not None:
+            wp_, wmem, wshape, wstr, k2 = self._describe_weights(weights_image, streams)
+            if wshape != (W, H) or wstr != (H, 1) or wmem != lmem:
+                raise ValueError("weights image must be contiguous float32 (W,H) in the same memory as the labels")
+            wp = ctypes.c_void_p(wp_)
+        _lib.check(_lib.lib().smesh_fuse_view_labels(renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(lp), lcode,
+                                                     _c64(lstr), wp, lmem))
+        release_to(self.device, streams)
+        if lmem == _lib.MEM_DEVICE:
+            self._hold([k1, k2])
+
+    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None):
+        """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
+        views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
+        and memory go to the library as one batch; a mixed list is fused view by view."""
+        cameras, label_images = list(cameras), list(label_images)
+        n = len(cameras)
+        if len(label_images) != n or (weights_images is not None and len(weights_images) != n):
+            raise ValueError("fuse_views_labels needs one label image (and one weights image or None) per camera")
+        if n == 0:
+            return
+        streams, desc = [], []
+        for i, cam in enumerate(cameras):
+            W, H = cam.resolution
+            d = self._describe_labels(label_images[i], W, H, "label image %d" % i, streams)
+            w = None if weights_images is None else weights_images[i]
+            dw = None
+            if w is not None:
+                dw = self._describe_weights(w, streams)
+                if dw[2] != (W, H) or dw[3] != (H, 1) or dw[1] != d[1]:
+                    raise ValueError("weights image %d must be contiguous float32 (W,H) in the same memory as the labels" % i)
+            desc.append((d, dw))
+        first = desc[0][0]
+        uniform = all(d[1:4] == first[1:4] and (dw is None) == (desc[0][1] is None) for d, dw in desc)
+        if not uniform:
+            release_to(self.device, streams)
+            for i in range(n):
+                self.fuse_view_labels(renderer, cameras[i], label_images[i], None if weights_images is None else weights_images[i])
+            return
+        pods = (_lib.CameraPOD * n)(*[cam._pod for cam in cameras])
+        lptr = (ctypes.c_void_p * n)(*[d[0] for d, _ in desc])
+        wptr = None if desc[0][1] is None else (ctypes.c_void_p * n)(*[dw[0] for _, dw in desc])
+        _lib.check(_lib.lib().smesh_fuse_views_labels(renderer._h, self._h, pods, n, lptr, first[2], _c64(first[3]), wptr, first[1]))
+        release_to(self.device, streams)
+        if first[1] == _lib.MEM_DEVICE:
+            self._hold([d[4] for d, _ in desc] + [dw[4] for _, dw in desc if dw is not None])
 
     def add_many(self, primitive_images, probs_images, weights_images=None):
         """`add()` for a batch of views, in order (new functionality; the reference's loop adds one image per call).  Same sums as
