@@ -121,6 +121,9 @@ SIGNATURES = {
 # Label dtypes of include/smesh_labels.h (SMESH_LBL_*), by numpy dtype string
 LBL_CODES = {"uint8": 0, "int8": 1, "uint16": 2, "int16": 3, "uint32": 4, "int32": 5, "uint64": 6, "int64": 7}
 
+# Modes of include/smesh_vertices.h (SMESH_VTX_*)
+VTX_SUMS, VTX_ANNOTATIONS = 0, 1
+
 # name -> (restype, argtypes); one entry per symbol declared in include/smesh_labels.h: the label-image entry points, a product-only
 # extension of the ABI that the CPU oracle does not implement (which is why they are not in SIGNATURES)
 EXT_SIGNATURES = {
@@ -129,6 +132,18 @@ EXT_SIGNATURES = {
     "smesh_aggregator_add_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int,
                                             c_void_p, c_int, P(ctypes.c_int64), c_int,
                                             c_void_p, P(ctypes.c_int64), c_int, c_u64, c_u64]),
+}
+
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_vertices.h: the per-vertex results, product-only like
+# the label entry points (a table of its own: tests/test_labels_host.py pins EXT_SIGNATURES to the symbols of smesh_labels.h)
+VERTEX_SIGNATURES = {
+    "smesh_vertex_map_create": (c_int, [c_void_p, c_u64, c_u64, c_int, P(c_void_p)]),
+    "smesh_vertex_map_destroy": (c_int, [c_void_p]),
+    "smesh_vertex_map_size": (c_int, [c_void_p, P(c_u64), P(c_u64), P(c_u64)]),
+    "smesh_vertex_map_adjacency": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "smesh_vertex_map_gather": (c_int, [c_void_p, c_void_p, c_int, c_u32, c_int, c_float, c_void_p, c_void_p, c_int]),
+    "smesh_aggregator_vertex_annotations": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int]),
+    "smesh_renderer_texel_face_rows": (c_int, [c_void_p, c_void_p, c_int, c_u32, c_int, c_float, c_void_p, c_int]),
 }
 
 _lib = None
@@ -258,7 +273,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -217,3 +218,16 @@ int image_records_scatter_sparse_group(DeviceCtx* ctx, ImageRecords* const* recs
                                        float* acc, float* acc_lo, double* acc_d, hipStream_t st);
 
 }  // namespace smesh
+
+// What the per-vertex results (vertices.hip) need from the handles that fusion.hip and raster.hip define.
+struct smesh_aggregator;
+struct smesh_renderer;
+// Runs `use(ctx, rows, P, C)` on what get() would return -- the normalised float32 [P][C] result in the aggregator's device scratch,
+// queued on the context's main stream -- with the aggregator and its context locked.  Obeys get()'s rules: a pending row exchange is
+// joined first, a reduce-scattered accumulator is refused.
+int smesh_aggregator_with_final_rows(smesh_aggregator* a,
+                                     const std::function<int(smesh::DeviceCtx* ctx, const float* rows, uint64_t P, uint32_t C)>& use);
+// The device tables of a texel renderer's layout: [F] first texel and resolution of every face, P texels in all.  SMESH_ERR_INVALID
+// for a renderer of triangle primitives.
+int smesh_renderer_texel_tables(const smesh_renderer* r, smesh::DeviceCtx** ctx, uint64_t* F, uint64_t* P, const uint32_t** first,
+                                const uint32_t** res);

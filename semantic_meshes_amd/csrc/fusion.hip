@@ -3207,6 +3207,27 @@ int smesh_aggregator_get(smesh_aggregator_t* a, float* out, int memkind) {
   return copy_to_host(ctx, out, a->out_tmp.ptr, bytes);
 }
 
+}  // extern "C"
+
+// get() for a consumer on the device (vertices.hip; declared in common.hpp)
+int smesh_aggregator_with_final_rows(smesh_aggregator* a, const std::function<int(DeviceCtx*, const float*, uint64_t, uint32_t)>& use) {
+  if (!a) return fail(SMESH_ERR_INVALID, "NULL argument");
+  std::lock_guard<std::mutex> g(a->mu);
+  DeviceCtx* ctx = a->ctx;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  SMESH_HIP(hipSetDevice(ctx->device));
+  SMESH_TRY(smesh_aggregator_join_exchange(a));
+  SMESH_TRY(smesh_aggregator_refuse_scattered(a, "vertex annotations"));
+  const size_t bytes = (size_t)a->P * a->C * 4;
+  if (bytes) {
+    SMESH_TRY(a->out_tmp.reserve(bytes));
+    SMESH_TRY(finalize_into(a, static_cast<float*>(a->out_tmp.ptr)));
+  }
+  return use(ctx, bytes ? static_cast<const float*>(a->out_tmp.ptr) : nullptr, a->P, a->C);
+}
+
+extern "C" {
+
 int smesh_aggregator_get_rows(smesh_aggregator_t* a, uint64_t row_lo, uint64_t row_hi, float* out, int memkind) {
   if (!a || !out) return fail(SMESH_ERR_INVALID, "NULL argument");
   if (row_lo > row_hi || row_hi > a->P || (row_lo & 3)) return fail(SMESH_ERR_INVALID, "bad row range (row_lo must be a multiple of 4, row_hi <= P)");

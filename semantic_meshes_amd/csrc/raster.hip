@@ -2386,6 +2386,22 @@ int smesh_renderer_texel_layout(const smesh_renderer_t* r, int32_t* faces_out, u
   return SMESH_OK;
 }
 
+}  // extern "C"
+
+// (vertices.hip; declared in common.hpp)
+int smesh_renderer_texel_tables(const smesh_renderer* r, DeviceCtx** ctx, uint64_t* F, uint64_t* P, const uint32_t** first, const uint32_t** res) {
+  if (!r) return fail(SMESH_ERR_INVALID, "NULL renderer");
+  if (!r->texels) return fail(SMESH_ERR_INVALID, "not a texel renderer");
+  *ctx = r->ctx;
+  *F = r->F;
+  *P = r->num_primitives;
+  *first = r->tex_first;
+  *res = r->tex_res;
+  return SMESH_OK;
+}
+
+extern "C" {
+
 int smesh_renderer_render_device(smesh_renderer_t* r, const smesh_camera_t* cam, uint32_t** indices_dev, float** depth_dev) {
   if (!r || !indices_dev || !depth_dev) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(check_camera(cam));

@@ -111,6 +111,14 @@ class Ply(Mesh):
             raise ValueError("annotation_colors must be uint8[F,3], got %s %s" % (colors.dtype, colors.shape))
         _write_ply(path, self.vertices, self.faces, colors, binary)
 
+    def save_vertex_colors(self, path, vertex_colors, binary=True):
+        """The mesh with one colour per VERTEX (`red green blue` vertex properties, faces without colours): what viewers display
+        and what per-vertex results (fusion.VertexTransfer) are painted with."""
+        colors = np.asarray(vertex_colors)
+        if colors.dtype != np.uint8 or colors.ndim != 2 or colors.shape != (len(self.vertices), 3):
+            raise ValueError("vertex_colors must be uint8[V,3], got %s %s" % (colors.dtype, colors.shape))
+        _write_ply_vertex_colors(path, self.vertices, self.faces, colors, binary)
+
 
 def _read_ply(path):
     with open(path, "rb") as fh:
@@ -239,6 +247,27 @@ def _write_ply(path, vertices, faces, colors, binary):
                 fh.write(("%r %r %r\n" % (float(v[0]), float(v[1]), float(v[2]))).encode("ascii"))
             for f, c in zip(faces, colors):
                 fh.write(("3 %d %d %d %d %d %d\n" % (f[0], f[1], f[2], c[0], c[1], c[2])).encode("ascii"))
+
+
+def _write_ply_vertex_colors(path, vertices, faces, colors, binary):
+    header = ["ply", "format %s 1.0" % ("binary_little_endian" if binary else "ascii"),
+              "element vertex %d" % len(vertices), "property float x", "property float y", "property float z",
+              "property uchar red", "property uchar green", "property uchar blue",
+              "element face %d" % len(faces), "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        if binary:
+            vrec = np.empty(len(vertices), dtype=[("p", "<f4", (3,)), ("c", "u1", (3,))])
+            vrec["p"], vrec["c"] = vertices, colors
+            fh.write(vrec.tobytes())
+            frec = np.empty(len(faces), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+            frec["n"], frec["v"] = 3, faces
+            fh.write(frec.tobytes())
+        else:
+            for v, c in zip(vertices, colors):
+                fh.write(("%r %r %r %d %d %d\n" % (float(v[0]), float(v[1]), float(v[2]), c[0], c[1], c[2])).encode("ascii"))
+            for f in faces:
+                fh.write(("3 %d %d %d\n" % (f[0], f[1], f[2])).encode("ascii"))
 
 
 # ---- COLMAP workspace reader -----------------------------------------------------------

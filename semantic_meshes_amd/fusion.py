@@ -694,6 +694,133 @@ class ModelRenderer:
         return buf.view((W, H, self.classes), np.float32)
 
 
+def _dense_rows(source, rows, what, device, streams):
+    """(pointer, memkind, C, keep-alive) of a dense float32 [rows, C] array on the host or the device, C >= 1."""
+    if isinstance(source, np.ndarray) and source.dtype != np.float32:
+        raise ValueError("%s must be float32, got %s" % (what, source.dtype))
+    ptr, mem, shape, dt, strides, keep = describe(source, 2, what, device, streams)
+    if dt != np.float32:
+        raise ValueError("%s must be float32, got %s" % (what, dt))
+    if shape[0] != rows or shape[1] < 1:
+        raise ValueError("%s must be float32[%d,C], got shape %s" % (what, rows, tuple(shape)))
+    if shape[0] > 1 and tuple(strides) != (shape[1], 1) or shape[1] > 1 and strides[1] != 1:
+        if mem != _lib.MEM_HOST:
+            raise ValueError("%s must be dense (row-major, no padding)" % what)
+        keep = np.ascontiguousarray(keep)
+        ptr = keep.ctypes.data
+    return ptr, mem, int(shape[1]), keep
+
+
+class VertexTransfer:
+    """Face annotations to per-vertex annotations and labels, on the device (include/smesh_vertices.h) -- what the reference's
+    evaluation does on the host with a Python loop over every face, `tf.gather`, `reduce_sum`, a 0.9 "don't care" threshold and a
+    renormalisation (eval-scannet/eval_scannet.py:249-287).
+
+    `faces`: int[F,3], `num_vertices`: V.  The vertex-to-faces table is built once, on `device`.  A `source` is a MeshAggregator
+    over the F faces (its `get()` never leaves the device), a float32 [F,C] numpy array, or a dense float32 [F,C] device array.
+    For vertex v, sums[v] is the float32 sum of the rows of v's faces in ascending face order; annotations[v] is sums[v] divided by
+    its total, or all zero where that total is below `dont_care_threshold`; labels[v] is the argmax of sums[v], -1 where don't care."""
+
+    def __init__(self, faces, num_vertices, device=0):
+        f = np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+            raise ValueError("faces must be an integer array [F,3], got %s %s" % (f.dtype, f.shape))
+        self.num_vertices, self.num_faces, self.device = int(num_vertices), len(f), int(device)
+        if self.num_vertices < 0:
+            raise ValueError("num_vertices must be >= 0")
+        if f.size and (f.min() < 0 or f.max() >= self.num_vertices):      # (the library checks again, on the device)
+            raise ValueError("face indices out of range [0, %d)" % self.num_vertices)
+        f = np.ascontiguousarray(f, dtype=np.int32)
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().smesh_vertex_map_create(f.ctypes.data_as(ctypes.c_void_p), len(f), self.num_vertices, self.device,
+                                                     ctypes.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_mesh(cls, mesh, device=0):
+        return cls(mesh.faces, len(mesh.vertices), device)
+
+    @classmethod
+    def from_renderer(cls, texel_renderer, num_vertices):
+        """For a texel renderer: its layout's faces, the order `face_annotations()` returns its rows in."""
+        if not hasattr(texel_renderer, "texel_layout"):
+            raise ValueError("from_renderer needs a texel renderer (render.texels)")
+        return cls(texel_renderer.texel_layout()[0], num_vertices, texel_renderer.device)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            try:
+                _lib.lib().smesh_vertex_map_destroy(h)
+            except Exception:
+                pass
+
+    def adjacency(self):
+        """The vertex-to-faces table as `(offsets uint64[V+1], faces uint32[nnz])`: the faces of vertex v, ascending, are
+        `faces[offsets[v]:offsets[v+1]]`."""
+        nnz = ctypes.c_uint64()
+        _lib.check(_lib.lib().smesh_vertex_map_size(self._h, None, None, ctypes.byref(nnz)))
+        offsets, faces = np.empty(self.num_vertices + 1, np.uint64), np.empty(int(nnz.value), np.uint32)
+        _lib.check(_lib.lib().smesh_vertex_map_adjacency(self._h, offsets.ctypes.data_as(ctypes.c_void_p), faces.ctypes.data_as(ctypes.c_void_p)))
+        return offsets, faces
+
+    def _run(self, source, mode, threshold, want_rows, want_labels, on_device):
+        V = self.num_vertices
+        if isinstance(source, _MeshAggregator):
+            if source.primitives != self.num_faces:
+                raise ValueError("the aggregator has %d primitives, the mesh %d faces" % (source.primitives, self.num_faces))
+            if source.device != self.device:
+                raise ValueError("aggregator and VertexTransfer live on different devices")
+            C = source.classes
+        else:
+            streams = []
+            ptr, mem, C, keep = _dense_rows(source, self.num_faces, "face rows", self.device, streams)
+        rows = labels = None
+        if on_device:
+            from .device import DeviceBuffer
+            if want_rows:
+                rows = DeviceBuffer(max(V * C * 4, 4), self.device).view((V, C), np.float32)
+            if want_labels:
+                labels = DeviceBuffer(max(V * 4, 4), self.device).view((V,), np.int32)
+            prow, plab, omem = (None if rows is None else ctypes.c_void_p(rows.ptr), None if labels is None else ctypes.c_void_p(labels.ptr),
+                                _lib.MEM_DEVICE)
+        else:
+            if want_rows:
+                rows = result_empty((V, C), np.float32)
+            if want_labels:
+                labels = np.empty(V, np.int32)
+            prow, plab, omem = (None if rows is None else rows.ctypes.data_as(ctypes.c_void_p),
+                                None if labels is None else labels.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST)
+        if isinstance(source, _MeshAggregator):
+            # (`_h`: the aggregator's deferred views are handed to the library first, as get() does)
+            _lib.check(_lib.lib().smesh_aggregator_vertex_annotations(source._h, self._h, mode, float(threshold), prow, plab, omem))
+            source._drain()
+        else:
+            _lib.check(_lib.lib().smesh_vertex_map_gather(self._h, ctypes.c_void_p(ptr), mem, C, mode, float(threshold), prow, plab, omem))
+            release_to(self.device, streams)
+        return rows, labels
+
+    def sums(self, source):
+        """float32 [V,C]: per vertex, the sum of its faces' rows."""
+        return self._run(source, _lib.VTX_SUMS, 0.0, True, False, False)[0]
+
+    def annotations(self, source, dont_care_threshold=0.9):
+        """float32 [V,C]: the sums renormalised; all-zero rows where the sum is below `dont_care_threshold` (eval_scannet.py:271-287)."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, False)[0]
+
+    def labels(self, source, dont_care_threshold=0.9):
+        """int32 [V]: the class with the largest sum (the lowest one among equals), -1 where don't care.  No [V,C] array is made."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, False)[1]
+
+    def annotations_device(self, source, dont_care_threshold=0.9):
+        """`annotations()` left in HBM: a `DeviceArray` in a fresh allocation owned by the returned object."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, True)[0]
+
+    def labels_device(self, source, dont_care_threshold=0.9):
+        """`labels()` left in HBM."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, True)[1]
+
+
 class MeshAggregatorSum(_MeshAggregator):
     pass
 

@@ -211,6 +211,45 @@ class _Renderer:
                                                    idx.ctypes.data_as(ctypes.c_void_p), depth.ctypes.data_as(ctypes.c_void_p)))
         return idx, depth
 
+    # ---- texel annotations back on the mesh (include/smesh_vertices.h); texel renderers only -------------------------------------
+    def _face_rows(self, source, threshold, normalize, on_device):
+        from .fusion import _MeshAggregator, _dense_rows
+        from .device import DeviceBuffer, release_to, result_empty
+        if not getattr(self, "is_texel", False):     # (defined for every renderer so that a triangle renderer is refused, not unknown)
+            raise ValueError("face_annotations needs a texel renderer (render.texels): the primitives of this one are its faces")
+        P, F = self.getPrimitivesNum(), self._num_faces
+        streams, keep = [], None
+        if isinstance(source, _MeshAggregator):
+            if source.primitives != P:
+                raise ValueError("the aggregator has %d primitives, the renderer %d texels" % (source.primitives, P))
+            if source.device != self.device:
+                raise ValueError("aggregator and renderer live on different devices")
+            keep = source.get_device()        # (the [P,C] result stays in HBM)
+            ptr, mem, C = keep.ptr, _lib.MEM_DEVICE, source.classes
+        else:
+            ptr, mem, C, keep = _dense_rows(source, P, "texel rows", self.device, streams)
+        if on_device:
+            out = DeviceBuffer(max(F * C * 4, 4), self.device).view((F, C), np.float32)
+            pout, omem = ctypes.c_void_p(out.ptr), _lib.MEM_DEVICE
+        else:
+            out = result_empty((F, C), np.float32)
+            pout, omem = out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST
+        _lib.check(_lib.lib().smesh_renderer_texel_face_rows(self._h, ctypes.c_void_p(ptr), mem, C,
+                                                            _lib.VTX_ANNOTATIONS if normalize else _lib.VTX_SUMS, float(threshold), pout, omem))
+        release_to(self.device, streams)
+        return out
+
+    def face_annotations(self, source, dont_care_threshold=0.9, normalize=True):
+        """Texel annotations back on the mesh: float32 [F,C], row f the sum of the rows of face f's texels (ascending texel order),
+        in the order of `texel_layout()`'s faces.  `source`: a MeshAggregator over this renderer's texels, a float32 [P,C] numpy
+        array or a dense device array.  `normalize`: divide each row by its total, all zero where that total is below
+        `dont_care_threshold` (what `VertexTransfer` does per vertex); False: the plain sums."""
+        return self._face_rows(source, dont_care_threshold, normalize, False)
+
+    def face_annotations_device(self, source, dont_care_threshold=0.9, normalize=True):
+        """`face_annotations()` left in HBM: a `DeviceArray` in a fresh allocation owned by the returned object."""
+        return self._face_rows(source, dont_care_threshold, normalize, True)
+
 
 class PlyRendererTriangles(_Renderer):
     """Triangle primitives: id == ordinal of the face in the mesh (TriangleRenderer.h:41-44,57-60)."""
