@@ -15,6 +15,12 @@
  * which k_fuse_tri_labels keeps a wave's 64 accumulator rows in LDS (255); beyond it the owner lane read-modify-writes the row
  * in global memory.
  *
+ * Two more read-only names report which instance of the triangle-order fusion the calling thread's last launch was (class vectors,
+ * not labels; smesh_last_fuse_kernel names the kernel from the class count alone): "last_fuse_slot" is the class-count slot handed
+ * to k_fuse_tri -- 5, 13, 19, 20, 21, 40 for the exact instances, 8, 16, 24, 32, 41, 48 for the run-time-C instances with 8, 16, 24,
+ * 32, 40 and 48 register slots --, 0 when the launch was k_fuse_tri_any, k_fuse_tri_wide or k_fuse_tri_wide_list, -1 before the
+ * first such launch; "last_fuse_views" is the number of views of that launch (1, 2, 4 or 8).
+ *
  * Conventions are those of smesh.h: label images are (W,H) with y fastest, strides in ELEMENTS and >= 0, every function
  * returns a status, SMESH_ERR_INVALID for a bad dtype, stride or shape.
  */

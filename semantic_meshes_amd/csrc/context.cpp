@@ -306,6 +306,8 @@ void Scratch::release() {
 
 using namespace smesh;
 
+void smesh_last_fuse_instance(int* slot, int* views);   // fusion.hip: the calling thread's last triangle-order launch
+
 extern "C" {
 
 const char* smesh_backend(void) { return "hip-gfx950"; }
@@ -325,6 +327,17 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "group_pipeline")) { *value = opt_group_pipeline() ? 1 : 0; return SMESH_OK; }
   // read-only: up to this class count k_fuse_tri_labels keeps a wave's rows in LDS, beyond it read-modify-writes them in global memory
   if (!strcmp(name, "labels_lds_max_classes")) { *value = (int64_t)kLabelsLdsMaxC; return SMESH_OK; }
+  // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --
+  // "last_fuse_slot": the class-count slot handed to k_fuse_tri (5 / 13 / 19 / 20 / 21 / 40: the exact instances; 8 / 16 / 24 / 32 / 41 / 48:
+  // the run-time-C instances with 8 .. 32, 40 and 48 register slots), 0 when the launch was k_fuse_tri_any, k_fuse_tri_wide or
+  // k_fuse_tri_wide_list, -1 before the first such launch; "last_fuse_views": the views of that launch (1, 2, 4 or 8; 0 before the first)
+  const bool want_slot = !strcmp(name, "last_fuse_slot");
+  if (want_slot || !strcmp(name, "last_fuse_views")) {
+    int slot, views;
+    smesh_last_fuse_instance(&slot, &views);
+    *value = want_slot ? slot : views;
+    return SMESH_OK;
+  }
   return fail(SMESH_ERR_INVALID, std::string("unknown option: ") + name);
 }
 

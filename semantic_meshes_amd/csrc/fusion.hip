@@ -2467,6 +2467,13 @@ static bool launch_fuse_wide_list(int wide_chunks, uint32_t C, dim3 grid, hipStr
   }
 }
 
+// Which instance the calling thread's last triangle-order launch was (reporting only, like smesh_last_fuse_kernel; read-only options
+// "last_fuse_slot" / "last_fuse_views" of smesh_get_option, context.cpp): the class-count slot `tri_ct` handed to k_fuse_tri, 0 for
+// k_fuse_tri_any / k_fuse_tri_wide / k_fuse_tri_wide_list, -1 before the first launch; and the `nviews` of that launch.
+static thread_local int g_last_fuse_slot = -1;
+static thread_local int g_last_fuse_views = 0;
+void smesh_last_fuse_instance(int* slot, int* views) { *slot = g_last_fuse_slot; *views = g_last_fuse_views; }
+
 // `nviews` = 1, 2, 4 or 8 (smesh_aggregator_max_fused_views): views[0], views[1] ... of the same renderer in one launch.
 // `part` / `nparts`: only the triangles of smesh_fuse_part_rows(F, part, nparts) -- the queued medium triangles (fuse_mid_entries, float
 // atomics) all go with part 0, the queued big ones with the part their position falls into.
@@ -2577,6 +2584,7 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
   {
     ProfScope prof(ctx, SMESH_PROF_FUSE_SCATTER);
     prof_note(ctx, SMESH_PROF_FUSE_SCATTER, 1, part == 0 ? (uint64_t)nviews : 0);
+    g_last_fuse_slot = tri_ct; g_last_fuse_views = nviews;   // (reporting only)
 #define SMESH_FA(K)                                                                            \
     switch (G) {                                                                               \
       case 1:  hipLaunchKernelGGL((k_fuse_tri_any<K, 1>), tgrid, block, 0, st, t, tv, nviews); break;  \

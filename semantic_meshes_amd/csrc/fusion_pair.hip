@@ -1,6 +1,6 @@
 // fusion_pair.hip -- the two-views-per-launch instances of the triangle-order fusion kernel (smesh_fuse_views; see fusion.hip and
 // DESIGN.md 3.2).  A translation unit of its own: the 36 instances take as long to compile as the rest of fusion.hip.
-// (fusion_multi4.hip / fusion_multi8.hip: the four- and eight-view instances for class counts up to 24.)
+// (fusion_multi4.hip / fusion_multi8.hip: the four- and eight-view instances, for class counts up to 40.)
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
@@ -21,7 +21,7 @@ void smesh_launch_fuse_tri_8(int kind, int tri_ct, dim3 grid, hipStream_t st, co
 
 // `tri_ct`: the class-count slot smesh_aggregator_fuse_triangles chose (exact instances 5 / 13 / 19 / 20 / 21 / 40; run-time-C
 // instances sized 8, 16, 24, 32, 40 [slot 41], 48).  One wave per workgroup; `grid` as for the one-view kernel.  `nviews`: 2, 4 or 8
-// (4 and 8: class counts up to 24 only), the first `nviews` entries of `tv`.
+// (4 and 8: class counts up to 40 only -- every slot but 48), the first `nviews` entries of `tv`.
 void smesh_launch_fuse_tri_multi(int kind, int tri_ct, int nviews, dim3 grid, hipStream_t st, const TriFuseArgs& t, const TriViews<8>& tv) {
   if (nviews == 8) { smesh_launch_fuse_tri_8(kind, tri_ct, grid, st, t, tv); return; }
   if (nviews == 4) { smesh_launch_fuse_tri_4(kind, tri_ct, grid, st, t, tv); return; }
