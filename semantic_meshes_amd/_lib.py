@@ -146,6 +146,24 @@ VERTEX_SIGNATURES = {
     "smesh_renderer_texel_face_rows": (c_int, [c_void_p, c_void_p, c_int, c_u32, c_int, c_float, c_void_p, c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_eval.h: confusion matrices and primitive labels,
+# product-only like the tables above
+PROF_CONFUSION = 5
+EVAL_SIGNATURES = {
+    "smesh_confusion_create": (c_int, [c_u32, c_int, P(c_void_p)]),
+    "smesh_confusion_destroy": (c_int, [c_void_p]),
+    "smesh_confusion_reset": (c_int, [c_void_p]),
+    "smesh_confusion_get": (c_int, [c_void_p, c_void_p, P(c_u64)]),
+    "smesh_confusion_add_counts": (c_int, [c_void_p, c_void_p, c_u64]),
+    "smesh_confusion_add_labels": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_u64]),
+    "smesh_aggregator_labels": (c_int, [c_void_p, c_float, c_void_p, c_int]),
+    "smesh_confusion_add_image": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int, c_void_p, c_u64, c_int,
+                                          c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64]),
+    "smesh_confusion_add_view": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_void_p, c_u64, c_void_p, c_int, P(ctypes.c_int64), c_int]),
+    "smesh_confusion_add_views": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, c_void_p, c_u64, P(c_void_p), c_int,
+                                          P(ctypes.c_int64), c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -273,7 +291,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -89,6 +89,12 @@ void dev_cache_stats(uint64_t* live_blocks, uint64_t* cached_blocks, uint64_t* c
 // Run-time options (smesh_set_option; the environment supplies the defaults).  group_pipeline: smesh_fuse_views rasterises group
 // g + 1 on the raster stream beside the fusion of group g (default on; SMESH_GROUP_PIPELINE=0).
 bool opt_group_pipeline();
+// confusion_wave_aggregate: k_confusion adds the population count of the lanes that share a key once (default on; eval.hip).
+bool opt_confusion_wave_aggregate();
+
+// Largest class count whose confusion matrix a workgroup of k_confusion keeps as a private uint32 histogram in LDS (eval.hip, where
+// the budget is stated and this value is checked against it).  Read-only option "confusion_lds_max_classes" (smesh_get_option).
+constexpr uint32_t kConfusionLdsMaxC = 180;
 
 // Grow-only device scratch buffer.
 struct Scratch {
@@ -231,3 +237,12 @@ int smesh_aggregator_with_final_rows(smesh_aggregator* a,
 // for a renderer of triangle primitives.
 int smesh_renderer_texel_tables(const smesh_renderer* r, smesh::DeviceCtx** ctx, uint64_t* F, uint64_t* P, const uint32_t** first,
                                 const uint32_t** res);
+// The label of every row of a dense float32 [n, C] device array by the rule of smesh_vertices.h for a vertex with that one row
+// (vertices.hip: k_vertex_gather, one row per item); `out_labels`: int32[n] in `out_memkind`.  Context locked, device current.
+int smesh_rows_labels(smesh::DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, float dont_care_threshold, int32_t* out_labels,
+                      int out_memkind);
+// What the confusion matrices (eval.hip) need from a renderer: `n` views (at most eight) rasterised on the context's main stream with
+// FULLY WRITTEN index planes, and `use(view, idx, W, H)` called for each with the renderer and its context locked -- what `use`
+// queues on the main stream reads the plane before anything overwrites it.  `P` must be the renderer's primitive count.
+int smesh_renderer_with_index_planes(smesh_renderer* r, const smesh_camera_t* cams, int n, uint64_t P, smesh::DeviceCtx* ctx,
+                                     const std::function<int(int view, const uint32_t* idx, uint64_t W, uint64_t H)>& use);

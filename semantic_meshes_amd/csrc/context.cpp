@@ -30,6 +30,9 @@ int fail_hip(hipError_t e, const char* what, const char* file, int line) {
   return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SMESH_ERR_NODEVICE : SMESH_ERR_RUNTIME;
 }
 
+static std::atomic<int> g_confusion_wave_aggregate{1};   // (on: it pays on uniform label images, profiles/confusion_bench.json)
+bool opt_confusion_wave_aggregate() { return g_confusion_wave_aggregate.load() != 0; }
+
 static std::atomic<int> g_group_pipeline{-1};   // -1: not decided yet (the environment, else on)
 bool opt_group_pipeline() {
   int v = g_group_pipeline.load();
@@ -320,6 +323,9 @@ const char* smesh_last_error(void) { return g_err.c_str(); }
 int smesh_set_option(const char* name, int64_t value) {
   if (!name) return fail(SMESH_ERR_INVALID, "option name is NULL");
   if (!strcmp(name, "group_pipeline")) { g_group_pipeline.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  // k_confusion (eval.hip): lanes of a wave that share a key add their population count once (1, the default), or every lane adds 1
+  // for itself (0) -- same counts; tools/confusion_bench.py measures both
+  if (!strcmp(name, "confusion_wave_aggregate")) { g_confusion_wave_aggregate.store(value != 0 ? 1 : 0); return SMESH_OK; }
   return fail(SMESH_ERR_INVALID, std::string("unknown option: ") + name);
 }
 int smesh_get_option(const char* name, int64_t* value) {
@@ -327,6 +333,9 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "group_pipeline")) { *value = opt_group_pipeline() ? 1 : 0; return SMESH_OK; }
   // read-only: up to this class count k_fuse_tri_labels keeps a wave's rows in LDS, beyond it read-modify-writes them in global memory
   if (!strcmp(name, "labels_lds_max_classes")) { *value = (int64_t)kLabelsLdsMaxC; return SMESH_OK; }
+  // read-only: up to this class count k_confusion keeps a workgroup's histogram in LDS, beyond it adds straight into global memory
+  if (!strcmp(name, "confusion_lds_max_classes")) { *value = (int64_t)kConfusionLdsMaxC; return SMESH_OK; }
+  if (!strcmp(name, "confusion_wave_aggregate")) { *value = opt_confusion_wave_aggregate() ? 1 : 0; return SMESH_OK; }
   // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --
   // "last_fuse_slot": the class-count slot handed to k_fuse_tri (5 / 13 / 19 / 20 / 21 / 40: the exact instances; 8 / 16 / 24 / 32 / 41 / 48:
   // the run-time-C instances with 8 .. 32, 40 and 48 register slots), 0 when the launch was k_fuse_tri_any, k_fuse_tri_wide or

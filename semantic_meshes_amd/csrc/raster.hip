@@ -2677,6 +2677,48 @@ int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, con
   return SMESH_OK;
 }
 
+// ---- confusion matrices (include/smesh_eval.h; the entry points are eval.hip's) --------------------------------------------------------
+// n <= kMaxGroup views rasterised on the MAIN stream, every index plane fully written (idx_optional = 0: the planes are what the
+// caller reads, there are no records to stand in for them), then use(v, plane, W, H) for each.  Two views and more share their
+// rasteriser launches (render_group_into, slots 0 .. n-1) where smesh_fuse_views would group them; else view by view through
+// slot 0, each plane consumed on the stream before the next render overwrites it.  Locks and stream hand-over as fuse_view_impl.
+int smesh_renderer_with_index_planes(smesh_renderer* r, const smesh_camera_t* cams, int n, uint64_t P, DeviceCtx* want_ctx,
+                                     const std::function<int(int view, const uint32_t* idx, uint64_t W, uint64_t H)>& use) {
+  if (!r || (n && !cams) || n < 0 || n > kMaxGroup) return fail(SMESH_ERR_INVALID, "bad argument");
+  for (int v = 0; v < n; v++) SMESH_TRY(check_camera(&cams[v]));
+  DeviceCtx* ctx = r->ctx;
+  if (ctx != want_ctx) return fail(SMESH_ERR_INVALID, "confusion matrix and renderer live on different devices");
+  if (P != r->num_primitives)
+    return fail(SMESH_ERR_INVALID, "the label table has " + std::to_string(P) + " entries, the renderer " + std::to_string(r->num_primitives) + " primitives");
+  if (n == 0) return SMESH_OK;
+  std::lock_guard<std::mutex> g(r->mu);
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  SMESH_HIP(hipSetDevice(ctx->device));
+  SMESH_TRY(main_after_raster(r));   // (a pipelined smesh_fuse_views call may still be rasterising into the view slots)
+  r->main_pending = true;            // the next pipelined group must wait for what this call does to the slots on the main stream
+  bool grouped = n >= 2 && r->F != 0 && r->V != 0;
+  for (int v = 0; v < n && grouped; v++) grouped = queues_fit_group(cams[v].width, cams[v].height);
+  if (grouped) {
+    SMESH_TRY(render_group_into(r, cams, n, ctx->stream, 0, -1, /*idx_optional=*/0));
+    for (int v = 0; v < n; v++) SMESH_TRY(use(v, static_cast<const uint32_t*>(r->fused[v].ptr), cams[v].width, cams[v].height));
+    return SMESH_OK;
+  }
+  for (int v = 0; v < n; v++) {
+    const uint64_t N = cams[v].width * cams[v].height;
+    if (r->fused[0].bytes < N * 8) {
+      // growing a slot frees the old buffer: nothing may still be reading it
+      SMESH_HIP(hipStreamSynchronize(ctx->raster_stream));
+      SMESH_HIP(hipStreamSynchronize(ctx->stream));
+      SMESH_TRY(r->fused[0].reserve(N * 8));
+    }
+    uint32_t* d_idx = static_cast<uint32_t*>(r->fused[0].ptr);
+    r->last_idx[0] = nullptr; r->rec_valid[0] = false;   // the records of a render_device() on this side are being overwritten
+    SMESH_TRY(render_into(r, &cams[v], d_idx, /*d_depth=*/nullptr, ctx->stream, 0, /*idx_optional=*/0));
+    SMESH_TRY(use(v, d_idx, cams[v].width, cams[v].height));
+  }
+  return SMESH_OK;
+}
+
 // smesh_aggregator_add_rendered for a label plane: *done = 1 if `idx_dev` is the untouched output of one of r's latest
 // smesh_renderer_render_device() calls and the view was fused from that render's records (k_fuse_tri_labels, or -- labels expanded --
 // the triangle / texel kernels of the class-vector path); *done = 0: nothing happened.

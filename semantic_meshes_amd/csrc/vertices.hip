@@ -175,8 +175,8 @@ __global__ __launch_bounds__(kBlock) void k_vtx_sort_long(const uint32_t* __rest
 
 // ---- the gather ----------------------------------------------------------------------------------------------------------------
 struct GatherArgs {
-  // items: the vertices of a map (offsets + list name the rows of each) or the faces of a texel layout (list == nullptr: item i owns
-  // the rows [seg_first[i], seg_first[i] + seg_res[i] (seg_res[i] + 1) / 2))
+  // items: the vertices of a map (offsets + list name the rows of each), the faces of a texel layout (list == nullptr: item i owns
+  // the rows [seg_first[i], seg_first[i] + seg_res[i] (seg_res[i] + 1) / 2)) or the rows themselves (neither: item i owns row i)
   const uint32_t* offsets;
   const uint32_t* list;
   const uint32_t* seg_first;
@@ -209,7 +209,8 @@ __global__ __launch_bounds__(kBlock) void k_vertex_gather(GatherArgs a) {
   uint32_t beg = 0, end = 0;
   if (valid) {
     if (a.list) { beg = a.offsets[item]; end = a.offsets[item + 1]; }
-    else { const uint32_t r = a.seg_res[item]; beg = a.seg_first[item]; end = beg + r * (r + 1) / 2; }
+    else if (a.seg_first) { const uint32_t r = a.seg_res[item]; beg = a.seg_first[item]; end = beg + r * (r + 1) / 2; }
+    else { beg = (uint32_t)item; end = beg + 1u; }
   }
   const uint32_t* const list = a.list;
   const float* const rows = a.rows;
@@ -442,6 +443,20 @@ int build_map(smesh_vertex_map* m, const int32_t* faces) {
 }
 
 }  // namespace
+
+// What eval.hip (smesh_aggregator_labels) needs: the label of every row of a dense float32 [n, C] array on the device -- a vertex
+// that owns exactly one row: 0 + x == x, so the row total and the label are those of the row itself.  Context locked, device current.
+int smesh_rows_labels(DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, float dont_care_threshold, int32_t* out_labels, int out_memkind) {
+  SMESH_TRY(check_gather_args(C, SMESH_VTX_ANNOTATIONS, nullptr, out_labels, SMESH_MEM_DEVICE, out_memkind));
+  if (n >= 0xFFFFFFFFull) return fail(SMESH_ERR_INVALID, "labels: the row count must stay below 2^32");
+  GatherArgs g = {};
+  g.rows = d_rows;
+  g.n = n;
+  g.C = C;
+  g.mode = SMESH_VTX_ANNOTATIONS;
+  g.threshold = dont_care_threshold;
+  return gather_device_rows(ctx, g, nullptr, out_labels, out_memkind);
+}
 
 extern "C" {
 

@@ -482,6 +482,29 @@ class _MeshAggregator:
         self._drain()     # (get() waited for the stream: every earlier call's reads are over)
         return out
 
+    def _labels(self, dont_care_threshold, on_device):
+        if on_device:
+            from .device import DeviceBuffer
+            out = DeviceBuffer(max(self.primitives * 4, 4), self.device).view((self.primitives,), np.int32)
+            ptr, mem = ctypes.c_void_p(out.ptr), _lib.MEM_DEVICE
+        else:
+            out = np.empty(self.primitives, np.int32)
+            ptr, mem = out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST
+        # (`_h`: the deferred views are handed to the library first, as get() does)
+        _lib.check(_lib.lib().smesh_aggregator_labels(self._h, float(dont_care_threshold), ptr, mem))
+        self._drain()
+        return out
+
+    def labels(self, dont_care_threshold=0.9):
+        """int32 [P]: per primitive, the class with the largest value of `get()` (the lowest one among equals), -1 where the row's
+        float32 sum, taken in ascending class order, is below `dont_care_threshold`.  No [P,C] array leaves the device."""
+        return self._labels(dont_care_threshold, False)
+
+    def labels_device(self, dont_care_threshold=0.9):
+        """`labels()` left in HBM: a `DeviceArray` in a fresh allocation owned by the returned object -- what
+        `ConfusionMatrix.add_views` / `add_image` take as their label table."""
+        return self._labels(dont_care_threshold, True)
+
     def get_rows(self, row_lo, row_hi):
         """`get()` for the rows [row_lo, row_hi) only (row_lo a multiple of 4): what a rank owns after
         `Communicator.reduce_scatter` (new functionality)."""
@@ -844,3 +867,7 @@ def MeshAggregator(primitives, classes, aggregator="sum", images_equal_weight=0.
     if name not in _CLASSES:
         raise ValueError("unknown aggregator %r (expected one of sum, summax, mul)" % (aggregator,))
     return _CLASSES[name](primitives, classes, name, images_equal_weight, device)
+
+
+# Confusion matrices of the fused mesh against ground truth (include/smesh_eval.h)
+from .evaluation import ConfusionMatrix, confusion_accuracy, confusion_iou, confusion_mean_iou  # noqa: E402,F401
