@@ -164,6 +164,18 @@ EVAL_SIGNATURES = {
                                           P(ctypes.c_int64), c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_label_images.h: the fused mesh rendered back into the
+# views as label and colour images, product-only like the tables above
+PROF_LABEL_IMAGES = 6
+LAYOUT_WH, LAYOUT_HW = 0, 1
+LABEL_IMAGE_SIGNATURES = {
+    "smesh_label_renderer_create": (c_int, [c_void_p, c_u64, c_int, c_u32, c_int, c_u32, c_void_p, c_void_p, c_int, P(c_void_p)]),
+    "smesh_label_renderer_destroy": (c_int, [c_void_p]),
+    "smesh_label_renderer_render_image": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_int,
+                                                  c_void_p, c_void_p, c_int]),
+    "smesh_label_renderer_render_views": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, c_int, P(c_void_p), P(c_void_p), c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -291,7 +303,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args
