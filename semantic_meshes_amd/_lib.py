@@ -118,6 +118,14 @@ SIGNATURES = {
     "smesh_memcpy": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_int, c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_meshlets.h: the grouped rasteriser's per-block vertex
+# tables (built on the host, no device needed) and which path its last launch took; product-only like the tables below
+MESHLET_SIGNATURES = {
+    "smesh_meshlets_build": (c_int, [c_void_p, c_u64, c_u64, c_void_p, c_void_p, c_u64, c_void_p, P(c_u64), P(c_int)]),
+    "smesh_last_raster_path": (ctypes.c_char_p, []),
+}
+MESHLET_TRIS, MESHLET_MAX_VERTS = 256, 384      # SMESH_MESHLET_TRIS / SMESH_MESHLET_MAX_VERTS
+
 # Label dtypes of include/smesh_labels.h (SMESH_LBL_*), by numpy dtype string
 LBL_CODES = {"uint8": 0, "int8": 1, "uint16": 2, "int16": 3, "uint32": 4, "int32": 5, "uint64": 6, "int64": 7}
 
@@ -303,7 +311,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args
@@ -347,6 +355,25 @@ def last_add_path():
     """Which path the calling thread's last add() took (`smesh_last_add_path`); deferred views are handed over first."""
     flush_pending()
     return lib().smesh_last_add_path().decode()
+
+
+def last_raster_path():
+    """Which path the calling thread's last grouped raster launch took (`smesh_last_raster_path`): "meshlets", "vertex-stage" or
+    "none"; deferred views are handed over first."""
+    flush_pending()
+    return lib().smesh_last_raster_path().decode()
+
+
+def set_option(name, value):
+    """`smesh_set_option`: a run-time option by name (include/smesh.h), e.g. "raster_meshlets"."""
+    check(lib().smesh_set_option(name.encode(), int(value)))
+
+
+def get_option(name):
+    """`smesh_get_option`: the value of a run-time option."""
+    v = ctypes.c_int64(0)
+    check(lib().smesh_get_option(name.encode(), ctypes.byref(v)))
+    return v.value
 
 
 def synchronize(device=0):

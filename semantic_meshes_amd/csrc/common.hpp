@@ -89,6 +89,10 @@ void dev_cache_stats(uint64_t* live_blocks, uint64_t* cached_blocks, uint64_t* c
 // Run-time options (smesh_set_option; the environment supplies the defaults).  group_pipeline: smesh_fuse_views rasterises group
 // g + 1 on the raster stream beside the fusion of group g (default on; SMESH_GROUP_PIPELINE=0).
 bool opt_group_pipeline();
+// raster_meshlets: the grouped launches of the one-lane-per-triangle rasteriser instances read per-block vertex tables built once per
+// renderer and run without a vertex stage (raster.hip: render_group_into; SMESH_RASTER_MESHLETS=0 / 1).
+constexpr int kRasterMeshletsDefault = 1;
+bool opt_raster_meshlets();
 // confusion_wave_aggregate: k_confusion adds the population count of the lanes that share a key once (default on; eval.hip).
 bool opt_confusion_wave_aggregate();
 

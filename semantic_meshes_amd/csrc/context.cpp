@@ -44,6 +44,19 @@ bool opt_group_pipeline() {
   return v != 0;
 }
 
+// "raster_meshlets": grouped raster launches of the one-lane-per-triangle instances read the renderer's meshlet tables and have no
+// vertex stage (raster.hip: render_group_into).  Same results either way.
+static std::atomic<int> g_raster_meshlets{-1};   // -1: not decided yet (the environment, else the default)
+bool opt_raster_meshlets() {
+  int v = g_raster_meshlets.load();
+  if (v < 0) {
+    const char* e = getenv("SMESH_RASTER_MESHLETS");
+    v = e ? (atoi(e) != 0 ? 1 : 0) : kRasterMeshletsDefault;
+    g_raster_meshlets.store(v);
+  }
+  return v != 0;
+}
+
 static std::mutex g_ctx_mu;
 static std::vector<std::unique_ptr<DeviceCtx>> g_ctx;
 
@@ -323,6 +336,7 @@ const char* smesh_last_error(void) { return g_err.c_str(); }
 int smesh_set_option(const char* name, int64_t value) {
   if (!name) return fail(SMESH_ERR_INVALID, "option name is NULL");
   if (!strcmp(name, "group_pipeline")) { g_group_pipeline.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  if (!strcmp(name, "raster_meshlets")) { g_raster_meshlets.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // k_confusion (eval.hip): lanes of a wave that share a key add their population count once (1, the default), or every lane adds 1
   // for itself (0) -- same counts; tools/confusion_bench.py measures both
   if (!strcmp(name, "confusion_wave_aggregate")) { g_confusion_wave_aggregate.store(value != 0 ? 1 : 0); return SMESH_OK; }
@@ -331,6 +345,7 @@ int smesh_set_option(const char* name, int64_t value) {
 int smesh_get_option(const char* name, int64_t* value) {
   if (!name || !value) return fail(SMESH_ERR_INVALID, "NULL argument");
   if (!strcmp(name, "group_pipeline")) { *value = opt_group_pipeline() ? 1 : 0; return SMESH_OK; }
+  if (!strcmp(name, "raster_meshlets")) { *value = opt_raster_meshlets() ? 1 : 0; return SMESH_OK; }
   // read-only: up to this class count k_fuse_tri_labels keeps a wave's rows in LDS, beyond it read-modify-writes them in global memory
   if (!strcmp(name, "labels_lds_max_classes")) { *value = (int64_t)kLabelsLdsMaxC; return SMESH_OK; }
   // read-only: up to this class count k_confusion keeps a workgroup's histogram in LDS, beyond it adds straight into global memory

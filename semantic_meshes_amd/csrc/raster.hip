@@ -19,6 +19,8 @@
 // Depth test: a pixel holds one 64-bit key (float bits of z << 32 | primitive id); nearer z wins and equal
 // z resolves to the lower id, so the result does not depend on the order triangles are processed in.
 #include "common.hpp"
+#include "meshlets.hpp"
+#include "../../include/smesh_meshlets.h"
 
 #include <algorithm>
 #include <cmath>
@@ -314,6 +316,14 @@ struct RasterArgs {
 // make neighbouring fragments share cache lines: no change in k_raster_small, slower resolve.)
 __device__ __forceinline__ uint64_t key_index(uint32_t x, uint32_t y, uint32_t H) { return (uint64_t)x * H + y; }
 
+// Projected vertex i of the view.  A grouped launch that reads meshlets (k_raster_frag_group_ml) has no vertex stage and leaves a.sv null:
+// the few triangles its OTHER kernels handle (the queued ones: raster_huge_block, load_piece) project their vertices on the spot --
+// project_point, the function the vertex stage calls: the same bits.
+__device__ __forceinline__ ScreenVertex screen_vertex(const RasterArgs& a, const int32_t i) {
+  if (a.sv) return a.sv[i];
+  return project_point(a.cam, a.verts[3 * (uint64_t)i + 0], a.verts[3 * (uint64_t)i + 1], a.verts[3 * (uint64_t)i + 2]);
+}
+
 __device__ __forceinline__ bool load_tri(const RasterArgs& a, uint64_t f, Tri& t, const int32_t i0, const int32_t i1, const int32_t i2);
 __device__ __forceinline__ bool load_tri(const RasterArgs& a, uint64_t f, Tri& t) {
   return load_tri(a, f, t, a.faces[3 * f + 0], a.faces[3 * f + 1], a.faces[3 * f + 2]);
@@ -324,7 +334,7 @@ __device__ __forceinline__ bool load_tri(const RasterArgs& a, uint64_t f, Tri& t
   if ((uint64_t)max((uint32_t)i0, max((uint32_t)i1, (uint32_t)i2)) >= a.V) return false;
   if (a.tex_res && a.tex_res[f] == 0) return false;
   // all three vertices are fetched before any of them is tested: one memory round trip instead of three
-  const ScreenVertex va = a.sv[i0], vb = a.sv[i1], vc = a.sv[i2];
+  const ScreenVertex va = screen_vertex(a, i0), vb = screen_vertex(a, i1), vc = screen_vertex(a, i2);
   return setup_tri(va, vb, vc, a.W, a.H, t);
 }
 
@@ -434,7 +444,7 @@ __device__ __forceinline__ bool load_piece(const RasterArgs& a, const uint64_t f
   const int32_t i0 = a.faces[3 * f + 0], i1 = a.faces[3 * f + 1], i2 = a.faces[3 * f + 2];
   if ((uint64_t)max((uint32_t)i0, max((uint32_t)i1, (uint32_t)i2)) >= a.V) return false;
   if (a.tex_res && a.tex_res[f] == 0) return false;
-  const ScreenVertex va = a.sv[i0], vb = a.sv[i1], vc = a.sv[i2];
+  const ScreenVertex va = screen_vertex(a, i0), vb = screen_vertex(a, i1), vc = screen_vertex(a, i2);
   const int cls = clip_class(va, vb, vc);
   pc.clipped = cls > 0;
   if (cls < 0) return false;
@@ -477,14 +487,37 @@ __device__ __forceinline__ unsigned long long shade_piece_key(const RasterArgs& 
 
 // load_tri for the one-lane-per-triangle kernels: 1 = an ordinary triangle, set up in `t`; 2 = a triangle that crosses the near
 // plane, t.x0 .. t.y1 = the screen box of what is left of it (to be shaded piece by piece, load_piece); 0 = nothing to draw.
+// (NULLABLE_SV: a.sv may be null, screen_vertex -- not for the one-lane-per-triangle kernels, which always have the array or meshlets)
+template <bool NULLABLE_SV = false>
 __device__ __forceinline__ int load_tri_ex(const RasterArgs& a, uint64_t f, Tri& t, const int32_t i0, const int32_t i1, const int32_t i2) {
   if ((uint64_t)max((uint32_t)i0, max((uint32_t)i1, (uint32_t)i2)) >= a.V) return 0;
   if (a.tex_res && a.tex_res[f] == 0) return 0;
-  const ScreenVertex va = a.sv[i0], vb = a.sv[i1], vc = a.sv[i2];
+  ScreenVertex va, vb, vc;
+  if constexpr (NULLABLE_SV) { va = screen_vertex(a, i0); vb = screen_vertex(a, i1); vc = screen_vertex(a, i2); }
+  else { va = a.sv[i0]; vb = a.sv[i1]; vc = a.sv[i2]; }
   const int cls = clip_class(va, vb, vc);
   if (cls == 0) return setup_tri(va, vb, vc, a.W, a.H, t) ? 1 : 0;
   if (cls < 0) return 0;
   return clip_bbox(a, i0, i1, i2, va, vb, vc, cls, t.x0, t.y0, t.x1, t.y1) ? 2 : 0;
+}
+
+// A lane's triangle as a meshlet workgroup hands it over (k_raster_frag_group_ml): its three projected vertices, read from the block's
+// table in LDS, and -- for the rare triangle that crosses the near plane, which re-reads its world-space vertices -- where the
+// block's global vertex ids are and which three of them it uses.
+struct MeshletTri {
+  ScreenVertex va, vb, vc;
+  const uint32_t* ids;       // the block's list of global vertex ids
+  uint32_t l0, l1, l2;       // the triangle's positions in it
+};
+// load_tri_ex for such a triangle: the same tests in the same order on the same vertex values (the table holds only valid indices:
+// build_meshlets refuses a mesh with any other).
+__device__ __forceinline__ int load_tri_ml(const RasterArgs& a, uint64_t f, Tri& t, const MeshletTri& m) {
+  if (a.tex_res && a.tex_res[f] == 0) return 0;
+  const int cls = clip_class(m.va, m.vb, m.vc);
+  if (cls == 0) return setup_tri(m.va, m.vb, m.vc, a.W, a.H, t) ? 1 : 0;
+  if (cls < 0) return 0;
+  const int32_t i0 = (int32_t)m.ids[m.l0], i1 = (int32_t)m.ids[m.l1], i2 = (int32_t)m.ids[m.l2];
+  return clip_bbox(a, i0, i1, i2, m.va, m.vb, m.vc, cls, t.x0, t.y0, t.x1, t.y1) ? 2 : 0;
 }
 
 // Depth-test key of triangle f at sample (x, y), or kNullKey if the sample is not covered.
@@ -518,7 +551,7 @@ __global__ void k_raster_small(RasterArgs a) {
   TriFrag rec;
   rec.x0 = 0; rec.y0 = 0; rec.kind = 0; rec.pad = 0; rec.mask = 0ull;
   Tri t;
-  const int have = load_tri_ex(a, f, t, a.faces[3 * f + 0], a.faces[3 * f + 1], a.faces[3 * f + 2]);
+  const int have = load_tri_ex<>(a, f, t, a.faces[3 * f + 0], a.faces[3 * f + 1], a.faces[3 * f + 2]);
   if (have) {
     const int bw = t.x1 - t.x0 + 1, bh = t.y1 - t.y0 + 1;
     rec.x0 = (uint16_t)t.x0; rec.y0 = (uint16_t)t.y0;
@@ -819,9 +852,12 @@ __device__ __forceinline__ void coop_walk(const RasterArgs& a, const Tri& t, con
 // 97 -> 125: a second dependent round trip for every wave costs more than the bytes.  Not kept.)  (Round 6 also built instances whose lanes project their
 // triangles' vertices themselves -- no vertex stage, no 24-byte record per vertex and view: k_raster_frag_group 195 -> 242 us per eight
 // cfg2 views for 24 us of vertex stage saved, cfg4 668 -> 814 for 106; not kept.)
-template <int MODE>
+// ML: the lane's triangle comes as a MeshletTri (`ml`; i0 .. i2 unused) -- everything after its set-up is the same code.
+// NULLABLE_SV: load_tri_ex's.
+template <int MODE, bool ML = false, bool NULLABLE_SV = false>
 __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64_t f, const int32_t i0, const int32_t i1, const int32_t i2,
-                                               const uint32_t sub, const int part_in = -1, const bool listed = false) {
+                                               const uint32_t sub, const int part_in = -1, const bool listed = false,
+                                               const MeshletTri* ml = nullptr) {
   constexpr bool kWgPush = (MODE & 1) != 0, kSpreadMode = (MODE & 2) != 0, kTex = (MODE & 4) != 0;
   const int lane = threadIdx.x & 63;
   const int part = kSpreadMode ? part_in : -1;
@@ -835,7 +871,9 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
   bool medium = false, lanebox = false, small = false;
   bool q_big = false, q_mid = false, q_huge = false;   // this lane's triangle goes into the view's queues (below, one atomic per wave and queue)
   const uint32_t pid = (a.prim_id && f < a.F) ? a.prim_id[f] : (uint32_t)f;   // value written to the index image
-  const int have = f < a.F ? load_tri_ex(a, f, t, i0, i1, i2) : 0;   // 2: crosses the near plane (t holds only its screen box)
+  int have = 0;                                                      // 2: crosses the near plane (t holds only its screen box)
+  if constexpr (ML) { if (f < a.F) have = load_tri_ml(a, f, t, *ml); }
+  else { if (f < a.F) have = load_tri_ex<NULLABLE_SV>(a, f, t, i0, i1, i2); }
   if (have) {
     const int bw = t.x1 - t.x0 + 1, bh = t.y1 - t.y0 + 1;
     rec.x0 = (uint16_t)t.x0; rec.y0 = (uint16_t)t.y0;
@@ -1000,7 +1038,7 @@ __device__ __forceinline__ void raster_medium_wave(const RasterArgs& a, const ui
     if (g >= a.F) continue;
     const int32_t g0 = a.faces[3 * (uint64_t)g + 0], g1 = a.faces[3 * (uint64_t)g + 1], g2 = a.faces[3 * (uint64_t)g + 2];
     Tri t;
-    if (load_tri_ex(a, g, t, g0, g1, g2) != 1) continue;            // (never: its owner lane found it drawable)
+    if (load_tri_ex<true>(a, g, t, g0, g1, g2) != 1) continue;            // (never: its owner lane found it drawable)
     uint32_t rb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     if (lane == 0) coop_reserve(a, t, i & (kQSub - 1), rb);
     coop_walk<TEX>(a, t, rb, 0, g, a.prim_id ? a.prim_id[g] : g, i & (kQSub - 1));
@@ -1016,7 +1054,7 @@ __device__ __forceinline__ void raster_medium_wave(const RasterArgs& a, const ui
     if (tri < kTris && e < nl) fs = a.med_queue[a.big_capacity - 1u - e];
     int32_t s0 = 0, s1 = 0, s2 = 0;
     if (fs < a.F) { s0 = a.faces[3 * fs + 0]; s1 = a.faces[3 * fs + 1]; s2 = a.faces[3 * fs + 2]; }
-    raster_frag_64<TEX ? 6 : 2>(a, fs, s0, s1, s2, i & (kQSub - 1), lane % kLanes, true);
+    raster_frag_64<TEX ? 6 : 2, false, true>(a, fs, s0, s1, s2, i & (kQSub - 1), lane % kLanes, true);
   }
 }
 template <bool TEX>
@@ -1096,6 +1134,11 @@ struct RasterGroup {
   uint32_t tile_end[kMaxGroup];   // ... whose tiles are blocks [tile_end[v-1], tile_end[v])
   uint32_t n, blocks_per_view;
   uint32_t chunk;                 // k_raster_frag_group: nonzero = XCD-aware placement (below): consecutive triangle blocks per run of an XCD
+  // k_raster_frag_group_ml: the renderer's meshlet tables (meshlets.hpp), else null
+  const uint32_t* ml_first;       // [blocks_per_view + 1]
+  const uint32_t* ml_ids;
+  const float* ml_pos;            // world-space position of every entry of ml_ids (a copy: one coalesced read, no gather through the ids)
+  const uint32_t* ml_tris;        // [F]
 };
 // (five waves per SIMD -- 96 registers -- for the small-triangle instance; the instances for views of medium triangles may take 128: at 96
 // they spill, and their waves are long)
@@ -1116,6 +1159,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 3) 
     tb = blockIdx.x - v * g.blocks_per_view;
   }
   raster_frag_wave<true, MODE>(g.view[v], ((uint64_t)tb * blockDim.x + threadIdx.x) >> 6);
+}
+// The same launch from meshlets (MODE 0 and 4: one triangle per lane, no spread, no wg_push; RasterArgs::tpw = 64, groups = 1, so that the
+// workgroup's 256 lanes hold exactly triangle block tb of meshlets.hpp).  No vertex stage ran and view[v].sv is null: the workgroup projects
+// the block's distinct vertices -- ~0.6 per triangle of a regular mesh, the vertex stage's 0.5 -- for ITS view into LDS, with the vertex
+// stage's project_point, and its lanes take their three vertices from there: the 24-byte record per vertex and view is neither written
+// (96 MB per eight cfg2 views) nor gathered back through faces -> index -> record, the second dependent round trip of every wave.  What
+// a workgroup reads instead -- its block's packed local indices and raw vertices, a few KB -- is shared by the launch's views, which
+// run back to back on the block's XCD (placement as above).  Everything after the triangle's set-up is raster_frag_64 as it was.
+template <int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_raster_frag_group_ml(RasterGroup g) {
+  static_assert((MODE & 3) == 0, "one triangle per lane only");
+  __shared__ double s_u[kMeshletMaxVerts], s_v[kMeshletMaxVerts], s_iz[kMeshletMaxVerts];
+  uint32_t v, tb;
+  if (g.chunk) {
+    const uint32_t k = blockIdx.x >> 3, sq = k / g.n;
+    v = k - sq * g.n;
+    tb = xcd_block(blockIdx.x & 7u, sq, g.chunk);
+    if (tb >= g.blocks_per_view) return;               // block-uniform, and ahead of the barrier below
+  } else {
+    v = blockIdx.x / g.blocks_per_view;                // block-uniform
+    tb = blockIdx.x - v * g.blocks_per_view;
+  }
+  const RasterArgs& a = g.view[v];
+  const uint32_t id0 = g.ml_first[tb];
+  const uint32_t nv = min(g.ml_first[tb + 1] - id0, kMeshletMaxVerts);      // (build_meshlets keeps every block within the cap)
+  const uint32_t* __restrict__ ids = g.ml_ids + id0;
+  // (the positions come from the table's own copy of them, in the order of the block's list: the first thing a workgroup asks memory
+  // for, beside its packed indices -- a gather through the ids would be the dependent round trip this kernel exists to remove)
+  const float* __restrict__ pos = g.ml_pos + 3u * (uint64_t)id0;
+  for (uint32_t i = threadIdx.x; i < nv; i += 256u) {
+    const ScreenVertex s = project_point(a.cam, pos[3u * i + 0u], pos[3u * i + 1u], pos[3u * i + 2u]);
+    s_u[i] = s.u; s_v[i] = s.v; s_iz[i] = s.iz;
+  }
+  __syncthreads();
+  const uint64_t f = (uint64_t)tb * 256u + threadIdx.x;
+  MeshletTri m;
+  m.ids = ids;
+  m.l0 = 0u; m.l1 = 0u; m.l2 = 0u;
+  if (f < a.F) {
+    const uint32_t w = g.ml_tris[f];
+    constexpr uint32_t kMask = (1u << kMeshletIndexBits) - 1u;
+    // (local indices are below nv by construction; the clamp keeps a damaged table inside the LDS arrays)
+    m.l0 = min(w & kMask, kMeshletMaxVerts - 1u); m.l1 = min((w >> kMeshletIndexBits) & kMask, kMeshletMaxVerts - 1u);
+    m.l2 = min((w >> (2u * kMeshletIndexBits)) & kMask, kMeshletMaxVerts - 1u);
+  }
+  m.va.u = s_u[m.l0]; m.va.v = s_v[m.l0]; m.va.iz = s_iz[m.l0];
+  m.vb.u = s_u[m.l1]; m.vb.v = s_v[m.l1]; m.vb.iz = s_iz[m.l1];
+  m.vc.u = s_u[m.l2]; m.vc.v = s_v[m.l2]; m.vc.iz = s_iz[m.l2];
+  const uint64_t wave_id = ((uint64_t)tb * 256u + threadIdx.x) >> 6;
+  raster_frag_64<MODE, true>(a, f < a.F ? f : a.F, 0, 0, 0, (uint32_t)wave_id & (kQSub - 1), -1, false, &m);
+}
+// What the vertex stage does besides projecting: it opens the render by emptying the views' queues of large triangles.  For a launch
+// without a vertex stage, on the same stream ahead of the raster kernel.
+struct CountGroup {
+  uint32_t* big_count[kMaxGroup];
+  uint32_t n;
+};
+__global__ void k_reset_big_counts(CountGroup g) {
+  const uint32_t v = threadIdx.x / 6u, k = threadIdx.x - v * 6u;
+  if (v < g.n) g.big_count[v][k] = 0u;
 }
 template <bool TEX>
 __global__ __launch_bounds__(256) void k_raster_medium_group(RasterGroup g, uint32_t blocks_per_view) {
@@ -1435,10 +1538,14 @@ struct smesh_renderer {
   // prove, per camera, that the queue of k_raster_huge stays empty.  valid = every vertex finite, at least one usable face.
   struct Bounds { bool valid = false; double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, max_edge = 0, mean_edge = 0; } bounds;
   uint32_t* prim_id = nullptr;     // [F] primitive id per triangle position, when the triangles were re-ordered (else null)
+  // Meshlet tables of the final face order (meshlets.hpp), built and uploaded once (create_common); all null: the mesh has none
+  // (a block with too many distinct vertices, a face with an index out of range) and every launch keeps the vertex stage
+  // (pos: the positions of the listed vertices, float32[3] per entry of ids -- the mesh's vertices never change)
+  struct Meshlets { uint32_t* first = nullptr; uint32_t* ids = nullptr; uint32_t* tris = nullptr; float* pos = nullptr; } ml;
   // What a render in flight needs besides the per-triangle records, per view slot: smesh_fuse_views rasterises up to
   // kMaxGroup views in the same launches (slots beyond 0 are allocated on first use); every other entry point uses slot 0.
   struct ViewScratch {
-    ScreenVertex* sv = nullptr;      // projected vertices [V]
+    ScreenVertex* sv = nullptr;      // projected vertices [V] (slots beyond 0: allocated by the first launch with a vertex stage, alloc_scratch)
     uint32_t* huge_queue = nullptr;  // [big_capacity] triangles larger than kMedium x kMedium
     uint32_t* med_queue = nullptr;   // [big_capacity] RasterArgs::med_queue
     unsigned long long* keys = nullptr;   // global key image (direct path; overflow of the fragment queues)
@@ -1804,12 +1911,14 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
 }
 
 hipError_t alloc_side(smesh_renderer* r, int i);
+thread_local const char* g_last_raster_path = "none";   // smesh_last_raster_path()
 
 // Scratch of view slot `i` (smesh_fuse_views rasterises several views per launch).
-hipError_t alloc_scratch(smesh_renderer* r, int i) {
+// `need_sv`: the launch has a vertex stage (a slot that only ever sees meshlet launches never gets the 24 bytes per vertex).
+hipError_t alloc_scratch(smesh_renderer* r, int i, bool need_sv) {
   smesh_renderer::ViewScratch& vs = r->vs[i];
   hipError_t e = hipSuccess;
-  if (!vs.sv) e = dev_malloc(reinterpret_cast<void**>(&vs.sv), std::max<uint64_t>(r->V * sizeof(ScreenVertex), 16));
+  if (!vs.sv && need_sv) e = dev_malloc(reinterpret_cast<void**>(&vs.sv), std::max<uint64_t>(r->V * sizeof(ScreenVertex), 16));
   if (e == hipSuccess && !vs.huge_queue) e = dev_malloc(reinterpret_cast<void**>(&vs.huge_queue), (size_t)r->big_capacity * 4);
   if (e == hipSuccess && !vs.med_queue) e = dev_malloc(reinterpret_cast<void**>(&vs.med_queue), (size_t)r->big_capacity * 4);
   return e;
@@ -1831,11 +1940,13 @@ bool queues_fit_group(uint64_t W, uint64_t H) {
 // Everything a group of views needs in view slots base .. base + n - 1 (records, scratch, fragment queues, index planes), allocated
 // and initialised on `st` -- what render_group_into does on first use, callable ahead of time for the OTHER bank of the group
 // pipeline so that no allocation falls between two groups.
+// (The projected-vertex arrays: only where the renderer cannot take meshlet launches at all; a renderer that can gets them when a
+// launch turns out to need the vertex stage -- another instance of the kernel, render_group_into.)
 int prepare_group_slots(smesh_renderer* r, const smesh_camera_t* cams, int n, hipStream_t st, int base) {
   for (int v = 0; v < n; v++) {
     const uint64_t W = cams[v].width, H = cams[v].height, N = W * H;
     SMESH_HIP(alloc_side(r, base + v));
-    SMESH_HIP(alloc_scratch(r, base + v));
+    SMESH_HIP(alloc_scratch(r, base + v, !(r->ml.tris && opt_raster_meshlets())));
     smesh_renderer::ViewScratch& vs = r->vs[base + v];
     SMESH_TRY(ensure_keys(vs, W, H, st));
     int qs = SMESH_OK;
@@ -1864,7 +1975,7 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   for (int v = 0; v < n; v++) {
     const uint64_t W = cams[v].width, H = cams[v].height, N = W * H;
     SMESH_HIP(alloc_side(r, side_base + v));
-    SMESH_HIP(alloc_scratch(r, base + v));
+    SMESH_HIP(alloc_scratch(r, base + v, /*need_sv: decided below, with the launch's mode*/ false));
     smesh_renderer::ViewScratch& vs = r->vs[base + v];
     SMESH_TRY(ensure_keys(vs, W, H, st));
     int qs = SMESH_OK;
@@ -1903,14 +2014,41 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
     for (int v = 0; v < n; v++) rg.view[v].balance = 2 * balance_votes >= n && balance_votes > 0 ? (n > 1 ? 1u : 2u) : 0u;
   }
   for (int v = 0; v < n; v++) rg.view[v].groups = frag_groups(r->F, n, rg.view[0].tpw);
+  // Meshlets (option "raster_meshlets"): the one-lane-per-triangle instances of a renderer that has the tables.  A workgroup then owns
+  // one block of 256 consecutive triangles -- 64 per wave, one group per wave, whatever the mesh's size -- and there is no vertex stage.
+  const int mode = raster_mode(rg.view[0]);
+  const bool meshlets = (mode & 3) == 0 && r->ml.tris != nullptr && opt_raster_meshlets();
+  if (meshlets) {
+    for (int v = 0; v < n; v++) { rg.view[v].tpw = 64u; rg.view[v].groups = 1u; rg.view[v].sv = nullptr; }
+    rg.ml_first = r->ml.first; rg.ml_ids = r->ml.ids; rg.ml_tris = r->ml.tris; rg.ml_pos = r->ml.pos;
+  } else {
+    for (int v = 0; v < n; v++) {
+      SMESH_HIP(alloc_scratch(r, base + v, true));
+      pg.sv[v] = r->vs[base + v].sv;
+      rg.view[v].sv = r->vs[base + v].sv;
+    }
+  }
+  g_last_raster_path = meshlets ? "meshlets" : "vertex-stage";
   rg.blocks_per_view = (uint32_t)div_up(div_up(r->F, rg.view[0].tpw * rg.view[0].groups), 4);
   ProfScope prof(ctx, SMESH_PROF_RASTER, st);
-  hipLaunchKernelGGL(k_project_vertices_group, dim3((uint32_t)div_up(r->V, 256)), dim3(256), 0, st, pg);
+  if (meshlets) {
+    CountGroup cg;
+    memset(&cg, 0, sizeof cg);
+    for (int v = 0; v < n; v++) cg.big_count[v] = pg.big_count[v];
+    cg.n = (uint32_t)n;
+    hipLaunchKernelGGL(k_reset_big_counts, dim3(1), dim3(64), 0, st, cg);
+  } else {
+    hipLaunchKernelGGL(k_project_vertices_group, dim3((uint32_t)div_up(r->V, 256)), dim3(256), 0, st, pg);
+  }
   SMESH_HIP(hipGetLastError());
   {
     rg.chunk = rg.blocks_per_view >= 64u ? kRasterXcdRun : 0u;
     const dim3 grid(rg.chunk ? 8u * xcd_slots(rg.blocks_per_view, rg.chunk) * (uint32_t)n : (uint32_t)n * rg.blocks_per_view);
-    switch (raster_mode(rg.view[0])) {     // (one mode per launch: render_group_into made the views agree)
+    if (meshlets) {
+      if (mode & 4) hipLaunchKernelGGL(k_raster_frag_group_ml<4>, grid, dim3(256), 0, st, rg);
+      else hipLaunchKernelGGL(k_raster_frag_group_ml<0>, grid, dim3(256), 0, st, rg);
+    } else
+    switch (mode) {     // (one mode per launch: render_group_into made the views agree)
       case 7:  hipLaunchKernelGGL(k_raster_frag_group<7>, grid, dim3(256), 0, st, rg); break;
       case 5:  hipLaunchKernelGGL(k_raster_frag_group<5>, grid, dim3(256), 0, st, rg); break;
       case 4:  hipLaunchKernelGGL(k_raster_frag_group<4>, grid, dim3(256), 0, st, rg); break;
@@ -2082,6 +2220,22 @@ int create_common(const float* vertices, uint64_t V, const int32_t* faces, uint6
   if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&r->vs[0].med_queue), (size_t)r->big_capacity * 4);
   if (e == hipSuccess && V) e = hipMemcpyAsync(r->verts, vertices, V * 12, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess && F) e = hipMemcpyAsync(r->faces, faces, F * 12, hipMemcpyHostToDevice, ctx->stream);
+  // the meshlet tables of these faces (the FINAL order: both constructors re-order before they come here)
+  MeshletTables mt;
+  std::vector<float> ml_pos;
+  if (e == hipSuccess && F && V && build_meshlets(faces, F, V, mt)) {
+    e = dev_malloc(reinterpret_cast<void**>(&r->ml.first), mt.first.size() * 4);
+    if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&r->ml.ids), std::max<uint64_t>(mt.ids.size() * 4, 16));
+    if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&r->ml.tris), mt.tris.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->ml.first, mt.first.data(), mt.first.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && !mt.ids.empty()) e = hipMemcpyAsync(r->ml.ids, mt.ids.data(), mt.ids.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(r->ml.tris, mt.tris.data(), mt.tris.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    ml_pos.resize(3 * mt.ids.size());
+    for (size_t k = 0; k < mt.ids.size(); k++)
+      for (int d = 0; d < 3; d++) ml_pos[3 * k + d] = vertices[3 * (uint64_t)mt.ids[k] + d];
+    if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&r->ml.pos), std::max<uint64_t>(ml_pos.size() * 4, 16));
+    if (e == hipSuccess && !ml_pos.empty()) e = hipMemcpyAsync(r->ml.pos, ml_pos.data(), ml_pos.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+  }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
     smesh_renderer_destroy(r);
@@ -2224,6 +2378,7 @@ extern "C" {
 
 const char* smesh_last_fuse_kernel(void) { return g_last_fuse_kernel; }
 const char* smesh_last_add_path(void) { return g_last_add_path; }
+const char* smesh_last_raster_path(void) { return g_last_raster_path; }
 
 int smesh_renderer_create_triangles(const float* vertices, uint64_t V, const int32_t* faces, uint64_t F, int device,
                                     smesh_renderer_t** out) {
@@ -2347,7 +2502,7 @@ int smesh_renderer_destroy(smesh_renderer_t* r) {
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->raster_stream);
   (void)hipStreamSynchronize(r->ctx->stream);
-  for (void* p : {(void*)r->prim_id, (void*)r->verts, (void*)r->faces, (void*)r->tex_res, (void*)r->tex_first})
+  for (void* p : {(void*)r->prim_id, (void*)r->verts, (void*)r->faces, (void*)r->tex_res, (void*)r->tex_first, (void*)r->ml.first, (void*)r->ml.ids, (void*)r->ml.tris, (void*)r->ml.pos})
     if (p) (void)dev_free(p);
   for (auto& sd : r->side)
     for (void* p : {(void*)sd.big_queue, (void*)sd.big_count, (void*)sd.frags, (void*)sd.kinds})
