@@ -142,6 +142,21 @@ EXT_SIGNATURES = {
                                             c_void_p, P(ctypes.c_int64), c_int, c_u64, c_u64]),
 }
 
+# Class-vector dtypes of include/smesh_half.h (SMESH_PROBS_*)
+PROBS_F32, PROBS_F16, PROBS_BF16 = 0, 1, 2
+PROBS_NAMES = {PROBS_F32: "float32", PROBS_F16: "float16", PROBS_BF16: "bfloat16"}
+
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_half.h: float16 / bfloat16 class-vector images,
+# product-only like the label entry points
+HALF_SIGNATURES = {
+    "smesh_fuse_view_probs16": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_void_p, c_int, c_void_p, c_int]),
+    "smesh_fuse_views_probs16": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, P(c_void_p), c_int, P(c_void_p), c_int]),
+    "smesh_aggregator_add_probs16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                             c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                             c_void_p, P(ctypes.c_int64), c_int, c_u64, c_u64]),
+    "smesh_narrow_probs": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_int, c_int]),
+}
+
 # name -> (restype, argtypes); one entry per symbol declared in include/smesh_vertices.h: the per-vertex results, product-only like
 # the label entry points (a table of its own: tests/test_labels_host.py pins EXT_SIGNATURES to the symbols of smesh_labels.h)
 VERTEX_SIGNATURES = {
@@ -311,7 +326,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -194,6 +194,7 @@ struct RenderedView {
   const uint8_t* kinds = nullptr;   // texel renderers: TriFrag::kind of every triangle again, a byte each (RasterArgs::kinds)
   bool fine = false;            // bounded on the host (raster.hip box_extent_bound <= 48 pixels): a finely tessellated mesh seen from outside -- few or no queued triangles
   const void* labels = nullptr; // label views (fusion_labels.hip): the dense uint8 / uint16 label plane [W][H] that stands in for `probs`
+  const void* probs16 = nullptr;   // 16-bit class-vector views (fusion_half.hip): the float16 / bfloat16 image [W][H][C] that stands in for `probs` (strides: ps0, ps1)
 };
 
 // Medium triangles: a bounding box over 8 x 8 pixels of at most kMidBox pixels (16 x 16: beyond that a whole wave per triangle --

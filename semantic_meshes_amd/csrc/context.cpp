@@ -1,6 +1,7 @@
 // context.cpp -- device contexts, error strings, memory helpers and the timing hooks of the C ABI.
 #include "common.hpp"
 #include "labels_scratch.hpp"
+#include "half_scratch.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -323,6 +324,7 @@ void Scratch::release() {
 using namespace smesh;
 
 void smesh_last_fuse_instance(int* slot, int* views);   // fusion.hip: the calling thread's last triangle-order launch
+int smesh_last_fuse_probs_dtype();                      // raster.hip: SMESH_PROBS_* of the class vectors the calling thread's last fusion read
 
 extern "C" {
 
@@ -348,6 +350,9 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "raster_meshlets")) { *value = opt_raster_meshlets() ? 1 : 0; return SMESH_OK; }
   // read-only: up to this class count k_fuse_tri_labels keeps a wave's rows in LDS, beyond it read-modify-writes them in global memory
   if (!strcmp(name, "labels_lds_max_classes")) { *value = (int64_t)kLabelsLdsMaxC; return SMESH_OK; }
+  // read-only (smesh_half.h): the largest class count k_fuse_tri_h16 serves; the dtype of the class vectors the last fusion read
+  if (!strcmp(name, "half_max_classes")) { *value = (int64_t)kHalfMaxClasses; return SMESH_OK; }
+  if (!strcmp(name, "last_fuse_probs_dtype")) { *value = (int64_t)smesh_last_fuse_probs_dtype(); return SMESH_OK; }
   // read-only: up to this class count k_confusion keeps a workgroup's histogram in LDS, beyond it adds straight into global memory
   if (!strcmp(name, "confusion_lds_max_classes")) { *value = (int64_t)kConfusionLdsMaxC; return SMESH_OK; }
   if (!strcmp(name, "confusion_wave_aggregate")) { *value = opt_confusion_wave_aggregate() ? 1 : 0; return SMESH_OK; }

@@ -28,6 +28,7 @@
 //     ONE float atomic each: 19 consecutive lanes cover one 128-byte accumulator row = one request.
 #include "common.hpp"
 #include "labels_scratch.hpp"
+#include "half_scratch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -2143,6 +2144,7 @@ struct smesh_aggregator {
   Scratch out_tmp;                       // get(): normalised result before the D2H copy
   ImageRecords rec;                      // add() on an image the library did not render: per-primitive records (image_records.hip)
   ImageRecords rec_many[7];              // add_many(): the record sets of the further images of a group of up to eight (rec is the first)
+  HalfScratch half;                      // add_probs16 / fuse_view(s)_probs16 (fusion_half.hip): staged 16-bit images and weights, the widened float32 image
   LabelScratch labels;                   // add_labels / fuse_view(s)_labels (fusion_labels.hip): staged and narrowed label planes, one-hot expansion
   // Exchange of row ranges beside the fusion (smesh_allreduce_rows, comm.cpp): ev_part marks the main stream where the range became
   // final, ev_xchg the exchange stream behind the range's collective; xchg_pending: the main stream has not yet waited for ev_xchg.
@@ -2761,6 +2763,7 @@ int smesh_aggregator_acc(smesh_aggregator* a, float** acc, uint64_t* num_floats,
 uint32_t smesh_aggregator_classes(smesh_aggregator* a) { return a->C; }
 uint64_t smesh_aggregator_primitives(smesh_aggregator* a) { return a->P; }
 LabelScratch& smesh_aggregator_label_scratch(smesh_aggregator* a) { return a->labels; }
+HalfScratch& smesh_aggregator_half_scratch(smesh_aggregator* a) { return a->half; }
 // What the label kernels (fusion_labels.hip) update and with which weights; every out pointer may be null.
 void smesh_aggregator_label_target(smesh_aggregator* a, float** acc, uint64_t* P, uint32_t* C, int* kind, float* iew) {
   if (acc) *acc = a->acc;
@@ -2913,6 +2916,7 @@ int smesh_aggregator_destroy(smesh_aggregator_t* a) {
   a->rec.release();
   for (auto& r : a->rec_many) r.release();
   a->labels.release();
+  a->half.release();
   delete a;
   return SMESH_OK;
 }

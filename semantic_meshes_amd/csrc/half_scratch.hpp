@@ -1,0 +1,30 @@
+// half_scratch.hpp -- what the 16-bit class-vector entry points (fusion_half.hip, include/smesh_half.h) share with the rest of the
+// library: the aggregator-owned device scratch (allocated on first use, released by smesh_aggregator_destroy, like LabelScratch)
+// and how a view's dtype rides through raster.hip's view-batch driver.
+#pragma once
+
+#include <mutex>
+
+#include "common.hpp"
+
+namespace smesh {
+
+// Largest class count k_fuse_tri_h16 serves: run-time class counts in 8 / 16 .. 48 register slots, as k_fuse_tri's run-time-C
+// instances.  Read-only option "half_max_classes" (smesh_get_option).
+constexpr uint32_t kHalfMaxClasses = 48;
+
+// raster.hip's drivers carry one int per call that says what the `probs` pointers are: 0 = float32 class vectors, 1 / 2 = label
+// planes of that many bytes per pixel, kHalfMode | SMESH_PROBS_F16 / _BF16 = 16-bit class vectors.
+constexpr int kHalfMode = 0x10;
+inline int half_dtype_of(int mode) { return (mode & kHalfMode) ? (mode & 0xF) : 0; }
+
+// Staged host images (16 bits per element) and staged weights of up to eight views, and the widened float32 image of the routes
+// k_fuse_tri_h16 does not serve.  Everything that writes or reads them is ordered on the context's main stream.  `mu` is held for a
+// whole entry point of smesh_half.h: it is taken before any other lock of the library, and by those entry points only.
+struct HalfScratch {
+  std::mutex mu;
+  Scratch stage, w, wide;
+  void release() { stage.release(); w.release(); wide.release(); }
+};
+
+}  // namespace smesh

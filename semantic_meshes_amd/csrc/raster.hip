@@ -20,6 +20,7 @@
 // z resolves to the lower id, so the result does not depend on the order triangles are processed in.
 #include "common.hpp"
 #include "meshlets.hpp"
+#include "half_scratch.hpp"
 #include "../../include/smesh_meshlets.h"
 
 #include <algorithm>
@@ -66,6 +67,12 @@ Scratch& smesh_aggregator_stage_w(smesh_aggregator* a);
 bool smesh_labels_native(smesh_aggregator* a, uint64_t F, uint64_t N);
 int smesh_labels_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int label_bytes);
 int smesh_labels_expand(smesh_aggregator* a, const void* plane, int label_bytes, uint64_t N, const float** probs);
+// fusion_half.hip: 16-bit class-vector views (include/smesh_half.h)
+bool smesh_half_native(smesh_aggregator* a, uint64_t F);
+bool smesh_half_takes_strides(int64_t ps0, int64_t ps1);
+int smesh_half_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int probs_dtype);
+int smesh_half_widen(smesh_aggregator* a, const void* probs, int probs_dtype, const int64_t s[3], uint64_t W, uint64_t H, const float** out,
+                     int slot = 0, size_t slot_bytes = 0, int nslots = 1);
 
 namespace {
 
@@ -2310,7 +2317,10 @@ static bool spatial_order(const float* v, uint64_t V, const int32_t* f, uint64_t
 
 static thread_local const char* g_last_fuse_kernel = "none";
 static thread_local const char* g_last_add_path = "none";   // "render-records" (the rasteriser's per-triangle records), or what add_device reports
-void smesh_note_fuse(const char* kernel, const char* path) { g_last_fuse_kernel = kernel; g_last_add_path = path; }
+static thread_local int g_last_fuse_probs_dtype = 0;        // SMESH_PROBS_* of the class vectors the last fusion READ (smesh_half.h)
+void smesh_note_fuse(const char* kernel, const char* path) { g_last_fuse_kernel = kernel; g_last_add_path = path; g_last_fuse_probs_dtype = 0; }
+int smesh_last_fuse_probs_dtype() { return g_last_fuse_probs_dtype; }
+static void note_fuse_half(int probs_dtype) { smesh_note_fuse("k_fuse_tri_h16", "render-records"); g_last_fuse_probs_dtype = probs_dtype; }
 
 // Do label views of this renderer into this aggregator take k_fuse_tri_labels (fusion_labels.hip)?  Triangle primitives in the caller's
 // face order (the kernel knows no prim_id table), Sum / Summax.  Everything else: labels expanded on the device, class-vector path.
@@ -2324,16 +2334,40 @@ static bool labels_native(smesh_renderer* r, smesh_aggregator* a, uint64_t N) {
 // for itself) but level 1: one decision per raster launch, all planes as soon as one view has queued triangles or flagged masks.
 constexpr int kLabelsPlaneLevel = 1;
 
+// Do 16-bit class-vector views of this renderer into this aggregator take k_fuse_tri_h16 (fusion_half.hip)?  Triangle primitives in the
+// caller's face order, Sum / Summax, at most kHalfMaxClasses classes.  Everything else: the image widened on the device, float32 path.
+static bool half_native(smesh_renderer* r, smesh_aggregator* a) { return !r->texels && !r->prim_id && smesh_half_native(a, r->F); }
+// Does the kernel that follows the raster launch of a view in this mode (fuse_rendered's `label_bytes`) read index planes the way
+// k_fuse_tri_labels does?  The tail waves of k_fuse_tri_h16 are that kernel's: they SCAN the plane of every view of the launch for a
+// queued triangle, so its raster launches take kLabelsPlaneLevel as well (no cheaper level is safe: there is no by-mask path).
+static bool scans_all_planes(smesh_renderer* r, smesh_aggregator* a, int label_bytes, uint64_t N) {
+  if (half_dtype_of(label_bytes)) return half_native(r, a);
+  return label_bytes && labels_native(r, a, N);
+}
+
 // The fusion half of smesh_fuse_view / smesh_aggregator_add_rendered: `d_idx` is the index plane of the render
 // whose per-triangle records sit in r->side[slot].
-// (`label_bytes` != 0: `probs` is no class-vector image but a dense label plane of that many bytes per pixel in DEVICE memory)
+// (`label_bytes` 1 / 2: `probs` is no class-vector image but a dense label plane of that many bytes per pixel in DEVICE memory;
+// kHalfMode | dtype: a 16-bit class-vector image in DEVICE memory, class stride 1 -- half_scratch.hpp)
 static int fuse_rendered(smesh_renderer* r, smesh_aggregator* a, int slot, const uint32_t* d_idx, const float* probs,
                          const float* weights, int memkind, uint64_t W, uint64_t H, int64_t ps0 = 0, int64_t ps1 = 0, int label_bytes = 0) {
   DeviceCtx* ctx = r->ctx;
   const uint64_t N = W * H;
   const float* d_probs = probs;
   const float* d_w = weights;
-  if (label_bytes) {
+  if (const int dt16 = half_dtype_of(label_bytes)) {
+    if (half_native(r, a)) {
+      RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H, ps0, ps1, true};
+      rv.probs16 = probs;
+      SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, dt16));
+      note_fuse_half(dt16);
+      return SMESH_OK;
+    }
+    const int64_t C = (int64_t)smesh_aggregator_classes(a);
+    const int64_t s[3] = {(ps0 || ps1) ? ps0 : (int64_t)H * C, (ps0 || ps1) ? ps1 : C, 1};
+    SMESH_TRY(smesh_half_widen(a, probs, dt16, s, W, H, &d_probs));
+    ps0 = ps1 = 0;
+  } else if (label_bytes) {
     if (labels_native(r, a, N)) {
       RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H, 0, 0, true};
       rv.labels = probs;
@@ -2641,7 +2675,8 @@ static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smes
   r->last_idx[slot] = nullptr; r->rec_valid[slot] = false;   // the records of a render_device() on this side are being overwritten
   // (the fusion only consumes the index plane -- and the triangle-order kernels not even that, where the view has no queued triangles)
   // (a label view: k_fuse_tri_labels follows the raster launch, or -- labels expanded -- the class-vector kernels as ever)
-  const int tri_path = (label_bytes && labels_native(r, a, N)) ? kLabelsPlaneLevel : plane_optional_level(r, a);
+  // (16-bit class vectors: k_fuse_tri_h16 follows and takes the label kernel's level, see scans_all_planes)
+  const int tri_path = scans_all_planes(r, a, label_bytes, N) ? kLabelsPlaneLevel : plane_optional_level(r, a);
   SMESH_TRY(render_into(r, cam, d_idx, /*d_depth=*/nullptr, ctx->stream, slot, tri_path));
   SMESH_TRY(fuse_rendered(r, a, slot, d_idx, probs, weights, memkind, W, H, 0, 0, label_bytes));
   r->fused_seq++;
@@ -2677,6 +2712,7 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && !r->texels && r->F != 0 && smesh_aggregator_can_fuse_triangles(a, r->F) &&
                smesh_aggregator_can_fuse_pair(a);
     if (label_bytes) {   // k_fuse_tri_labels follows every raster launch of this call: any class count, up to eight views per launch
+      // (or k_fuse_tri_h16, whose tail waves scan the index planes as that kernel's do: the same level, see scans_all_planes)
       tri_path = kLabelsPlaneLevel;
       pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0;
     }
@@ -2791,14 +2827,17 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
                                weights ? weights[k] : nullptr, cams[k].width, cams[k].height, 0, 0, true};
           rv[v].no_big = no_big_possible(r, &cams[k]);
           rv[v].fine = box_extent_bound(r->bounds, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
-          if (label_bytes) { rv[v].labels = probs[k]; rv[v].probs = nullptr; }
+          if (half_dtype_of(label_bytes)) { rv[v].probs16 = probs[k]; rv[v].probs = nullptr; }
+          else if (label_bytes) { rv[v].labels = probs[k]; rv[v].probs = nullptr; }
         }
-        if (label_bytes) SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, label_bytes));
+        if (half_dtype_of(label_bytes)) SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, rv, nv, half_dtype_of(label_bytes)));
+        else if (label_bytes) SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, label_bytes));
         else SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv));
         j += nv;
       }
     }
-    if (pairable) smesh_note_fuse(label_bytes ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
+    if (pairable && half_dtype_of(label_bytes)) note_fuse_half(half_dtype_of(label_bytes));
+    else if (pairable) smesh_note_fuse(label_bytes ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
     if (grouped && group_pipeline) SMESH_HIP(hipEventRecord(r->ev_bank_consumed[base / kMaxGroup], ctx->stream));
     r->fused_seq += (uint64_t)gn;
     i += (uint64_t)gn;
@@ -2829,6 +2868,68 @@ int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, con
   const float* const* p = reinterpret_cast<const float* const*>(planes);
   if (native) return fuse_views_impl(r, a, cams, n, p, weights, SMESH_MEM_DEVICE, label_bytes);
   for (uint64_t i = 0; i < n; i++) SMESH_TRY(fuse_view_impl(r, a, &cams[i], p[i], weights ? weights[i] : nullptr, SMESH_MEM_DEVICE, label_bytes));
+  return SMESH_OK;
+}
+
+// ---- 16-bit class-vector views (include/smesh_half.h; the entry points are fusion_half.hip's) ------------------------------------------
+// smesh_fuse_views for `n` views whose dense (W,H,C) images of `probs_dtype` and weights are in DEVICE memory.  Where k_fuse_tri_h16
+// serves the renderer and the aggregator: the group pipeline and the eight-view grouping of smesh_fuse_views.  Else group by group:
+// up to kMaxGroup images widened on the device into as many scratch slots, then smesh_fuse_views' own path for that group -- its
+// multi-view launches and shared rasteriser launches, unchanged.
+int smesh_renderer_fuse_views_half(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
+                                   const float* const* weights, int probs_dtype) {
+  bool native;
+  {
+    std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+    native = half_native(r, a);
+  }
+  const float* const* p = reinterpret_cast<const float* const*>(probs);
+  if (native) return fuse_views_impl(r, a, cams, n, p, weights, SMESH_MEM_DEVICE, kHalfMode | probs_dtype);
+  DeviceCtx* ctx = r->ctx;
+  const uint64_t C = smesh_aggregator_classes(a);
+  for (uint64_t i = 0; i < n; i += (uint64_t)kMaxGroup) {
+    const int m = (int)std::min<uint64_t>((uint64_t)kMaxGroup, n - i);
+    size_t slot_bytes = 256;
+    for (int v = 0; v < m; v++) slot_bytes = std::max<size_t>(slot_bytes, (cams[i + v].width * cams[i + v].height * C * 4 + 255) & ~(size_t)255);
+    const float* wide[kMaxGroup];
+    {
+      // (the widening kernels go to the main stream, behind the previous group's fusion launches, which read the same slots)
+      std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+      SMESH_HIP(hipSetDevice(ctx->device));
+      for (int v = 0; v < m; v++) {
+        const uint64_t W = cams[i + v].width, H = cams[i + v].height;
+        const int64_t s[3] = {(int64_t)(H * C), (int64_t)C, 1};
+        SMESH_TRY(smesh_half_widen(a, probs[i + v], probs_dtype, s, W, H, &wide[v], v, slot_bytes, m));
+      }
+    }
+    SMESH_TRY(fuse_views_impl(r, a, &cams[i], (uint64_t)m, wide, weights ? &weights[i] : nullptr, SMESH_MEM_DEVICE, 0));
+  }
+  return SMESH_OK;
+}
+
+// smesh_aggregator_add_rendered for a 16-bit image in DEVICE memory (x / y element strides ps0 / ps1, class stride 1): *done = 1 if
+// `idx_dev` is the untouched output of one of r's latest smesh_renderer_render_device() calls and the view was fused from that
+// render's records (k_fuse_tri_h16, or -- the image widened -- the triangle / texel kernels of the float32 path); *done = 0: nothing
+// happened.
+int smesh_renderer_add_rendered_half(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* probs, int probs_dtype,
+                                     int64_t ps0, int64_t ps1, const float* weights, uint64_t W, uint64_t H, int* done) {
+  *done = 0;
+  DeviceCtx* ctx = r->ctx;
+  if (smesh_aggregator_ctx(a) != ctx || W == 0 || H == 0) return SMESH_OK;
+  std::lock_guard<std::mutex> g(r->mu);
+  std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  SMESH_TRY(smesh_aggregator_join_exchange(a));
+  int side = -1;
+  for (int sd = 0; sd < kRecordSides; sd++)
+    if (idx_dev == r->last_idx[sd] && W == r->last_W[sd] && H == r->last_H[sd]) side = sd;
+  if (side < 0 || !((!r->texels && smesh_aggregator_can_fuse_triangles(a, r->F)) || (r->texels && smesh_aggregator_can_fuse_texels(a, r->num_primitives))))
+    return SMESH_OK;
+  SMESH_HIP(hipSetDevice(ctx->device));
+  const int64_t C = (int64_t)smesh_aggregator_classes(a);
+  if (ps0 == (int64_t)H * C && ps1 == C) ps0 = ps1 = 0;   // (the dense image)
+  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(probs), weights, SMESH_MEM_DEVICE, W, H, ps0, ps1, kHalfMode | probs_dtype));
+  *done = 1;
   return SMESH_OK;
 }
 

@@ -33,6 +33,7 @@ class DeviceArray:
         self._on_release = on_release  # returns the buffer to its pool
         self._rendered_by = None       # render(): the renderer whose latest output this is (MeshAggregator.add fast path)
         self._exported = False         # handed to another framework: the contents may have been changed behind our back
+        self.bfloat16 = False          # a uint16 array whose elements are bfloat16 bit patterns (fusion.narrow_probs; numpy has no such dtype)
 
     unrun = False                      # (render.py: a plane of a render() that has not been rasterised yet says True)
 
@@ -95,7 +96,7 @@ class DeviceArray:
         self._seal()
         self._exported = True
         _lib.synchronize(self.device)
-        return dlpack.to_capsule(self.ptr, self.shape, self.strides, self.dtype, dlpack.kDLROCM, self.device, self)
+        return dlpack.to_capsule(self.ptr, self.shape, self.strides, self.dtype, dlpack.kDLROCM, self.device, self, bfloat16=self.bfloat16)
 
     def capsule(self):
         """A `"dltensor"` PyCapsule over the buffer -- the object the reference's render() returns
@@ -104,7 +105,7 @@ class DeviceArray:
         from . import dlpack
         self._seal()                       # whoever consumes the capsule may write to the plane later
         _lib.synchronize(self.device)      # ... and reads it on its own stream
-        return dlpack.to_capsule(self.ptr, self.shape, self.strides, self.dtype, dlpack.kDLROCM, self.device, self)
+        return dlpack.to_capsule(self.ptr, self.shape, self.strides, self.dtype, dlpack.kDLROCM, self.device, self, bfloat16=self.bfloat16)
 
     def transpose(self, *axes):
         """Stride permutation without a copy (callers transpose (H,W,C) network output to (W,H,C))."""
@@ -112,8 +113,10 @@ class DeviceArray:
             axes = tuple(axes[0])
         if not axes:
             axes = tuple(reversed(range(self.ndim)))
-        return DeviceArray(self.ptr, [self.shape[a] for a in axes], self.dtype, self.device,
-                           [self.strides[a] for a in axes], owner=self)
+        out = DeviceArray(self.ptr, [self.shape[a] for a in axes], self.dtype, self.device,
+                          [self.strides[a] for a in axes], owner=self)
+        out.bfloat16 = self.bfloat16
+        return out
 
     @property
     def T(self):
@@ -300,10 +303,15 @@ def describe(obj, want_ndim, what, device=None, streams=None):
     Device memory that does not come from this library is ordered after its producer's stream (`device` = the GPU of
     the handle the argument is for); the producer streams are appended to `streams` for release_to().
     """
+    cai = None
+    if not isinstance(obj, DeviceArray):
+        try:      # (torch raises TypeError here for a bfloat16 tensor, which the protocol cannot describe: such a tensor comes by DLPack)
+            cai = getattr(obj, "__cuda_array_interface__", None)
+        except (TypeError, RuntimeError):
+            cai = None
     if isinstance(obj, DeviceArray):
         shape, dtype, strides, ptr, mem, keep = obj.shape, obj.dtype, obj.strides, obj.ptr, _lib.MEM_DEVICE, obj
-    elif hasattr(obj, "__cuda_array_interface__"):
-        cai = obj.__cuda_array_interface__
+    elif cai is not None:
         if device is not None:   # (None: layout bookkeeping only -- every entry point of the package passes its handle's GPU)
             st = _order_after_producer(obj, cai, device)
             if streams is not None:

@@ -12,6 +12,7 @@ import numpy as np
 kDLCPU, kDLCUDA, kDLCUDAHost, kDLROCM, kDLROCMHost = 1, 2, 3, 10, 11
 _CODES = {"i": 0, "u": 1, "f": 2}
 _KINDS = {0: "i", 1: "u", 2: "f"}
+kDLBfloat = 4      # (numpy has no bfloat16: such a tensor is imported as uint16 bit patterns with `.bfloat16` set)
 
 
 class DLDevice(ctypes.Structure):
@@ -65,9 +66,9 @@ def _capsule_destructor(capsule):
         _live.pop(addr, None)
 
 
-def to_capsule(ptr, shape, strides_elems, dtype, device_type, device_id, owner):
+def to_capsule(ptr, shape, strides_elems, dtype, device_type, device_id, owner, bfloat16=False):
     """PyCapsule named "dltensor" over a DLManagedTensor describing the buffer; `owner` is kept alive
-    until the consumer calls the deleter."""
+    until the consumer calls the deleter.  `bfloat16`: the uint16 elements are bfloat16 bit patterns (exported as kDLBfloat)."""
     dtype = np.dtype(dtype)
     nd = len(shape)
     shp = (ctypes.c_int64 * nd)(*shape)
@@ -76,7 +77,9 @@ def to_capsule(ptr, shape, strides_elems, dtype, device_type, device_id, owner):
     mt.dl_tensor.data = ctypes.c_void_p(ptr)
     mt.dl_tensor.device = DLDevice(device_type, device_id)
     mt.dl_tensor.ndim = nd
-    mt.dl_tensor.dtype = DLDataType(_CODES[dtype.kind], dtype.itemsize * 8, 1)
+    if bfloat16 and dtype != np.uint16:
+        raise ValueError("bfloat16 bit patterns are held in uint16 arrays")
+    mt.dl_tensor.dtype = DLDataType(kDLBfloat if bfloat16 else _CODES[dtype.kind], dtype.itemsize * 8, 1)
     mt.dl_tensor.shape = shp
     mt.dl_tensor.strides = std
     mt.dl_tensor.byte_offset = 0
@@ -99,10 +102,11 @@ class Imported:
         _api.PyCapsule_SetName(capsule, b"used_dltensor")
         self._capsule = capsule
         t = self._mt.contents.dl_tensor
-        if t.dtype.lanes != 1 or t.dtype.code not in _KINDS:
+        self.bfloat16 = t.dtype.lanes == 1 and t.dtype.code == kDLBfloat and t.dtype.bits == 16
+        if t.dtype.lanes != 1 or (t.dtype.code not in _KINDS and not self.bfloat16):
             self.close()
             raise ValueError("unsupported DLPack dtype")
-        self.dtype = np.dtype("%s%d" % (_KINDS[t.dtype.code], t.dtype.bits // 8))
+        self.dtype = np.dtype(np.uint16) if self.bfloat16 else np.dtype("%s%d" % (_KINDS[t.dtype.code], t.dtype.bits // 8))
         self.shape = tuple(int(t.shape[i]) for i in range(t.ndim))
         if t.strides:
             self.strides = tuple(int(t.strides[i]) for i in range(t.ndim))

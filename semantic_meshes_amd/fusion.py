@@ -45,6 +45,80 @@ def narrow_labels(labels, classes):
     return np.ascontiguousarray(np.where(u < u.dtype.type(limit), u, u.dtype.type(code)).astype(out, copy=False))
 
 
+def probs_code(dtype, keep=None, probs_dtype=None, what="probs image"):
+    """The SMESH_PROBS_* code (include/smesh_half.h) of a class-vector image of numpy dtype `dtype`, or None for a dtype the fusion
+    does not read.  float16 is recognised from the dtype.  numpy has no bfloat16: it is a dtype NAMED bfloat16 (ml_dtypes) where one
+    is installed, a uint16 array that says so itself (`keep.bfloat16`: a DLPack import of kDLBfloat/16, `narrow_probs`' result), or a
+    uint16 array with `probs_dtype="bfloat16"` -- its bits are bfloat16.  `probs_dtype` None: infer."""
+    dtype = np.dtype(dtype)
+    if probs_dtype is not None:
+        name = probs_dtype if isinstance(probs_dtype, str) else np.dtype(probs_dtype).name
+        if name == "bfloat16":
+            if dtype == np.uint16 or (dtype.name == "bfloat16" and dtype.itemsize == 2):
+                return _lib.PROBS_BF16
+            raise ValueError('%s: probs_dtype="bfloat16" needs a uint16 array (its bits are bfloat16), got %s' % (what, dtype))
+        if name not in ("float16", "float32"):
+            raise ValueError("probs_dtype must be None, 'float32', 'float16' or 'bfloat16', got %r" % (probs_dtype,))
+        if dtype.name != name and not (name == "float32" and dtype.kind == "f" and dtype.itemsize > 4):
+            raise ValueError("%s: probs_dtype=%r but the array is %s" % (what, name, dtype))
+    if dtype == np.float32:
+        return _lib.PROBS_F32
+    if dtype == np.float16:
+        return _lib.PROBS_F16
+    if (dtype.name == "bfloat16" and dtype.itemsize == 2) or (dtype == np.uint16 and getattr(keep, "bfloat16", False)):
+        return _lib.PROBS_BF16
+    return None
+
+
+def _peek_code(obj, probs_dtype):
+    """`probs_code` of an image without touching it (no copy, no stream ordering, no capsule consumed): None where that cannot be
+    told from the outside."""
+    dt = None
+    if isinstance(obj, (np.ndarray, DeviceArray)):
+        dt = obj.dtype
+    else:
+        try:
+            cai = getattr(obj, "__cuda_array_interface__", None)
+        except (TypeError, RuntimeError):
+            cai = None
+        if cai is not None:
+            dt = np.dtype(cai["typestr"])
+    if dt is None:
+        return None
+    return probs_code(dt, obj, probs_dtype)
+
+
+def narrow_probs(array, dtype, device=0):
+    """float32 class vectors rounded to float16 or bfloat16 ON THE DEVICE (`smesh_narrow_probs`: round to nearest even, overflow to
+    inf, subnormals kept): a dense `DeviceArray` of the same shape in a fresh allocation -- float16, or uint16 bit patterns with
+    `.bfloat16` set.  `array`: a float32 numpy array or dense float32 device array; `dtype`: "float16" / np.float16 / "bfloat16".
+    For tests, benchmarks and users whose network ran in float32."""
+    from .device import DeviceBuffer, to_device
+    name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+    if name not in ("float16", "bfloat16"):
+        raise ValueError("narrow_probs: dtype must be float16 or bfloat16, got %r" % (dtype,))
+    if isinstance(array, np.ndarray) or not (isinstance(array, DeviceArray) or hasattr(array, "__cuda_array_interface__")):
+        array = to_device(np.ascontiguousarray(array, dtype=np.float32), device)
+    streams = []
+    ptr, mem, shape, dt, strides, keep = describe(array, len(array.shape), "narrow_probs input", getattr(array, "device", device), streams)
+    dev = int(getattr(array, "device", device)) if isinstance(array, DeviceArray) else int(device)
+    dense = DeviceArray(0, shape, np.float32, dev).strides
+    if dt != np.float32 or mem != _lib.MEM_DEVICE or tuple(strides) != tuple(dense):
+        raise ValueError("narrow_probs needs a dense float32 array")
+    n = 1
+    for s in shape:
+        n *= int(s)
+    out = DeviceBuffer(max(n * 2, 2), dev).view(shape, np.float16 if name == "float16" else np.uint16)
+    out.bfloat16 = name == "bfloat16"
+    if n:
+        _lib.check(_lib.lib().smesh_narrow_probs(ctypes.c_void_p(ptr), ctypes.c_void_p(out.ptr), n,
+                                                 _lib.PROBS_F16 if name == "float16" else _lib.PROBS_BF16, dev, _lib.MEM_DEVICE))
+    release_to(dev, streams)
+    if not isinstance(keep, DeviceArray):
+        _lib.synchronize(dev)      # (a foreign input may be freed by its owner as soon as we return)
+    return out
+
+
 GROUP_VIEWS = 8                                                     # views per deferred group (= the library's views per launch)
 DEFER_VIEWS = os.environ.get("SMESH_DEFER_VIEWS", "1") != "0"       # default of MeshAggregator.defer
 
@@ -81,7 +155,7 @@ class _MeshAggregator:
         # share their rasteriser launches and each accumulator row makes one round trip for all of them: the batch entry point's
         # throughput behind the reference's per-view loop (colorize_cityscapes_mesh.py:54-67).  Same sums in the same order.  The group
         # is handed over on the eighth view, at anything else that uses the aggregator (`_h`), at `flush()`, at `_lib.synchronize()`.
-        self._pending = []      # [(renderer, CameraPOD, W, H, probs array -- or label plane --, weights array or None, is a label view)]
+        self._pending = []      # [(renderer, CameraPOD, W, H, probs array -- or label plane --, weights array or None, is a label view, SMESH_PROBS_* of a probs array)]
         self._pending_lock = threading.RLock()
         self.defer = DEFER_VIEWS
         with _aggregators_lock:
@@ -111,22 +185,32 @@ class _MeshAggregator:
                 _lib.check(_lib.lib().smesh_fuse_views_labels(renderer._h, self._handle, pods, n, pptr, _lib.LBL_CODES[todo[0][4].dtype.name],
                                                               None, wptr, _lib.MEM_DEVICE))
                 return
+            if todo[0][7] != _lib.PROBS_F32:     # a group of float16 / bfloat16 images (one dtype: _defer)
+                _lib.check(_lib.lib().smesh_fuse_views_probs16(renderer._h, self._handle, pods, n, pptr, todo[0][7], wptr, _lib.MEM_DEVICE))
+                return
             _lib.check(_lib.lib().smesh_fuse_views(renderer._h, self._handle, pods, n, pptr, wptr, _lib.MEM_DEVICE))
             # (the class vectors are this library's own arrays: freed behind its streams, no completion token needed)
 
-    def _deferrable(self, probs_image, weights_image, W, H):
+    def _deferrable(self, probs_image, weights_image, W, H, probs_dtype=None):
         """May a view with these inputs wait for its group?  Only with inputs nobody else can write to behind our back: this library's
-        own dense float32 device arrays that were never exported to another framework (anything else is consumed by the call itself,
-        in order: foreign device tensors may be re-used by their owner as soon as the call returns, host arrays likewise)."""
+        own dense float32 / float16 / bfloat16 device arrays that were never exported to another framework (anything else is consumed
+        by the call itself, in order: foreign device tensors may be re-used by their owner as soon as the call returns, host arrays
+        likewise).  Returns None, or the SMESH_PROBS_* code of the class vectors (0 is float32: test with `is not None`)."""
         if not self.defer:
-            return False
-        ok = (type(probs_image) is DeviceArray and not probs_image._exported and probs_image.device == self.device
-              and probs_image.dtype == np.float32 and probs_image.shape == (W, H, self.classes)
+            return None
+        if type(probs_image) is not DeviceArray:
+            return None
+        try:
+            code = probs_code(probs_image.dtype, probs_image, probs_dtype)
+        except ValueError:
+            return None       # (the call itself raises it)
+        ok = (code is not None and not probs_image._exported and probs_image.device == self.device
+              and probs_image.shape == (W, H, self.classes)
               and probs_image.strides == (H * self.classes, self.classes, 1))
         if ok and weights_image is not None:
             ok = (type(weights_image) is DeviceArray and not weights_image._exported and weights_image.device == self.device
                   and weights_image.dtype == np.float32 and weights_image.shape == (W, H) and weights_image.strides == (H, 1))
-        return ok
+        return code if ok else None
 
     def _deferrable_labels(self, label_image, weights_image, W, H):
         """`_deferrable` for a label view: this library's own dense uint8 / uint16 device plane, never exported."""
@@ -139,15 +223,16 @@ class _MeshAggregator:
                   and weights_image.dtype == np.float32 and weights_image.shape == (W, H) and weights_image.strides == (H, 1))
         return ok
 
-    def _defer(self, renderer, pod, W, H, probs_image, weights_image, labels=False):
+    def _defer(self, renderer, pod, W, H, probs_image, weights_image, labels=False, code=_lib.PROBS_F32):
         with self._pending_lock:
             if self._pending:
                 first = self._pending[0]
-                # one group = one renderer, one image size, weights for all views or for none, class vectors or labels (of one dtype)
+                # one group = one renderer, one image size, weights for all views or for none, class vectors (of one dtype) or labels
+                # (of one dtype)
                 if (first[0] is not renderer or (first[2], first[3]) != (W, H) or (first[5] is None) != (weights_image is None)
-                        or first[6] != labels or (labels and first[4].dtype != probs_image.dtype)):
+                        or first[6] != labels or first[7] != code or (labels and first[4].dtype != probs_image.dtype)):
                     self.flush()
-            self._pending.append((renderer, pod, W, H, probs_image, weights_image, labels))
+            self._pending.append((renderer, pod, W, H, probs_image, weights_image, labels, code))
             if len(self._pending) >= GROUP_VIEWS:
                 self.flush()
 
@@ -188,29 +273,37 @@ class _MeshAggregator:
             except Exception:
                 pass
 
-    def add(self, primitive_image, probs_image, weights_image=None):
-        """Fuse one view: `primitive_image` (W,H) of uint32/int32/uint64/int64, `probs_image` (W,H,C) float32,
-        optional `weights_image` (W,H) float32; host numpy or device arrays, any non-negative strides."""
+    def add(self, primitive_image, probs_image, weights_image=None, probs_dtype=None):
+        """Fuse one view: `primitive_image` (W,H) of uint32/int32/uint64/int64, `probs_image` (W,H,C) float32, float16 or bfloat16,
+        optional `weights_image` (W,H) float32; host numpy or device arrays, any non-negative strides.  A 16-bit image gives what
+        its exactly widened float32 copy gives, without that copy (include/smesh_half.h); `probs_dtype="bfloat16"` says that a
+        uint16 array holds bfloat16 bits (see `probs_code`), None infers the dtype from the array."""
         if type(primitive_image).__name__ == "PyCapsule":
             # render() in capsule mode (the reference's return type) handed straight back, as python/scripts/colorize_cityscapes_mesh.py:65-67 does
             from . import dlpack
             own = dlpack.own_capsule_owner(primitive_image)
             if own is not None:
                 primitive_image = own
-        if (getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
-                and self._deferrable(probs_image, weights_image, *primitive_image.shape)):
+        lazy = getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
+        dcode = self._deferrable(probs_image, weights_image, *primitive_image.shape, probs_dtype=probs_dtype) if lazy else None
+        if dcode is not None:
             # render()'s index plane handed straight back, not rasterised yet (render.py: _LazyPlane): nobody has looked at it, so
             # (camera, probs) joins the aggregator's group of deferred views and the plane is never produced
             pend = primitive_image._pending
             if pend.W and pend.H:
-                self._defer(pend.renderer, pend.pod, pend.W, pend.H, probs_image, weights_image)
+                self._defer(pend.renderer, pend.pod, pend.W, pend.H, probs_image, weights_image, code=dcode)
             return
         streams = []   # streams of other frameworks whose device arrays this call reads (ordered before and after, no host wait)
+        if isinstance(probs_image, np.ndarray):
+            probs_code(probs_image.dtype, probs_image, probs_dtype)      # (a refused probs_dtype leaves a lazy plane lazy)
         ip, imem, ishape, idt, istr, k0 = describe(primitive_image, 2, "primitive image", self.device, streams)
         pp, pmem, pshape, pdt, pstr, k1 = describe(probs_image, 3, "probs image", self.device, streams)
         if idt not in _IDX_CODES:
             raise ValueError("primitive image dtype must be one of uint32/int32/uint64/int64, got %s" % idt)
-        if pdt != np.float32:
+        code = probs_code(pdt, k1, probs_dtype)
+        if code in (_lib.PROBS_F16, _lib.PROBS_BF16):
+            pass      # (read as it is: smesh_aggregator_add_probs16 below)
+        elif pdt != np.float32:
             if pmem == _lib.MEM_HOST and pdt.kind == "f":
                 probs_image = np.asarray(probs_image, dtype=np.float32)
                 pp, pmem, pshape, pdt, pstr, k1 = describe(probs_image, 3, "probs image", self.device, streams)
@@ -235,6 +328,20 @@ class _MeshAggregator:
         if W == 0 or H == 0:
             return
         rb = getattr(primitive_image, "_rendered_by", None)
+        if code in (_lib.PROBS_F16, _lib.PROBS_BF16):
+            # float16 / bfloat16 class vectors: the untouched output of renderer.render() takes the 16-bit triangle-order kernel (the
+            # library re-checks that it is the latest render); everything else is widened on the device and takes add()'s path
+            if not (rb is not None and not primitive_image._exported and getattr(rb, "_h", None) is not None and rb._h.value
+                    and rb.device == self.device):
+                rb = None
+            _lib.check(_lib.lib().smesh_aggregator_add_probs16(
+                self._h, None if rb is None else rb._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
+                ctypes.c_void_p(pp), code, _c64(pstr), pmem,
+                None if wp is None else ctypes.c_void_p(wp), None if wstr is None else _c64(wstr), wmem, W, H))
+            release_to(self.device, streams)
+            self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if pmem == _lib.MEM_DEVICE else None,
+                        k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
+            return
         if (rb is not None and not primitive_image._exported and getattr(rb, "_h", None) is not None and rb._h.value
                 and idt == np.uint32 and tuple(istr) == (H, 1)):
             # the untouched output of renderer.render(): the reference's two-call loop (colorize_cityscapes_mesh.py:65-67)
@@ -405,7 +512,7 @@ class _MeshAggregator:
         if first[1] == _lib.MEM_DEVICE:
             self._hold([d[4] for d, _ in desc] + [dw[4] for _, dw in desc if dw is not None])
 
-    def add_many(self, primitive_images, probs_images, weights_images=None):
+    def add_many(self, primitive_images, probs_images, weights_images=None, probs_dtype=None):
         """`add()` for a batch of views, in order (new functionality; the reference's loop adds one image per call).  Same sums as
         the calls one by one -- per accumulator row the same float32 additions in the same order -- but device-resident dense
         uint32 / int32 index images with dense float32 device class vectors, all of one size, share their kernel launches in groups
@@ -416,6 +523,16 @@ class _MeshAggregator:
         if len(probs) != n or (wts is not None and len(wts) != n):
             raise ValueError("add_many needs one probs image (and one weights image) per primitive image")
         if n == 0:
+            return
+        codes = [_peek_code(p, probs_dtype) for p in probs]
+        known = [c for c in codes if c is not None]
+        if any(c != known[0] for c in known):
+            raise ValueError("add_many: all probs images must have one dtype (got %s)" % ", ".join(sorted({_lib.PROBS_NAMES[c] for c in known})))
+        if known and known[0] != _lib.PROBS_F32:
+            # float16 / bfloat16 class vectors: view by view through add(), where render() planes that have not been rasterised yet and
+            # this library's own device images gather in deferred groups of eight -- one fuse_views call per group
+            for i in range(n):
+                self.add(prims[i], probs[i], None if wts is None else wts[i], probs_dtype=probs_dtype)
             return
         streams, desc = [], []
         for i in range(n):
@@ -439,7 +556,7 @@ class _MeshAggregator:
             uniform = False      # (add() raises the reference's error for the image concerned)
         if not uniform or n < 2:
             for i in range(n):
-                self.add(prims[i], probs[i], None if wts is None else wts[i])
+                self.add(prims[i], probs[i], None if wts is None else wts[i], probs_dtype=probs_dtype)
             return
         W, H = ishape0
         if W == 0 or H == 0:
@@ -552,17 +669,21 @@ class _MeshAggregator:
         """`ModelAggregator::renderer()` (Mesh.h:124-129): snapshot of the fused annotations for image gathers."""
         return ModelRenderer(self)
 
-    def fuse_view(self, renderer, camera, probs_image, weights_image=None):
-        """render(camera) + add(indices, probs) in one call without the indices leaving the device."""
+    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None):
+        """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
+        float32, float16 or bfloat16 (see add())."""
         W, H = camera.resolution
-        if (W > 0 and H > 0 and W <= 65536 and H <= 65536 and W * H < 0x7FFFFFFF // 4 and renderer.device == self.device
-                and self._deferrable(probs_image, weights_image, W, H)):
-            self._defer(renderer, _lib.CameraPOD.from_buffer_copy(camera._pod), W, H, probs_image, weights_image)
+        dcode = None
+        if W > 0 and H > 0 and W <= 65536 and H <= 65536 and W * H < 0x7FFFFFFF // 4 and renderer.device == self.device:
+            dcode = self._deferrable(probs_image, weights_image, W, H, probs_dtype=probs_dtype)
+        if dcode is not None:
+            self._defer(renderer, _lib.CameraPOD.from_buffer_copy(camera._pod), W, H, probs_image, weights_image, code=dcode)
             return
         streams = []
         pp, pmem, pshape, pdt, pstr, k1 = describe(probs_image, 3, "probs image", self.device, streams)
-        if tuple(pshape) != (W, H, self.classes) or pdt != np.float32:
-            raise ValueError("probs image must be float32 (W,H,C) = %s" % ((W, H, self.classes),))
+        code = probs_code(pdt, k1, probs_dtype)
+        if tuple(pshape) != (W, H, self.classes) or code is None:
+            raise ValueError("probs image must be float32, float16 or bfloat16 (W,H,C) = %s" % ((W, H, self.classes),))
         if pstr != (H * self.classes, self.classes, 1):
             raise ValueError("fuse_view needs a contiguous (W,H,C) probs image")
         wp = None
@@ -571,26 +692,36 @@ class _MeshAggregator:
             if tuple(wshape) != (W, H) or wdt != np.float32 or wstr != (H, 1) or wmem != pmem:
                 raise ValueError("weights image must be contiguous float32 (W,H) in the same memory as probs")
             wp = ctypes.c_void_p(wp_)
-        _lib.check(_lib.lib().smesh_fuse_view(renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(pp), wp, pmem))
+        if code != _lib.PROBS_F32:
+            _lib.check(_lib.lib().smesh_fuse_view_probs16(renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(pp), code, wp, pmem))
+        else:
+            _lib.check(_lib.lib().smesh_fuse_view(renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(pp), wp, pmem))
         release_to(self.device, streams)
         if pmem == _lib.MEM_DEVICE:
             self._hold([k1, k2 if weights_image is not None else None])
 
-    def _marshal_views(self, cameras, probs_images, weights_images, what):
-        """ctypes arguments of a batch of views: (pods, n, probs pointers, weights pointers or None, memory kind, keep-alives, streams)."""
+    def _marshal_views(self, cameras, probs_images, weights_images, what, probs_dtype=None):
+        """ctypes arguments of a batch of views: (pods, n, probs pointers, weights pointers or None, memory kind, keep-alives, streams,
+        SMESH_PROBS_* code of the class vectors -- one dtype for the whole batch)."""
         cameras, probs_images = list(cameras), list(probs_images)
         n = len(cameras)
         if len(probs_images) != n or (weights_images is not None and len(weights_images) != n):
             raise ValueError("%s needs one probs image (and one weights image or None) per camera" % what)
         pods = (_lib.CameraPOD * max(n, 1))()
         pptr, wptr = (ctypes.c_void_p * max(n, 1))(), (ctypes.c_void_p * max(n, 1))()
-        keep, mem, streams = [], None, []
+        keep, mem, streams, code = [], None, [], None
         for i, cam in enumerate(cameras):
             W, H = cam.resolution
             pods[i] = cam._pod
             pp, pmem, pshape, pdt, pstr, k1 = describe(probs_images[i], 3, "probs image", self.device, streams)
-            if tuple(pshape) != (W, H, self.classes) or pdt != np.float32:
-                raise ValueError("probs image %d must be float32 (W,H,C) = %s" % (i, (W, H, self.classes)))
+            ci = probs_code(pdt, k1, probs_dtype, "probs image %d" % i)
+            if tuple(pshape) != (W, H, self.classes) or ci is None:
+                raise ValueError("probs image %d must be float32, float16 or bfloat16 (W,H,C) = %s" % (i, (W, H, self.classes)))
+            if code is None:
+                code = ci
+            if ci != code:
+                raise ValueError("%s: all probs images must have one dtype (image 0 is %s, image %d is %s)"
+                                 % (what, _lib.PROBS_NAMES[code], i, _lib.PROBS_NAMES[ci]))
             if pstr != (H * self.classes, self.classes, 1):
                 raise ValueError("%s needs contiguous (W,H,C) probs images" % what)
             if mem is None:
@@ -606,16 +737,21 @@ class _MeshAggregator:
                     raise ValueError("weights image %d must be contiguous float32 (W,H) in the same memory as probs" % i)
                 wptr[i] = wp_
                 keep.append(k2)
-        return pods, n, pptr, (None if weights_images is None else wptr), (mem if mem is not None else _lib.MEM_HOST), keep, streams
+        return (pods, n, pptr, (None if weights_images is None else wptr), (mem if mem is not None else _lib.MEM_HOST), keep, streams,
+                _lib.PROBS_F32 if code is None else code)
 
-    def fuse_views(self, renderer, cameras, probs_images, weights_images=None):
+    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
-        accumulator row is read and written once for all of them.  All images must live in the same memory (host or device)."""
-        pods, n, pptr, wptr, mem, keep, streams = self._marshal_views(cameras, probs_images, weights_images, "fuse_views")
+        accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
+        have one dtype: float32, float16 or bfloat16 (see add())."""
+        pods, n, pptr, wptr, mem, keep, streams, code = self._marshal_views(cameras, probs_images, weights_images, "fuse_views", probs_dtype)
         if n == 0:
             return
-        _lib.check(_lib.lib().smesh_fuse_views(renderer._h, self._h, pods, n, pptr, wptr, mem))
+        if code != _lib.PROBS_F32:
+            _lib.check(_lib.lib().smesh_fuse_views_probs16(renderer._h, self._h, pods, n, pptr, code, wptr, mem))
+        else:
+            _lib.check(_lib.lib().smesh_fuse_views(renderer._h, self._h, pods, n, pptr, wptr, mem))
         release_to(self.device, streams)
         if mem == _lib.MEM_DEVICE:
             self._hold(keep)
@@ -627,7 +763,9 @@ class _MeshAggregator:
         so a sharded job exchanges them (`Communicator.allreduce_rows`) while the next part is fused.  Same sums as `fuse_views`.
         Where rows are not in triangle order (texel renderers, re-ordered meshes, host images ...) part 0 is the whole job.
         Returns the list of (row_lo, row_hi)."""
-        pods, n, pptr, wptr, mem, keep, streams = self._marshal_views(cameras, probs_images, weights_images, "fuse_views_ranged")
+        pods, n, pptr, wptr, mem, keep, streams, code = self._marshal_views(cameras, probs_images, weights_images, "fuse_views_ranged")
+        if code != _lib.PROBS_F32:
+            raise ValueError("fuse_views_ranged needs float32 probs images")
         nparts = int(nparts)
         if n == 0 or nparts < 1:
             raise ValueError("fuse_views_ranged needs at least one view and nparts >= 1")

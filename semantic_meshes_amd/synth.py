@@ -86,9 +86,14 @@ def probs_seed(base_seed, view):
     return (int(base_seed) * 0x9E3779B1 + int(view) * 0x85EBCA6B + 0x5EED) & 0xFFFFFFFFFFFFFFFF
 
 
-def device_probs(width, height, classes, seed, zero_fraction=0.0, device=0, out=None):
+def device_probs(width, height, classes, seed, zero_fraction=0.0, device=0, out=None, dtype=np.float32):
     """float32 (W,H,C) class probabilities generated in HBM (kernel k_synth_probs); rows sum to 1,
-    `zero_fraction` of the pixels are all-zero don't-care rows."""
+    `zero_fraction` of the pixels are all-zero don't-care rows.  `dtype` float16 / "bfloat16": the same values narrowed on the
+    device (fusion.narrow_probs; `out` is then not used)."""
+    name = dtype if isinstance(dtype, str) else np.dtype(dtype).name
+    if name != "float32":
+        from .fusion import narrow_probs
+        return narrow_probs(device_probs(width, height, classes, seed, zero_fraction, device), name, device)
     n = width * height
     if out is None:
         buf = DeviceBuffer(n * classes * 4, device)
