@@ -199,6 +199,17 @@ LABEL_IMAGE_SIGNATURES = {
     "smesh_label_renderer_render_views": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, c_int, P(c_void_p), P(c_void_p), c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_probs_labels.h: the labels of a class-vector image and
+# their confusion matrix, product-only like the tables above
+PROF_PROBS_LABELS = 7
+PROBS_LABELS_SIGNATURES = {
+    "smesh_probs_labels": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_u32, c_float,
+                                   c_void_p, c_int, P(ctypes.c_int64), ctypes.c_int64, c_int, c_int]),
+    "smesh_confusion_add_probs": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                          c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_float,
+                                          c_void_p, c_int, P(ctypes.c_int64), ctypes.c_int64]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -326,7 +337,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

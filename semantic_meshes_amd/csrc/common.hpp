@@ -96,6 +96,12 @@ bool opt_raster_meshlets();
 // confusion_wave_aggregate: k_confusion adds the population count of the lanes that share a key once (default on; eval.hip).
 bool opt_confusion_wave_aggregate();
 
+// probs_labels_tiles: class-vector images whose layout allows it are arg-maxed from LDS tiles (default on; 0: every image takes the
+// generic one-lane-per-pixel path; probs_labels.hip).  Same results either way: a test hook.
+bool opt_probs_labels_tiles();
+// Largest class count the tiled path of probs_labels.hip serves.  Read-only option "probs_labels_tile_max_classes".
+constexpr uint32_t kProbsLabelsTileMaxC = 255;
+
 // Largest class count whose confusion matrix a workgroup of k_confusion keeps as a private uint32 histogram in LDS (eval.hip, where
 // the budget is stated and this value is checked against it).  Read-only option "confusion_lds_max_classes" (smesh_get_option).
 constexpr uint32_t kConfusionLdsMaxC = 180;

@@ -34,6 +34,9 @@ int fail_hip(hipError_t e, const char* what, const char* file, int line) {
 static std::atomic<int> g_confusion_wave_aggregate{1};   // (on: it pays on uniform label images, profiles/confusion_bench.json)
 bool opt_confusion_wave_aggregate() { return g_confusion_wave_aggregate.load() != 0; }
 
+static std::atomic<int> g_probs_labels_tiles{1};   // (off: the generic path everywhere -- a test hook, probs_labels.hip)
+bool opt_probs_labels_tiles() { return g_probs_labels_tiles.load() != 0; }
+
 static std::atomic<int> g_group_pipeline{-1};   // -1: not decided yet (the environment, else on)
 bool opt_group_pipeline() {
   int v = g_group_pipeline.load();
@@ -342,6 +345,8 @@ int smesh_set_option(const char* name, int64_t value) {
   // k_confusion (eval.hip): lanes of a wave that share a key add their population count once (1, the default), or every lane adds 1
   // for itself (0) -- same counts; tools/confusion_bench.py measures both
   if (!strcmp(name, "confusion_wave_aggregate")) { g_confusion_wave_aggregate.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  // probs_labels.hip: 0 sends every class-vector image down the generic one-lane-per-pixel path -- same labels, same counts
+  if (!strcmp(name, "probs_labels_tiles")) { g_probs_labels_tiles.store(value != 0 ? 1 : 0); return SMESH_OK; }
   return fail(SMESH_ERR_INVALID, std::string("unknown option: ") + name);
 }
 int smesh_get_option(const char* name, int64_t* value) {
@@ -356,6 +361,9 @@ int smesh_get_option(const char* name, int64_t* value) {
   // read-only: up to this class count k_confusion keeps a workgroup's histogram in LDS, beyond it adds straight into global memory
   if (!strcmp(name, "confusion_lds_max_classes")) { *value = (int64_t)kConfusionLdsMaxC; return SMESH_OK; }
   if (!strcmp(name, "confusion_wave_aggregate")) { *value = opt_confusion_wave_aggregate() ? 1 : 0; return SMESH_OK; }
+  if (!strcmp(name, "probs_labels_tiles")) { *value = opt_probs_labels_tiles() ? 1 : 0; return SMESH_OK; }
+  // read-only (smesh_probs_labels.h): the largest class count the tiled path serves
+  if (!strcmp(name, "probs_labels_tile_max_classes")) { *value = (int64_t)kProbsLabelsTileMaxC; return SMESH_OK; }
   // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --
   // "last_fuse_slot": the class-count slot handed to k_fuse_tri (5 / 13 / 19 / 20 / 21 / 40: the exact instances; 8 / 16 / 24 / 32 / 41 / 48:
   // the run-time-C instances with 8 .. 32, 40 and 48 register slots), 0 when the launch was k_fuse_tri_any, k_fuse_tri_wide or

@@ -6,48 +6,18 @@
 // tf.gather(annotations, primitive_indices) into a (H,W,C) float image, a confusion-matrix metric against the frame's label image).
 // Here a sample is two small integers: the ground-truth class g and the predicted class p = prim_labels[index], and the matrix cell
 // g (C + 1) + p gets one more.  Integer counts only: no result depends on launch shape, atomic order or batching.
-#include "common.hpp"
-
-#include <algorithm>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "../../include/smesh_eval.h"
+#include "confusion.hpp"
 
 using namespace smesh;
 
-struct smesh_confusion {
-  DeviceCtx* ctx = nullptr;
-  uint32_t C = 0;
-  uint64_t nbins = 0;                       // C (C + 1)
-  unsigned long long* d_counts = nullptr;   // [nbins + 1]: the matrix, then `ignored`
-  std::vector<uint64_t> merged;             // smesh_confusion_add_counts: [nbins + 1] on the host, added by get(); empty until used
-  Scratch stage_src, stage_gt, stage_lbl;   // device copies of HOST inputs (consumed before the call that staged them returns)
-  std::mutex mu;                            // held for a whole entry point; taken before the renderer's and the context's locks
-};
-
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kBlock = 1024;      // 16 waves: a histogram over 80 KiB leaves room for ONE workgroup per CU, and it should fill the CU
 constexpr int kPerThread = 4;     // samples per thread and step, their loads in flight together
 constexpr uint32_t kTile = kBlock * kPerThread;
 // A workgroup's uint32 bins cannot wrap: it takes at most kMaxTilesPerGroup tiles of kTile samples = 2^31 samples, and one bin gets
 // at most all of them.  (The host raises the grid for inputs beyond num_cus * 2^31 samples.)
 constexpr uint64_t kMaxTilesPerGroup = (1ull << 31) / kTile;
-// LDS budget of the histogram: 128 KiB of the CU's 160 KiB, declared statically.  Everything over 80 KiB means one workgroup per CU
-// anyway, and C = 150 (90.6 KB) is well inside; the small instance (16 KiB: up to 63 classes, which covers 19 and 40) lets two
-// workgroups share a CU.  kConfusionLdsMaxC (common.hpp) is the largest C with C (C + 1) + 1 counters in the budget.
-constexpr uint32_t kLdsWordsSmall = 4096, kLdsWordsLarge = 32768;
-static_assert((uint64_t)kConfusionLdsMaxC * (kConfusionLdsMaxC + 1) + 1 <= kLdsWordsLarge &&
-              (uint64_t)(kConfusionLdsMaxC + 1) * (kConfusionLdsMaxC + 2) + 1 > kLdsWordsLarge, "kConfusionLdsMaxC does not match the LDS budget");
-// In-wave aggregation: the lanes that share the first pending lane's key add their population count once.  Label images are large
-// uniform regions -- one to three distinct keys per wave -- so after kAggRounds rounds whoever is left adds 1 for itself: a wave of
-// 64 different keys pays three ballots, not 64.
-constexpr int kAggRounds = 3;
-constexpr uint32_t kNoClass = 0xFFFFFFFFu;
-
 struct ConfArgs {
   const void* src;              // labels mode: int32 pred[n]; image mode: the index image
   const int32_t* prim_labels;   // image mode: int32[P]; null: labels mode
@@ -63,22 +33,6 @@ struct ConfArgs {
   int aggregate;
 };
 
-// A ground-truth element as a class: its value where that lies in [0, C), else kNoClass (a negative value sign-extends to a huge one).
-__device__ __forceinline__ uint32_t load_class(const void* p, int dt, uint64_t off, uint32_t C) {
-  uint64_t u;
-  switch (dt) {
-    case SMESH_LBL_U8:  u = static_cast<const uint8_t*>(p)[off]; break;
-    case SMESH_LBL_I8:  u = (uint64_t)(int64_t) static_cast<const int8_t*>(p)[off]; break;
-    case SMESH_LBL_U16: u = static_cast<const uint16_t*>(p)[off]; break;
-    case SMESH_LBL_I16: u = (uint64_t)(int64_t) static_cast<const int16_t*>(p)[off]; break;
-    case SMESH_LBL_U32: u = static_cast<const uint32_t*>(p)[off]; break;
-    case SMESH_LBL_I32: u = (uint64_t)(int64_t) static_cast<const int32_t*>(p)[off]; break;
-    case SMESH_LBL_U64: u = static_cast<const uint64_t*>(p)[off]; break;
-    default:            u = (uint64_t) static_cast<const int64_t*>(p)[off]; break;
-  }
-  return u < (uint64_t)C ? (uint32_t)u : kNoClass;
-}
-
 // A primitive index, widened: the background (0xFFFFFFFF, or -1 of a signed image) is >= every P the host accepts.
 __device__ __forceinline__ uint64_t load_index(const void* p, int dt, uint64_t off) {
   switch (dt) {
@@ -87,31 +41,6 @@ __device__ __forceinline__ uint64_t load_index(const void* p, int dt, uint64_t o
     case SMESH_IDX_U64: return static_cast<const uint64_t*>(p)[off];
     default:            return (uint64_t) static_cast<const int64_t*>(p)[off];
   }
-}
-
-template <bool IN_LDS>
-__device__ __forceinline__ void add_count(uint32_t* hist, unsigned long long* counts, uint32_t key, uint32_t cnt) {
-  if (IN_LDS) atomicAdd(&hist[key], cnt);
-  else atomicAdd(&counts[key], (unsigned long long)cnt);
-}
-
-// One sample per lane (`on`: this lane has one).  Every lane of the wave gets here together.
-template <bool IN_LDS>
-__device__ __forceinline__ void add_keys(uint32_t* hist, unsigned long long* counts, uint32_t key, bool on, int aggregate) {
-  if (aggregate) {
-    const int lane = (int)(threadIdx.x & (kWave - 1));
-    unsigned long long todo = __ballot(on);
-    for (int round = 0; round < kAggRounds && todo; round++) {
-      const int src = __ffsll((long long)todo) - 1;
-      const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, src);   // wave-uniform
-      const bool mine = on && key == k;
-      const unsigned long long same = __ballot(mine);
-      if (lane == src) add_count<IN_LDS>(hist, counts, k, (uint32_t)__popcll(same));
-      on = on && !mine;
-      todo &= ~same;
-    }
-  }
-  if (on) add_count<IN_LDS>(hist, counts, key, 1u);
 }
 
 // The one counting kernel: 1-D labels, an index image with a label gather, dense or strided ground truth of any label dtype.
@@ -189,40 +118,7 @@ int launch_confusion(smesh_confusion* cm, ConfArgs a) {
   return SMESH_OK;
 }
 
-size_t label_itemsize(int dt) { return (size_t)1 << (dt >> 1); }
 size_t index_itemsize(int dt) { return dt <= SMESH_IDX_I32 ? 4 : 8; }
-
-bool bad_mem(int m) { return m != SMESH_MEM_HOST && m != SMESH_MEM_DEVICE; }
-
-int check_image_size(uint64_t W, uint64_t H) {
-  if (W > 65536 || H > 65536 || W * H >= 0x7FFFFFFFull / 4) return fail(SMESH_ERR_INVALID, "image too large");
-  return SMESH_OK;
-}
-
-int check_gt(const void* gt, int dt, const int64_t* strides, int mem) {
-  if (!gt) return fail(SMESH_ERR_INVALID, "NULL ground truth");
-  if (dt < 0 || dt > SMESH_LBL_I64) return fail(SMESH_ERR_INVALID, "bad ground-truth dtype");
-  if (strides && (strides[0] < 0 || strides[1] < 0)) return fail(SMESH_ERR_INVALID, "negative strides are not supported");
-  if (bad_mem(mem)) return fail(SMESH_ERR_INVALID, "bad memory kind");
-  return SMESH_OK;
-}
-
-bool is_dense(const int64_t* s, uint64_t W, uint64_t H) { return !s || ((s[0] == (int64_t)H || W == 1) && (s[1] == 1 || H == 1)); }
-
-// A (W,H) image of `itemsize`-byte elements on the device: itself, or a copy of the span its strides cover in `stage`.
-int image_on_device(DeviceCtx* ctx, Scratch& stage, const void* img, size_t itemsize, const int64_t* strides, int mem, uint64_t W, uint64_t H,
-                    const void** out, bool* staged) {
-  *out = img;
-  if (mem == SMESH_MEM_DEVICE) return SMESH_OK;
-  const int64_t dense[2] = {(int64_t)H, 1};
-  const int64_t* s = strides ? strides : dense;
-  const size_t span = (size_t)(1 + (W - 1) * (uint64_t)s[0] + (H - 1) * (uint64_t)s[1]) * itemsize;
-  SMESH_TRY(stage.reserve(std::max<size_t>(span, 16)));
-  SMESH_HIP(hipMemcpyAsync(stage.ptr, img, span, hipMemcpyHostToDevice, ctx->stream));
-  *out = stage.ptr;
-  *staged = true;
-  return SMESH_OK;
-}
 
 void set_gt(ConfArgs& a, const void* d_gt, int dt, const int64_t* strides, uint64_t W, uint64_t H) {
   a.gt = d_gt;
@@ -252,6 +148,19 @@ int count_plane(smesh_confusion* cm, const uint32_t* d_idx, const int32_t* d_lab
 }
 
 }  // namespace
+
+int smesh_confusion_count_label_image(smesh_confusion* cm, const int32_t* d_labels, const void* d_gt, int gt_dtype, const int64_t* gt_strides,
+                                      uint64_t W, uint64_t H) {
+  ConfArgs a = {};
+  a.src = d_labels;
+  a.n = W * H;
+  a.H = (uint32_t)H;
+  a.idx_dense = 1;
+  a.is0 = (int64_t)H;
+  a.is1 = 1;
+  set_gt(a, d_gt, gt_dtype, gt_strides, W, H);
+  return launch_confusion(cm, a);
+}
 
 extern "C" {
 

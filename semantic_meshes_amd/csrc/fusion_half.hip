@@ -78,20 +78,6 @@ typedef u32x4 u32x4_a2 __attribute__((aligned(2)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef u32x2 u32x2_a2 __attribute__((aligned(2)));
 typedef uint32_t u32_a2 __attribute__((aligned(2)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-
-// Two packed elements -> two float32, exactly.  binary16: v_cvt_f32_f16 (the kernels run in hipcc's default mode, which keeps
-// binary16 subnormals); bfloat16: the bits moved up.
-__device__ __forceinline__ void unpack2(uint32_t w, bool bf, float& lo, float& hi) {
-  if (bf) {
-    lo = __uint_as_float(w << 16);
-    hi = __uint_as_float(w & 0xFFFF0000u);
-  } else {
-    const h16x2 h = __builtin_bit_cast(h16x2, w);
-    lo = (float)h.x;
-    hi = (float)h.y;
-  }
-}
 
 // The row at `pr` into CT float32 registers, C <= CT run-time classes with CT = the multiple of eight at or above C: every chunk of
 // eight but the last is full.  Elements c >= C come out as +0.

@@ -18,6 +18,21 @@ constexpr uint32_t kHalfMaxClasses = 48;
 constexpr int kHalfMode = 0x10;
 inline int half_dtype_of(int mode) { return (mode & kHalfMode) ? (mode & 0xF) : 0; }
 
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+
+// Two packed elements -> two float32, exactly.  binary16: v_cvt_f32_f16 (the kernels run in hipcc's default mode, which keeps
+// binary16 subnormals); bfloat16: the bits moved up.  (fusion_half.hip and probs_labels.hip widen with this and nothing else.)
+__device__ __forceinline__ void unpack2(uint32_t w, bool bf, float& lo, float& hi) {
+  if (bf) {
+    lo = __uint_as_float(w << 16);
+    hi = __uint_as_float(w & 0xFFFF0000u);
+  } else {
+    const h16x2 h = __builtin_bit_cast(h16x2, w);
+    lo = (float)h.x;
+    hi = (float)h.y;
+  }
+}
+
 // Staged host images (16 bits per element) and staged weights of up to eight views, and the widened float32 image of the routes
 // k_fuse_tri_h16 does not serve.  Everything that writes or reads them is ordered on the context's main stream.  `mu` is held for a
 // whole entry point of smesh_half.h: it is taken before any other lock of the library, and by those entry points only.

@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, describe, release_to, to_device
+from .device import DeviceArray, DeviceBuffer, describe, release_to, to_device
 
 _IDX_CODES = {np.dtype(np.uint32): _lib.IDX_U32, np.dtype(np.int32): _lib.IDX_I32,
               np.dtype(np.uint64): _lib.IDX_U64, np.dtype(np.int64): _lib.IDX_I64}
@@ -62,12 +62,109 @@ def lds_max_classes():
     return int(v.value)
 
 
+# ---- the labels of a class-vector image (include/smesh_probs_labels.h) ---------------------------------------------------------
+_OUT_DTYPES = {np.dtype(np.uint8): 255, np.dtype(np.uint16): 65535, np.dtype(np.int32): 2 ** 31 - 1}
+
+
+def _describe_probs(probs, probs_dtype, device, streams, what="probs image"):
+    """(pointer, memkind, (W,H,C), SMESH_PROBS_* code, element strides, keep-alive) of a class-vector image: what
+    `MeshAggregator.add` takes -- float32 / float16 / bfloat16, numpy, `__cuda_array_interface__` or DLPack, any non-negative strides."""
+    from .fusion import probs_code
+    if isinstance(probs, np.ndarray):
+        probs_code(probs.dtype, probs, probs_dtype, what)       # (a refused probs_dtype is refused before anything is touched)
+    pp, pmem, pshape, pdt, pstr, keep = describe(probs, 3, what, device, streams)
+    code = probs_code(pdt, keep, probs_dtype, what)
+    if code is None:
+        if pmem == _lib.MEM_HOST and pdt.kind == "f":
+            pp, pmem, pshape, pdt, pstr, keep = describe(np.asarray(keep, dtype=np.float32), 3, what, device, streams)
+            code = _lib.PROBS_F32
+        else:
+            raise ValueError("%s must be float32, float16 or bfloat16, got %s" % (what, pdt))
+    if pshape[2] < 1:
+        raise ValueError("%s must have at least one class, got shape %s" % (what, tuple(pshape)))
+    return pp, pmem, tuple(int(v) for v in pshape), code, tuple(pstr), keep
+
+
+def _label_out(classes, dtype, dont_care_label):
+    """(numpy dtype, don't-care value) of a label image for `classes` classes: uint8 up to 255 classes, else uint16, unless `dtype`
+    (uint8 / uint16 / int32) says otherwise; the don't-care value defaults to the dtype's maximum and is never a class."""
+    classes = int(classes)
+    if dtype is None:
+        if classes > 65535:
+            raise ValueError("more than 65535 classes need dtype=np.int32")
+        dt = np.dtype(np.uint8 if classes <= 255 else np.uint16)
+    else:
+        dt = np.dtype(dtype)
+        if dt not in _OUT_DTYPES:
+            raise ValueError("label dtype must be uint8, uint16 or int32, got %s" % dt)
+    if dt != np.int32 and classes > _OUT_DTYPES[dt]:
+        raise ValueError("%s is too narrow for %d classes" % (dt, classes))
+    dc = _OUT_DTYPES[dt] if dont_care_label is None else int(dont_care_label)
+    info = np.iinfo(dt)
+    if not info.min <= dc <= info.max:
+        raise ValueError("%s cannot hold the don't-care label %d" % (dt, dc))
+    if 0 <= dc < classes:
+        raise ValueError("the don't-care label %d is one of the %d classes" % (dc, classes))
+    return dt, dc
+
+
+def _threshold(dont_care_threshold):
+    """None: no don't-care test (-inf: the kernel computes no sum)."""
+    if dont_care_threshold is None:
+        return float("-inf")
+    t = float(dont_care_threshold)
+    if t != t:
+        raise ValueError("the don't-care threshold must not be NaN")
+    return t
+
+
+def _label_image_like(W, H, pstr, dt, device):
+    """A fresh (W,H) device image of `dt` whose memory order follows the class-vector image's pixel order: y fastest for the dense
+    (W,H,C) image, x fastest for a network's (H,W,C) tensor seen as (W,H,C)."""
+    buf = DeviceBuffer(max(W * H * dt.itemsize, 1), device)
+    strides = (1, W) if (W > 1 and H > 1 and pstr[0] < pstr[1]) else (H, 1)
+    return DeviceArray(buf.ptr, (W, H), dt, device, strides, owner=buf)
+
+
+def argmax_labels_device(probs, dont_care_threshold=None, dont_care_label=None, dtype=None, probs_dtype=None, device=0):
+    """The label of every pixel of a class-vector image `probs` (W,H,C), on the device: the lowest class with the largest value (a NaN
+    never replaces the current best; include/smesh_probs_labels.h), as a (W,H) `DeviceArray` of `dtype` (None: uint8 up to 255
+    classes, else uint16).  With `dont_care_threshold` a pixel whose float32 class sum is below it gets `dont_care_label` (None: the
+    dtype's maximum) -- what `add_labels` and `ConfusionMatrix` read as "don't care".  `probs`: what `MeshAggregator.add` takes
+    (float32 / float16 / bfloat16; numpy, device arrays, DLPack; a (H,W,C) tensor as its transposed view); the result's memory order
+    follows the input's pixel order.  `add_labels(idx, argmax_labels_device(probs))` is hard-vote fusion of soft predictions."""
+    streams = []
+    thr = _threshold(dont_care_threshold)
+    pp, pmem, (W, H, C), code, pstr, keep = _describe_probs(probs, probs_dtype, device, streams)
+    dt, dc = _label_out(C, dtype, dont_care_label)
+    if isinstance(keep, DeviceArray):
+        device = keep.device
+    out = _label_image_like(W, H, pstr, dt, device)
+    if W and H:
+        _lib.check(_lib.lib().smesh_probs_labels(ctypes.c_void_p(pp), code, _c64(pstr), pmem, W, H, C, thr,
+                                                 ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], _c64(out.strides), dc, _lib.MEM_DEVICE,
+                                                 int(device)))
+    release_to(device, streams)
+    if pmem == _lib.MEM_DEVICE:
+        if isinstance(keep, DeviceArray):
+            out._inputs = keep            # (the kernel may still be reading it)
+        else:
+            _lib.synchronize(device)      # (a foreign input may be freed by its owner as soon as we return)
+    return out
+
+
+def argmax_labels(probs, dont_care_threshold=None, dont_care_label=None, dtype=None, probs_dtype=None, device=0):
+    """`argmax_labels_device` copied to a numpy array (W,H)."""
+    return argmax_labels_device(probs, dont_care_threshold, dont_care_label, dtype, probs_dtype, device).numpy()
+
+
 class ConfusionMatrix:
     """`ConfusionMatrix(classes, device=0)`: counts on `device`, read with `get()`.
 
     cm.add_views(renderer, cameras, labels, gt_images)   rasterise and score; no plane leaves HBM (add_view: one camera)
     cm.add_image(primitive_indices, labels, gt)          an index image from render() or from a cache
     cm.add(pred, gt)                                     1-D: per-vertex labels against per-vertex ground truth
+    cm.add_probs(probs, gt)                              the network's own (W,H,C) class-vector image, arg-maxed and counted in one pass
 
     `labels` is int32 [P], one label per primitive (`MeshAggregator.labels()` / `labels_device()`); ground truth is any integer
     dtype, images are (W,H) -- an (H,W) array passed as its transposed view is fine.  Host numpy or device arrays.  Device inputs
@@ -182,6 +279,36 @@ class ConfusionMatrix:
             _lib.check(_lib.lib().smesh_confusion_add_views(self._h, renderer._h, pods, m, ctypes.c_void_p(lp), P, gptr,
                                                             first[2], _c64(first[3]), first[1]))
         self._done(streams, [k0] + [d[4] for d in desc])
+
+    def add_probs(self, probs, gt, dont_care_threshold=None, probs_dtype=None, labels_out=False):
+        """Score a class-vector image itself -- the network's own prediction, the baseline the fused mesh is compared with: `probs`
+        (W,H,C) with C = classes (what `MeshAggregator.add` takes), arg-maxed by the rule of `argmax_labels_device` and counted against
+        `gt` integer (W,H) in the same pass.  With `dont_care_threshold` a pixel whose class sum is below it counts as don't care.
+        `labels_out=True` returns the label image of that pass as a (W,H) `DeviceArray`."""
+        streams = []
+        thr = _threshold(dont_care_threshold)
+        pp, pmem, (W, H, C), code, pstr, k0 = _describe_probs(probs, probs_dtype, self.device, streams)
+        if C != self.classes:
+            raise ValueError("probs image has %d classes, the confusion matrix was built for %d" % (C, self.classes))
+        gp, gmem, gcode, gstr, k1 = self._gt(gt, 2, (W, H), "ground truth", streams)
+        out, optr, ocode, ostr, dc = None, None, 0, None, 0
+        if labels_out:
+            dt, dc = _label_out(C, None if C <= 65535 else np.int32, None)
+            out = _label_image_like(W, H, pstr, dt, self.device)
+            optr, ocode, ostr = ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], _c64(out.strides)
+        if W and H:
+            _lib.check(_lib.lib().smesh_confusion_add_probs(self._h, ctypes.c_void_p(pp), code, _c64(pstr), pmem,
+                                                            ctypes.c_void_p(gp), gcode, _c64(gstr), gmem, W, H, thr, optr, ocode, ostr, dc))
+        self._done(streams, [k0, k1])
+        return out
+
+    def add_probs_many(self, probs_images, gt_images, dont_care_threshold=None, probs_dtype=None, labels_out=False):
+        """`add_probs` for a batch: a loop.  Returns the list of label images with `labels_out=True`."""
+        probs_images, gt_images = list(probs_images), list(gt_images)
+        if len(probs_images) != len(gt_images):
+            raise ValueError("add_probs_many needs one ground-truth image per class-vector image")
+        outs = [self.add_probs(p, g, dont_care_threshold, probs_dtype, labels_out) for p, g in zip(probs_images, gt_images)]
+        return outs if labels_out else None
 
     def add_counts(self, M, ignored=0):
         """Merge a matrix counted elsewhere (another rank, another scene): uint64 [classes, classes + 1]."""

@@ -1009,4 +1009,5 @@ def MeshAggregator(primitives, classes, aggregator="sum", images_equal_weight=0.
 
 # Confusion matrices of the fused mesh against ground truth (include/smesh_eval.h)
 from .evaluation import ConfusionMatrix, confusion_accuracy, confusion_iou, confusion_mean_iou  # noqa: E402,F401
+from .evaluation import argmax_labels, argmax_labels_device  # noqa: E402,F401
 from .label_images import LabelRenderer  # noqa: E402,F401
