@@ -210,6 +210,20 @@ PROBS_LABELS_SIGNATURES = {
                                           c_void_p, c_int, P(ctypes.c_int64), ctypes.c_int64]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_resize.h: class-vector images resampled from the
+# network's resolution to the camera's, their labels and their confusion matrix, product-only like the tables above (no profile slot)
+RESIZE_BILINEAR = 1
+RESIZE_MODES = {"bilinear": RESIZE_BILINEAR}
+RESIZE_SIGNATURES = {
+    "smesh_resize_probs": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_u32,
+                                   c_void_p, c_int, c_u64, c_u64, c_int, c_int]),
+    "smesh_resize_probs_labels": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_u32, c_float,
+                                          c_void_p, c_int, P(ctypes.c_int64), ctypes.c_int64, c_u64, c_u64, c_int, c_int]),
+    "smesh_confusion_add_probs_resized": (c_int, [c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64,
+                                                  c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_float, c_int,
+                                                  c_void_p, c_int, P(ctypes.c_int64), ctypes.c_int64]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -337,7 +351,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

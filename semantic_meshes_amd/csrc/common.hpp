@@ -99,6 +99,9 @@ bool opt_confusion_wave_aggregate();
 // probs_labels_tiles: class-vector images whose layout allows it are arg-maxed from LDS tiles (default on; 0: every image takes the
 // generic one-lane-per-pixel path; probs_labels.hip).  Same results either way: a test hook.
 bool opt_probs_labels_tiles();
+// resize_vector: class-vector images whose layout allows it are resampled with 16-byte loads and stores (default on; 0: every image
+// takes the generic one-lane-per-element path; resize.hip).  Same results either way: a test hook.
+bool opt_resize_vector();
 // Largest class count the tiled path of probs_labels.hip serves.  Read-only option "probs_labels_tile_max_classes".
 constexpr uint32_t kProbsLabelsTileMaxC = 255;
 

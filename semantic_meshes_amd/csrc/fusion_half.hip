@@ -417,18 +417,7 @@ __global__ __launch_bounds__(256) void k_widen_probs16(const uint16_t* __restric
   }
 }
 
-// float32 -> bfloat16 bits, round to nearest even; NaN stays a (quiet) NaN, overflow rounds to inf.
-__device__ __forceinline__ uint32_t bf16_rne(float x) {
-  const uint32_t u = __float_as_uint(x);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-// float32 -> binary16 bits: v_cvt_f16_f32 in the default mode (round to nearest even, subnormal results kept, overflow to inf).
-__device__ __forceinline__ uint32_t f16_rne(float x) {
-  const _Float16 h = (_Float16)x;
-  return (uint32_t)__builtin_bit_cast(uint16_t, h);
-}
-
+// (bf16_rne / f16_rne, the narrowing of smesh_narrow_probs: half_scratch.hpp)
 // smesh_narrow_probs: four elements per thread (one 16-byte load, one 8-byte store), the last few one by one.
 __global__ __launch_bounds__(256) void k_narrow_probs(const float* __restrict__ in, uint16_t* __restrict__ out, uint64_t n, uint32_t bf16) {
   const uint64_t e = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4u;

@@ -33,6 +33,19 @@ __device__ __forceinline__ void unpack2(uint32_t w, bool bf, float& lo, float& h
   }
 }
 
+// The narrowing of smesh_narrow_probs (fusion_half.hip; resize.hip rounds its 16-bit outputs with it).
+// float32 -> bfloat16 bits, round to nearest even; NaN stays a (quiet) NaN, overflow rounds to inf.
+__device__ __forceinline__ uint32_t bf16_rne(float x) {
+  const uint32_t u = __float_as_uint(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+// float32 -> binary16 bits: v_cvt_f16_f32 in the default mode (round to nearest even, subnormal results kept, overflow to inf).
+__device__ __forceinline__ uint32_t f16_rne(float x) {
+  const _Float16 h = (_Float16)x;
+  return (uint32_t)__builtin_bit_cast(uint16_t, h);
+}
+
 // Staged host images (16 bits per element) and staged weights of up to eight views, and the widened float32 image of the routes
 // k_fuse_tri_h16 does not serve.  Everything that writes or reads them is ordered on the context's main stream.  `mu` is held for a
 // whole entry point of smesh_half.h: it is taken before any other lock of the library, and by those entry points only.

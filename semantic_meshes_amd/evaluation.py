@@ -126,24 +126,44 @@ def _label_image_like(W, H, pstr, dt, device):
     return DeviceArray(buf.ptr, (W, H), dt, device, strides, owner=buf)
 
 
-def argmax_labels_device(probs, dont_care_threshold=None, dont_care_label=None, dtype=None, probs_dtype=None, device=0):
+def argmax_labels_device(probs, dont_care_threshold=None, dont_care_label=None, dtype=None, probs_dtype=None, device=0, size=None,
+                         resize=None):
     """The label of every pixel of a class-vector image `probs` (W,H,C), on the device: the lowest class with the largest value (a NaN
     never replaces the current best; include/smesh_probs_labels.h), as a (W,H) `DeviceArray` of `dtype` (None: uint8 up to 255
     classes, else uint16).  With `dont_care_threshold` a pixel whose float32 class sum is below it gets `dont_care_label` (None: the
     dtype's maximum) -- what `add_labels` and `ConfusionMatrix` read as "don't care".  `probs`: what `MeshAggregator.add` takes
     (float32 / float16 / bfloat16; numpy, device arrays, DLPack; a (H,W,C) tensor as its transposed view); the result's memory order
-    follows the input's pixel order.  `add_labels(idx, argmax_labels_device(probs))` is hard-vote fusion of soft predictions."""
+    follows the input's pixel order.  `add_labels(idx, argmax_labels_device(probs))` is hard-vote fusion of soft predictions.
+    With `size=(W,H)` and `resize="bilinear"` the labels are those of `resize_probs(probs, size)` in float32 (resize.py; DESIGN.md
+    3.8) -- a dense (W,H) image, and no (W,H,C) image is built."""
+    from .resize import resize_mode, target_size
+    mode = resize_mode(resize)
+    if (size is None) != (mode is None):
+        raise ValueError("size=(W,H) and resize='bilinear' go together, got size=%r, resize=%r" % (size, resize))
+    if size is not None:
+        size = target_size(size)
     streams = []
     thr = _threshold(dont_care_threshold)
     pp, pmem, (W, H, C), code, pstr, keep = _describe_probs(probs, probs_dtype, device, streams)
     dt, dc = _label_out(C, dtype, dont_care_label)
     if isinstance(keep, DeviceArray):
         device = keep.device
-    out = _label_image_like(W, H, pstr, dt, device)
-    if W and H:
-        _lib.check(_lib.lib().smesh_probs_labels(ctypes.c_void_p(pp), code, _c64(pstr), pmem, W, H, C, thr,
-                                                 ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], _c64(out.strides), dc, _lib.MEM_DEVICE,
-                                                 int(device)))
+    if mode is not None:
+        w, h = W, H
+        W, H = size
+        if W and H and not (w and h):
+            raise ValueError("an empty probs image %s cannot be resampled to %s" % ((w, h), (W, H)))
+        out = DeviceBuffer(max(W * H * dt.itemsize, 1), device).view((W, H), dt)
+        if W and H:
+            _lib.check(_lib.lib().smesh_resize_probs_labels(ctypes.c_void_p(pp), code, _c64(pstr), pmem, w, h, C, thr,
+                                                            ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], _c64(out.strides), dc,
+                                                            W, H, mode, int(device)))
+    else:
+        out = _label_image_like(W, H, pstr, dt, device)
+        if W and H:
+            _lib.check(_lib.lib().smesh_probs_labels(ctypes.c_void_p(pp), code, _c64(pstr), pmem, W, H, C, thr,
+                                                     ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], _c64(out.strides), dc, _lib.MEM_DEVICE,
+                                                     int(device)))
     release_to(device, streams)
     if pmem == _lib.MEM_DEVICE:
         if isinstance(keep, DeviceArray):
@@ -153,9 +173,9 @@ def argmax_labels_device(probs, dont_care_threshold=None, dont_care_label=None, 
     return out
 
 
-def argmax_labels(probs, dont_care_threshold=None, dont_care_label=None, dtype=None, probs_dtype=None, device=0):
+def argmax_labels(probs, dont_care_threshold=None, dont_care_label=None, dtype=None, probs_dtype=None, device=0, size=None, resize=None):
     """`argmax_labels_device` copied to a numpy array (W,H)."""
-    return argmax_labels_device(probs, dont_care_threshold, dont_care_label, dtype, probs_dtype, device).numpy()
+    return argmax_labels_device(probs, dont_care_threshold, dont_care_label, dtype, probs_dtype, device, size, resize).numpy()
 
 
 class ConfusionMatrix:
@@ -280,16 +300,23 @@ class ConfusionMatrix:
                                                             first[2], _c64(first[3]), first[1]))
         self._done(streams, [k0] + [d[4] for d in desc])
 
-    def add_probs(self, probs, gt, dont_care_threshold=None, probs_dtype=None, labels_out=False):
+    def add_probs(self, probs, gt, dont_care_threshold=None, probs_dtype=None, labels_out=False, resize=None):
         """Score a class-vector image itself -- the network's own prediction, the baseline the fused mesh is compared with: `probs`
         (W,H,C) with C = classes (what `MeshAggregator.add` takes), arg-maxed by the rule of `argmax_labels_device` and counted against
         `gt` integer (W,H) in the same pass.  With `dont_care_threshold` a pixel whose class sum is below it counts as don't care.
-        `labels_out=True` returns the label image of that pass as a (W,H) `DeviceArray`."""
+        `labels_out=True` returns the label image of that pass as a (W,H) `DeviceArray`.  With `resize="bilinear"` a `probs` image
+        whose (w,h) is not `gt`'s (W,H) is scored as `resize_probs(probs, (W,H))` would be (resize.py), without that image being
+        built; with `resize=None` such a pair is refused."""
+        from .resize import resize_mode
+        mode = resize_mode(resize)
         streams = []
         thr = _threshold(dont_care_threshold)
         pp, pmem, (W, H, C), code, pstr, k0 = _describe_probs(probs, probs_dtype, self.device, streams)
         if C != self.classes:
             raise ValueError("probs image has %d classes, the confusion matrix was built for %d" % (C, self.classes))
+        gshape = tuple(getattr(gt, "shape", None) or np.shape(gt)) if mode is not None else (W, H)
+        if mode is not None and len(gshape) == 2 and gshape != (W, H):
+            return self._add_probs_resized(streams, thr, (pp, pmem, (W, H, C), code, pstr, k0), gt, gshape, labels_out, mode)
         gp, gmem, gcode, gstr, k1 = self._gt(gt, 2, (W, H), "ground truth", streams)
         out, optr, ocode, ostr, dc = None, None, 0, None, 0
         if labels_out:
@@ -302,12 +329,31 @@ class ConfusionMatrix:
         self._done(streams, [k0, k1])
         return out
 
-    def add_probs_many(self, probs_images, gt_images, dont_care_threshold=None, probs_dtype=None, labels_out=False):
+    def _add_probs_resized(self, streams, thr, desc, gt, gshape, labels_out, mode):
+        """`add_probs` for a (w,h,C) image against (W,H) ground truth: `smesh_confusion_add_probs_resized`."""
+        pp, pmem, (w, h, C), code, pstr, k0 = desc
+        W, H = int(gshape[0]), int(gshape[1])
+        if W and H and not (w and h):
+            raise ValueError("an empty probs image %s cannot be resampled to %s" % ((w, h), (W, H)))
+        gp, gmem, gcode, gstr, k1 = self._gt(gt, 2, (W, H), "ground truth", streams)
+        out, optr, ocode, ostr, dc = None, None, 0, None, 0
+        if labels_out:
+            dt, dc = _label_out(C, None if C <= 65535 else np.int32, None)
+            out = DeviceBuffer(max(W * H * dt.itemsize, 1), self.device).view((W, H), dt)
+            optr, ocode, ostr = ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], _c64(out.strides)
+        if W and H:
+            _lib.check(_lib.lib().smesh_confusion_add_probs_resized(self._h, ctypes.c_void_p(pp), code, _c64(pstr), pmem, w, h,
+                                                                    ctypes.c_void_p(gp), gcode, _c64(gstr), gmem, W, H, thr, mode,
+                                                                    optr, ocode, ostr, dc))
+        self._done(streams, [k0, k1])
+        return out
+
+    def add_probs_many(self, probs_images, gt_images, dont_care_threshold=None, probs_dtype=None, labels_out=False, resize=None):
         """`add_probs` for a batch: a loop.  Returns the list of label images with `labels_out=True`."""
         probs_images, gt_images = list(probs_images), list(gt_images)
         if len(probs_images) != len(gt_images):
             raise ValueError("add_probs_many needs one ground-truth image per class-vector image")
-        outs = [self.add_probs(p, g, dont_care_threshold, probs_dtype, labels_out) for p, g in zip(probs_images, gt_images)]
+        outs = [self.add_probs(p, g, dont_care_threshold, probs_dtype, labels_out, resize) for p, g in zip(probs_images, gt_images)]
         return outs if labels_out else None
 
     def add_counts(self, M, ignored=0):

@@ -260,6 +260,20 @@ class _MeshAggregator:
                     break
                 self._inflight.pop(0)
 
+    def _resampled(self, probs_image, size, mode, probs_dtype):
+        """`probs_image` as a view of `size` = (W,H) takes it (the `resize=` keyword of add / add_many / fuse_view / fuse_views,
+        include/smesh_resize.h): itself where `mode` is None or its width and height are the view's already; else its resampled
+        image -- a dense DeviceArray of the input's dtype that this library owns and nobody else has seen, which is what `_deferrable`
+        asks for, so such views still gather in groups of eight and 16-bit images still reach the 16-bit kernel.  The kernel runs on
+        the library's main stream, ahead of the fusion that reads its output.  (An image that does not say its shape -- a DLPack
+        capsule -- is resampled whatever its size: equal sizes give an exact copy.)"""
+        if mode is None:
+            return probs_image
+        from .resize import _resize_device, image_size
+        if image_size(probs_image) == tuple(size):
+            return probs_image
+        return _resize_device(probs_image, tuple(size), None, probs_dtype, mode, self.device, hold=self._hold)
+
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
         self._pending = []      # (views nobody can ask the result of any more)
@@ -273,17 +287,25 @@ class _MeshAggregator:
             except Exception:
                 pass
 
-    def add(self, primitive_image, probs_image, weights_image=None, probs_dtype=None):
+    def add(self, primitive_image, probs_image, weights_image=None, probs_dtype=None, resize=None):
         """Fuse one view: `primitive_image` (W,H) of uint32/int32/uint64/int64, `probs_image` (W,H,C) float32, float16 or bfloat16,
         optional `weights_image` (W,H) float32; host numpy or device arrays, any non-negative strides.  A 16-bit image gives what
         its exactly widened float32 copy gives, without that copy (include/smesh_half.h); `probs_dtype="bfloat16"` says that a
-        uint16 array holds bfloat16 bits (see `probs_code`), None infers the dtype from the array."""
+        uint16 array holds bfloat16 bits (see `probs_code`), None infers the dtype from the array.  `resize="bilinear"`: a
+        `probs_image` (w,h,C) at the network's resolution is resampled to the index image's (W,H) on the device first (`_resampled`,
+        DESIGN.md 3.8); the weights image stays (W,H).  With `resize=None` such an image is refused."""
+        from .resize import resize_mode
+        mode = resize_mode(resize)
         if type(primitive_image).__name__ == "PyCapsule":
             # render() in capsule mode (the reference's return type) handed straight back, as python/scripts/colorize_cityscapes_mesh.py:65-67 does
             from . import dlpack
             own = dlpack.own_capsule_owner(primitive_image)
             if own is not None:
                 primitive_image = own
+        if mode is not None:
+            tshape = tuple(getattr(primitive_image, "shape", None) or np.shape(primitive_image))
+            if len(tshape) == 2:      # (anything else is refused below, as without the keyword)
+                probs_image = self._resampled(probs_image, tshape, mode, probs_dtype)
         lazy = getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
         dcode = self._deferrable(probs_image, weights_image, *primitive_image.shape, probs_dtype=probs_dtype) if lazy else None
         if dcode is not None:
@@ -512,17 +534,29 @@ class _MeshAggregator:
         if first[1] == _lib.MEM_DEVICE:
             self._hold([d[4] for d, _ in desc] + [dw[4] for _, dw in desc if dw is not None])
 
-    def add_many(self, primitive_images, probs_images, weights_images=None, probs_dtype=None):
+    def add_many(self, primitive_images, probs_images, weights_images=None, probs_dtype=None, resize=None):
         """`add()` for a batch of views, in order (new functionality; the reference's loop adds one image per call).  Same sums as
         the calls one by one -- per accumulator row the same float32 additions in the same order -- but device-resident dense
         uint32 / int32 index images with dense float32 device class vectors, all of one size, share their kernel launches in groups
-        of up to eight (`smesh_aggregator_add_many`).  Anything else in the batch is added image by image."""
+        of up to eight (`smesh_aggregator_add_many`).  Anything else in the batch is added image by image.  `resize="bilinear"`: see
+        add(); the batch is worked through in chunks of eight views, so at most eight resampled images are alive at once."""
+        from .resize import resize_mode
+        mode = resize_mode(resize)
         prims, probs = list(primitive_images), list(probs_images)
         wts = None if weights_images is None else list(weights_images)
         n = len(prims)
         if len(probs) != n or (wts is not None and len(wts) != n):
             raise ValueError("add_many needs one probs image (and one weights image) per primitive image")
         if n == 0:
+            return
+        if mode is not None:
+            for lo in range(0, n, GROUP_VIEWS):
+                hi = min(lo + GROUP_VIEWS, n)
+                chunk = []
+                for i in range(lo, hi):
+                    tshape = tuple(getattr(prims[i], "shape", None) or np.shape(prims[i]))
+                    chunk.append(self._resampled(probs[i], tshape, mode, probs_dtype) if len(tshape) == 2 else probs[i])
+                self.add_many(prims[lo:hi], chunk, None if wts is None else wts[lo:hi], probs_dtype=probs_dtype)
             return
         codes = [_peek_code(p, probs_dtype) for p in probs]
         known = [c for c in codes if c is not None]
@@ -669,10 +703,13 @@ class _MeshAggregator:
         """`ModelAggregator::renderer()` (Mesh.h:124-129): snapshot of the fused annotations for image gathers."""
         return ModelRenderer(self)
 
-    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None):
+    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None):
         """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
-        float32, float16 or bfloat16 (see add())."""
+        float32, float16 or bfloat16 (see add()); with `resize="bilinear"` any (w,h,C) image add() takes, resampled to the camera's
+        resolution on the device first."""
+        from .resize import resize_mode
         W, H = camera.resolution
+        probs_image = self._resampled(probs_image, (W, H), resize_mode(resize), probs_dtype)
         dcode = None
         if W > 0 and H > 0 and W <= 65536 and H <= 65536 and W * H < 0x7FFFFFFF // 4 and renderer.device == self.device:
             dcode = self._deferrable(probs_image, weights_image, W, H, probs_dtype=probs_dtype)
@@ -740,11 +777,28 @@ class _MeshAggregator:
         return (pods, n, pptr, (None if weights_images is None else wptr), (mem if mem is not None else _lib.MEM_HOST), keep, streams,
                 _lib.PROBS_F32 if code is None else code)
 
-    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None):
+    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
         accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
-        have one dtype: float32, float16 or bfloat16 (see add())."""
+        have one dtype: float32, float16 or bfloat16 (see add()).  `resize="bilinear"`: images at the network's resolution are
+        resampled to their camera's on the device (see add()); when any image of the batch needs that, the batch is worked through in
+        chunks of eight views -- the views of a fusion launch -- so at most eight resampled images are alive at once.  Same views in
+        the same order: the same sums."""
+        from .resize import image_size, resize_mode
+        mode = resize_mode(resize)
+        if mode is not None:
+            cameras, probs_images = list(cameras), list(probs_images)
+            wts = None if weights_images is None else list(weights_images)
+            n = len(cameras)
+            if len(probs_images) != n or (wts is not None and len(wts) != n):
+                raise ValueError("fuse_views needs one probs image (and one weights image or None) per camera")
+            if any(image_size(p) != tuple(cam.resolution) for cam, p in zip(cameras, probs_images)):
+                for lo in range(0, n, GROUP_VIEWS):
+                    hi = min(lo + GROUP_VIEWS, n)
+                    chunk = [self._resampled(probs_images[i], tuple(cameras[i].resolution), mode, probs_dtype) for i in range(lo, hi)]
+                    self.fuse_views(renderer, cameras[lo:hi], chunk, None if wts is None else wts[lo:hi], probs_dtype=probs_dtype)
+                return
         pods, n, pptr, wptr, mem, keep, streams, code = self._marshal_views(cameras, probs_images, weights_images, "fuse_views", probs_dtype)
         if n == 0:
             return
@@ -1011,3 +1065,4 @@ def MeshAggregator(primitives, classes, aggregator="sum", images_equal_weight=0.
 from .evaluation import ConfusionMatrix, confusion_accuracy, confusion_iou, confusion_mean_iou  # noqa: E402,F401
 from .evaluation import argmax_labels, argmax_labels_device  # noqa: E402,F401
 from .label_images import LabelRenderer  # noqa: E402,F401
+from .resize import resize_probs, resize_probs_device  # noqa: E402,F401
