@@ -224,6 +224,18 @@ RESIZE_SIGNATURES = {
                                                   c_void_p, c_int, P(ctypes.c_int64), ctypes.c_int64]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_sampled.h: (w,h,C) class vectors sampled inside the
+# fusion kernel, product-only like the tables above
+SAMPLED_SIGNATURES = {
+    "smesh_fuse_views_sampled": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, P(c_void_p), c_int, P(ctypes.c_int64), c_u64, c_u64,
+                                         P(c_void_p), c_int, c_int]),
+    "smesh_fuse_view_sampled": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_void_p, c_int, P(ctypes.c_int64), c_u64, c_u64,
+                                        c_void_p, c_int, c_int]),
+    "smesh_aggregator_add_sampled": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                             c_void_p, c_int, P(ctypes.c_int64), c_int,
+                                             c_void_p, P(ctypes.c_int64), c_int, c_u64, c_u64, c_u64, c_u64, c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -351,7 +363,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -40,6 +40,14 @@ bool opt_probs_labels_tiles() { return g_probs_labels_tiles.load() != 0; }
 static std::atomic<int> g_resize_vector{1};   // (off: the generic path everywhere -- a test hook, resize.hip)
 bool opt_resize_vector() { return g_resize_vector.load() != 0; }
 
+// "fuse_sampled" (fusion_sampled.hip): 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- a test hook, like
+// SMESH_FUSE_H16=0.  -1: not set by smesh_set_option -- the environment's SMESH_FUSE_SAMPLED, read at every call, else on.
+static std::atomic<int> g_fuse_sampled{-1};
+bool opt_fuse_sampled() {
+  const int v = g_fuse_sampled.load();
+  return (v < 0 ? env_int("SMESH_FUSE_SAMPLED", 1) : v) != 0;
+}
+
 static std::atomic<int> g_group_pipeline{-1};   // -1: not decided yet (the environment, else on)
 bool opt_group_pipeline() {
   int v = g_group_pipeline.load();
@@ -352,6 +360,8 @@ int smesh_set_option(const char* name, int64_t value) {
   if (!strcmp(name, "probs_labels_tiles")) { g_probs_labels_tiles.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // resize.hip: 0 sends every class-vector image down the generic one-lane-per-element path -- same images, same labels
   if (!strcmp(name, "resize_vector")) { g_resize_vector.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  // fusion_sampled.hip: 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- same sums
+  if (!strcmp(name, "fuse_sampled")) { g_fuse_sampled.store(value != 0 ? 1 : 0); return SMESH_OK; }
   return fail(SMESH_ERR_INVALID, std::string("unknown option: ") + name);
 }
 int smesh_get_option(const char* name, int64_t* value) {
@@ -368,6 +378,7 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "confusion_wave_aggregate")) { *value = opt_confusion_wave_aggregate() ? 1 : 0; return SMESH_OK; }
   if (!strcmp(name, "probs_labels_tiles")) { *value = opt_probs_labels_tiles() ? 1 : 0; return SMESH_OK; }
   if (!strcmp(name, "resize_vector")) { *value = opt_resize_vector() ? 1 : 0; return SMESH_OK; }
+  if (!strcmp(name, "fuse_sampled")) { *value = opt_fuse_sampled() ? 1 : 0; return SMESH_OK; }
   // read-only (smesh_probs_labels.h): the largest class count the tiled path serves
   if (!strcmp(name, "probs_labels_tile_max_classes")) { *value = (int64_t)kProbsLabelsTileMaxC; return SMESH_OK; }
   // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --

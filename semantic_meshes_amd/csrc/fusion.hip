@@ -2475,6 +2475,7 @@ static bool launch_fuse_wide_list(int wide_chunks, uint32_t C, dim3 grid, hipStr
 static thread_local int g_last_fuse_slot = -1;
 static thread_local int g_last_fuse_views = 0;
 void smesh_last_fuse_instance(int* slot, int* views) { *slot = g_last_fuse_slot; *views = g_last_fuse_views; }
+void smesh_set_last_fuse_instance(int slot, int views) { g_last_fuse_slot = slot; g_last_fuse_views = views; }   // (fusion_sampled.hip: register slots, views)
 
 // `nviews` = 1, 2, 4 or 8 (smesh_aggregator_max_fused_views): views[0], views[1] ... of the same renderer in one launch.
 // `part` / `nparts`: only the triangles of smesh_fuse_part_rows(F, part, nparts) -- the queued medium triangles (fuse_mid_entries, float

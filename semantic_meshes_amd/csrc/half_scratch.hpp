@@ -17,6 +17,15 @@ constexpr uint32_t kHalfMaxClasses = 48;
 // planes of that many bytes per pixel, kHalfMode | SMESH_PROBS_F16 / _BF16 = 16-bit class vectors.
 constexpr int kHalfMode = 0x10;
 inline int half_dtype_of(int mode) { return (mode & kHalfMode) ? (mode & 0xF) : 0; }
+// kSampledMode | SMESH_PROBS_*: (w,h,C) class vectors at the network's resolution, sampled inside the fusion kernel
+// (fusion_sampled.hip, include/smesh_sampled.h); the drivers then carry a SampledSrc beside the int.
+constexpr int kSampledMode = 0x20;
+inline bool sampled_mode(int mode) { return (mode & kSampledMode) != 0; }
+struct SampledSrc {
+  int dtype;          // SMESH_PROBS_* of every image of the call
+  uint32_t w, h;      // their width and height
+  int64_t s0, s1;     // element strides of x and y (class stride 1)
+};
 
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
@@ -49,10 +58,14 @@ __device__ __forceinline__ uint32_t f16_rne(float x) {
 // Staged host images (16 bits per element) and staged weights of up to eight views, and the widened float32 image of the routes
 // k_fuse_tri_h16 does not serve.  Everything that writes or reads them is ordered on the context's main stream.  `mu` is held for a
 // whole entry point of smesh_half.h: it is taken before any other lock of the library, and by those entry points only.
+// smp_*: the same for the entry points of smesh_sampled.h -- source images staged at their own size, staged weights, and the
+// resampled (W,H,C) images of the views the sampling kernel does not serve.  `smp_mu` is held for a whole entry point of that header
+// and taken before `mu` (those entry points call the ones of smesh_half.h).
 struct HalfScratch {
-  std::mutex mu;
+  std::mutex mu, smp_mu;
   Scratch stage, w, wide;
-  void release() { stage.release(); w.release(); wide.release(); }
+  Scratch smp_stage, smp_w, smp_full;
+  void release() { stage.release(); w.release(); wide.release(); smp_stage.release(); smp_w.release(); smp_full.release(); }
 };
 
 }  // namespace smesh

@@ -71,6 +71,9 @@ int smesh_labels_expand(smesh_aggregator* a, const void* plane, int label_bytes,
 bool smesh_half_native(smesh_aggregator* a, uint64_t F);
 bool smesh_half_takes_strides(int64_t ps0, int64_t ps1);
 int smesh_half_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int probs_dtype);
+// fusion_sampled.hip: (w,h,C) class vectors sampled inside the fusion kernel (include/smesh_sampled.h)
+bool smesh_sampled_native(smesh_aggregator* a, uint64_t F);
+int smesh_sampled_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, const SampledSrc* src);
 int smesh_half_widen(smesh_aggregator* a, const void* probs, int probs_dtype, const int64_t s[3], uint64_t W, uint64_t H, const float** out,
                      int slot = 0, size_t slot_bytes = 0, int nslots = 1);
 
@@ -2321,6 +2324,7 @@ static thread_local int g_last_fuse_probs_dtype = 0;        // SMESH_PROBS_* of 
 void smesh_note_fuse(const char* kernel, const char* path) { g_last_fuse_kernel = kernel; g_last_add_path = path; g_last_fuse_probs_dtype = 0; }
 int smesh_last_fuse_probs_dtype() { return g_last_fuse_probs_dtype; }
 static void note_fuse_half(int probs_dtype) { smesh_note_fuse("k_fuse_tri_h16", "render-records"); g_last_fuse_probs_dtype = probs_dtype; }
+static void note_fuse_sampled(int probs_dtype) { smesh_note_fuse("k_fuse_tri_sampled", "render-records"); g_last_fuse_probs_dtype = probs_dtype; }
 
 // Do label views of this renderer into this aggregator take k_fuse_tri_labels (fusion_labels.hip)?  Triangle primitives in the caller's
 // face order (the kernel knows no prim_id table), Sum / Summax.  Everything else: labels expanded on the device, class-vector path.
@@ -2340,7 +2344,10 @@ static bool half_native(smesh_renderer* r, smesh_aggregator* a) { return !r->tex
 // Does the kernel that follows the raster launch of a view in this mode (fuse_rendered's `label_bytes`) read index planes the way
 // k_fuse_tri_labels does?  The tail waves of k_fuse_tri_h16 are that kernel's: they SCAN the plane of every view of the launch for a
 // queued triangle, so its raster launches take kLabelsPlaneLevel as well (no cheaper level is safe: there is no by-mask path).
+// (k_fuse_tri_sampled's tail waves are k_fuse_tri_h16's: the same level.  A sampled view only gets here where that kernel serves it.)
+static bool sampled_native(smesh_renderer* r, smesh_aggregator* a) { return !r->texels && !r->prim_id && smesh_sampled_native(a, r->F); }
 static bool scans_all_planes(smesh_renderer* r, smesh_aggregator* a, int label_bytes, uint64_t N) {
+  if (sampled_mode(label_bytes)) return sampled_native(r, a);
   if (half_dtype_of(label_bytes)) return half_native(r, a);
   return label_bytes && labels_native(r, a, N);
 }
@@ -2348,13 +2355,23 @@ static bool scans_all_planes(smesh_renderer* r, smesh_aggregator* a, int label_b
 // The fusion half of smesh_fuse_view / smesh_aggregator_add_rendered: `d_idx` is the index plane of the render
 // whose per-triangle records sit in r->side[slot].
 // (`label_bytes` 1 / 2: `probs` is no class-vector image but a dense label plane of that many bytes per pixel in DEVICE memory;
-// kHalfMode | dtype: a 16-bit class-vector image in DEVICE memory, class stride 1 -- half_scratch.hpp)
+// kHalfMode | dtype: a 16-bit class-vector image in DEVICE memory, class stride 1 -- half_scratch.hpp;
+// kSampledMode | dtype: a (w,h,C) image in DEVICE memory that `smp` describes, which k_fuse_tri_sampled serves -- the caller made sure)
 static int fuse_rendered(smesh_renderer* r, smesh_aggregator* a, int slot, const uint32_t* d_idx, const float* probs,
-                         const float* weights, int memkind, uint64_t W, uint64_t H, int64_t ps0 = 0, int64_t ps1 = 0, int label_bytes = 0) {
+                         const float* weights, int memkind, uint64_t W, uint64_t H, int64_t ps0 = 0, int64_t ps1 = 0, int label_bytes = 0,
+                         const SampledSrc* smp = nullptr) {
   DeviceCtx* ctx = r->ctx;
   const uint64_t N = W * H;
   const float* d_probs = probs;
   const float* d_w = weights;
+  if (sampled_mode(label_bytes)) {
+    if (!smp || !sampled_native(r, a)) return fail(SMESH_ERR_INVALID, "sampled view: k_fuse_tri_sampled does not serve this renderer and aggregator");
+    RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H};   // (k_fuse_tri_sampled has no medium-triangle path: mid_queue stays false)
+    rv.probs16 = probs;
+    SMESH_TRY(smesh_sampled_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, smp));
+    note_fuse_sampled(smp->dtype);
+    return SMESH_OK;
+  }
   if (const int dt16 = half_dtype_of(label_bytes)) {
     if (half_native(r, a)) {
       RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H, ps0, ps1, true};
@@ -2649,7 +2666,7 @@ int smesh_renderer_render(smesh_renderer_t* r, const smesh_camera_t* cam, uint32
 // One iteration of the driver loop (colorize_cityscapes_mesh.py:54-67): render + add, indices never leave HBM.
 // Asynchronous for DEVICE probs: they must stay valid until smesh_synchronize().
 static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const float* probs,
-                          const float* weights, int memkind, int label_bytes) {
+                          const float* weights, int memkind, int label_bytes, const SampledSrc* smp = nullptr) {
   if (!r || !a || !probs) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(check_camera(cam));
   DeviceCtx* ctx = r->ctx;
@@ -2678,7 +2695,7 @@ static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smes
   // (16-bit class vectors: k_fuse_tri_h16 follows and takes the label kernel's level, see scans_all_planes)
   const int tri_path = scans_all_planes(r, a, label_bytes, N) ? kLabelsPlaneLevel : plane_optional_level(r, a);
   SMESH_TRY(render_into(r, cam, d_idx, /*d_depth=*/nullptr, ctx->stream, slot, tri_path));
-  SMESH_TRY(fuse_rendered(r, a, slot, d_idx, probs, weights, memkind, W, H, 0, 0, label_bytes));
+  SMESH_TRY(fuse_rendered(r, a, slot, d_idx, probs, weights, memkind, W, H, 0, 0, label_bytes, smp));
   r->fused_seq++;
   return SMESH_OK;
 }
@@ -2694,8 +2711,11 @@ int smesh_fuse_view(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_came
 // as two calls).  Asynchronous like smesh_fuse_view.
 // (`label_bytes` != 0: label views -- probs[i] are dense label planes in DEVICE memory, fused by k_fuse_tri_labels; the caller has made
 // sure that labels_native() holds for every view)
+// (kSampledMode | dtype: (w,h,C) images in DEVICE memory that `smp` describes, fused by k_fuse_tri_sampled; the caller has made sure
+// that sampled_native() holds)
 static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n,
-                           const float* const* probs, const float* const* weights, int memkind, int label_bytes) {
+                           const float* const* probs, const float* const* weights, int memkind, int label_bytes,
+                           const SampledSrc* smp = nullptr) {
   if (!r || !a || (n && (!cams || !probs))) return fail(SMESH_ERR_INVALID, "NULL argument");
   for (uint64_t i = 0; i < n; i++) {
     SMESH_TRY(check_camera(&cams[i]));
@@ -2726,7 +2746,7 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     bool grouped = !raster_pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0 && r->V != 0 && gn >= 2;
     for (int v = 0; v < gn && grouped; v++) grouped = queues_fit_group(cams[i + v].width, cams[i + v].height);
     if ((!pairable && !grouped) || i + 1 >= n) {
-      SMESH_TRY(fuse_view_impl(r, a, &cams[i], probs[i], weights ? weights[i] : nullptr, memkind, label_bytes));
+      SMESH_TRY(fuse_view_impl(r, a, &cams[i], probs[i], weights ? weights[i] : nullptr, memkind, label_bytes, smp));
       i += 1;
       continue;
     }
@@ -2807,7 +2827,7 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     for (int j = 0; j < gn && !pairable && !texel_multi; j++) {   // class counts beyond k_fuse_tri, foreign primitive counts
       const uint64_t k = i + (uint64_t)j;
       SMESH_TRY(fuse_rendered(r, a, base + j, static_cast<const uint32_t*>(r->fused[base + j].ptr), probs[k], weights ? weights[k] : nullptr,
-                              SMESH_MEM_DEVICE, cams[k].width, cams[k].height, 0, 0, label_bytes));
+                              SMESH_MEM_DEVICE, cams[k].width, cams[k].height, 0, 0, label_bytes, smp));
     }
     // the fusion launches of a group are back to back: one timed region for all of them (smesh_profile_*: a HIP event pair around a
     // single launch adds the dispatch latency that back-to-back launches hide)
@@ -2827,16 +2847,18 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
                                weights ? weights[k] : nullptr, cams[k].width, cams[k].height, 0, 0, true};
           rv[v].no_big = no_big_possible(r, &cams[k]);
           rv[v].fine = box_extent_bound(r->bounds, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
-          if (half_dtype_of(label_bytes)) { rv[v].probs16 = probs[k]; rv[v].probs = nullptr; }
+          if (half_dtype_of(label_bytes) || sampled_mode(label_bytes)) { rv[v].probs16 = probs[k]; rv[v].probs = nullptr; }
           else if (label_bytes) { rv[v].labels = probs[k]; rv[v].probs = nullptr; }
         }
-        if (half_dtype_of(label_bytes)) SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, rv, nv, half_dtype_of(label_bytes)));
+        if (sampled_mode(label_bytes)) SMESH_TRY(smesh_sampled_fuse_triangles(a, r->F, r->big_capacity, rv, nv, smp));
+        else if (half_dtype_of(label_bytes)) SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, rv, nv, half_dtype_of(label_bytes)));
         else if (label_bytes) SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, label_bytes));
         else SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv));
         j += nv;
       }
     }
-    if (pairable && half_dtype_of(label_bytes)) note_fuse_half(half_dtype_of(label_bytes));
+    if (pairable && sampled_mode(label_bytes)) note_fuse_sampled(smp->dtype);
+    else if (pairable && half_dtype_of(label_bytes)) note_fuse_half(half_dtype_of(label_bytes));
     else if (pairable) smesh_note_fuse(label_bytes ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
     if (grouped && group_pipeline) SMESH_HIP(hipEventRecord(r->ev_bank_consumed[base / kMaxGroup], ctx->stream));
     r->fused_seq += (uint64_t)gn;
@@ -2929,6 +2951,42 @@ int smesh_renderer_add_rendered_half(smesh_aggregator* a, smesh_renderer* r, con
   const int64_t C = (int64_t)smesh_aggregator_classes(a);
   if (ps0 == (int64_t)H * C && ps1 == C) ps0 = ps1 = 0;   // (the dense image)
   SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(probs), weights, SMESH_MEM_DEVICE, W, H, ps0, ps1, kHalfMode | probs_dtype));
+  *done = 1;
+  return SMESH_OK;
+}
+
+// ---- sampled class-vector views (include/smesh_sampled.h; the entry points are fusion_sampled.hip's) ---------------------------------
+bool smesh_renderer_sampled_native(smesh_renderer* r, smesh_aggregator* a) {
+  std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+  return sampled_native(r, a);
+}
+
+// smesh_fuse_views for `n` views whose (w,h,C) images (`src`: dtype, size, strides) and (W,H) weights are in DEVICE memory and which
+// k_fuse_tri_sampled serves (smesh_renderer_sampled_native): the group pipeline and the eight-view grouping of smesh_fuse_views.
+int smesh_renderer_fuse_views_sampled(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
+                                      const float* const* weights, const SampledSrc* src) {
+  if (!src) return fail(SMESH_ERR_INVALID, "NULL argument");
+  return fuse_views_impl(r, a, cams, n, reinterpret_cast<const float* const*>(probs), weights, SMESH_MEM_DEVICE, kSampledMode | src->dtype, src);
+}
+
+// smesh_renderer_add_rendered_half for a (w,h,C) image in DEVICE memory: *done = 1 if `idx_dev` is the untouched output of one of r's
+// latest smesh_renderer_render_device() calls and k_fuse_tri_sampled fused the view from that render's records; *done = 0: nothing
+// happened.
+int smesh_renderer_add_rendered_sampled(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* probs, const SampledSrc* src,
+                                        const float* weights, uint64_t W, uint64_t H, int* done) {
+  *done = 0;
+  DeviceCtx* ctx = r->ctx;
+  if (!src || smesh_aggregator_ctx(a) != ctx || W == 0 || H == 0) return SMESH_OK;
+  std::lock_guard<std::mutex> g(r->mu);
+  std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  SMESH_TRY(smesh_aggregator_join_exchange(a));
+  int side = -1;
+  for (int sd = 0; sd < kRecordSides; sd++)
+    if (idx_dev == r->last_idx[sd] && W == r->last_W[sd] && H == r->last_H[sd]) side = sd;
+  if (side < 0 || !sampled_native(r, a)) return SMESH_OK;
+  SMESH_HIP(hipSetDevice(ctx->device));
+  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(probs), weights, SMESH_MEM_DEVICE, W, H, 0, 0, kSampledMode | src->dtype, src));
   *done = 1;
   return SMESH_OK;
 }

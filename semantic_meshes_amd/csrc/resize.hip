@@ -4,11 +4,12 @@
 // Reference: eval-scannet/eval_scannet.py:221-236 (the (480,640,40) prediction resized to (968,1296,40) by tf.image.resize before
 // it is scored and fused), python/scripts/colorize_cityscapes_mesh.py:42 (multi_scale(predictor, [0.5])).
 //
-// The rule is evaluated in ONE place, axis_of() and blend() below: the source coordinates in double, the three lerps
+// The rule is evaluated in ONE place, axis_of() and blend() of resize_rule.hpp: the source coordinates in double, the three lerps
 // in float32, every operation rounded separately (the library is built with -ffp-contract=off).  No result depends on the path, the
 // dtype pair's load width or the launch shape.
 #include "confusion.hpp"
 #include "half_scratch.hpp"
+#include "resize_rule.hpp"
 
 #include <cmath>
 
@@ -48,26 +49,7 @@ struct RsArgs {
   int use_sum;
 };
 
-// One axis of the rule: output coordinate X of N, input size n, s = (double)n / (double)N.
-struct Axis {
-  uint32_t i0, i1;
-  float f;
-};
-__device__ __forceinline__ Axis axis_of(uint32_t X, double s, uint32_t n) {
-  double t = ((double)X + 0.5) * s - 0.5;
-  t = fmin(fmax(t, 0.0), (double)(n - 1u));
-  const double fl = floor(t);
-  Axis a;
-  a.i0 = (uint32_t)fl;                                  // in [0, n - 1]: t is clamped
-  a.i1 = a.i0 + 1u < n ? a.i0 + 1u : n - 1u;
-  a.f = (float)(t - fl);
-  return a;
-}
-
-__device__ __forceinline__ float lerp1(float a, float b, float f) { return f == 0.0f ? a : a + (b - a) * f; }
-__device__ __forceinline__ float blend(float a00, float a10, float a01, float a11, float fx, float fy) {
-  return lerp1(lerp1(a00, a10, fx), lerp1(a01, a11, fx), fy);
-}
+// (Axis, axis_of(), lerp1() and blend(): resize_rule.hpp, shared with fusion_sampled.hip)
 
 __device__ __forceinline__ float load_elem(const void* p, int dt, uint64_t off) {
   if (dt == SMESH_PROBS_F32) return static_cast<const float*>(p)[off];

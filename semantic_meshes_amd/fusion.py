@@ -138,6 +138,13 @@ def _flush_device(device=None):
 _lib._flush_hooks.append(_flush_device)
 
 
+class _PodCamera:
+    """The camera of a render() plane that has not been rasterised yet, as `_fuse_views_sampled` reads cameras."""
+
+    def __init__(self, pod, W, H):
+        self._pod, self.resolution = pod, (W, H)
+
+
 class _MeshAggregator:
     def __init__(self, primitives, classes, kind, images_equal_weight, device):
         self.primitives, self.classes = int(primitives), int(classes)
@@ -274,6 +281,104 @@ class _MeshAggregator:
             return probs_image
         return _resize_device(probs_image, tuple(size), None, probs_dtype, mode, self.device, hold=self._hold)
 
+    # ---- sample_in_kernel=True (include/smesh_sampled.h): the small image goes to the library as it is ----------------------------
+    @staticmethod
+    def _sampling_mode(resize, sample_in_kernel, what):
+        """The SMESH_RESIZE_* code of a call with `sample_in_kernel=True`, None for a call without it."""
+        from .resize import resize_mode
+        mode = resize_mode(resize)
+        if not sample_in_kernel:
+            return None
+        if mode is None:
+            raise ValueError('%s: sample_in_kernel=True is only meaningful together with resize="bilinear"' % what)
+        return mode
+
+    def _describe_sampled(self, probs_image, probs_dtype, streams, what="probs image"):
+        """`_describe_probs` of a (w,h,C) image for the sampled entry points: the class count is the aggregator's."""
+        from .evaluation import _describe_probs
+        d = _describe_probs(probs_image, probs_dtype, self.device, streams, what)
+        if d[2][2] != self.classes:
+            raise ValueError("%s has %d classes, aggregator was built for %d" % (what, d[2][2], self.classes))
+        if d[2][0] < 1 or d[2][1] < 1:
+            raise ValueError("an empty %s %s cannot be resampled" % (what, d[2][:2]))
+        return d
+
+    def _fuse_views_sampled(self, renderer, cameras, probs_images, weights_images, probs_dtype, mode, what):
+        """`fuse_views(..., resize="bilinear", sample_in_kernel=True)`: every image is checked first, then consecutive images of one
+        size, layout, dtype and memory go to `smesh_fuse_views_sampled` as one batch -- the library groups them by eight."""
+        cameras, probs_images = list(cameras), list(probs_images)
+        wts = None if weights_images is None else list(weights_images)
+        n = len(cameras)
+        if len(probs_images) != n or (wts is not None and len(wts) != n):
+            raise ValueError("%s needs one probs image (and one weights image or None) per camera" % what)
+        streams, desc = [], []
+        for i, cam in enumerate(cameras):
+            W, H = cam.resolution
+            d = self._describe_sampled(probs_images[i], probs_dtype, streams, "probs image %d" % i)
+            dw = None
+            if wts is not None and wts[i] is not None:
+                dw = self._describe_weights(wts[i], streams)
+                if dw[2] != (W, H) or dw[3] != (H, 1) or dw[1] != d[1]:
+                    raise ValueError("weights image %d must be contiguous float32 (W,H) in the same memory as probs" % i)
+            elif wts is not None:
+                raise ValueError("%s: weights for every view or for none" % what)
+            desc.append((d, dw))
+        lo = 0
+        while lo < n:
+            first = desc[lo][0]
+            hi = lo + 1
+            while hi < n and desc[hi][0][1:5] == first[1:5]:
+                hi += 1
+            m = hi - lo
+            pods = (_lib.CameraPOD * m)(*[cam._pod for cam in cameras[lo:hi]])
+            pptr = (ctypes.c_void_p * m)(*[d[0] for d, _ in desc[lo:hi]])
+            wptr = None if wts is None else (ctypes.c_void_p * m)(*[dw[0] for _, dw in desc[lo:hi]])
+            _lib.check(_lib.lib().smesh_fuse_views_sampled(renderer._h, self._h, pods, m, pptr, first[3], _c64(first[4]), first[2][0], first[2][1],
+                                                           wptr, first[1], mode))
+            lo = hi
+        release_to(self.device, streams)
+        self._hold([d[5] for d, _ in desc if d[1] == _lib.MEM_DEVICE] + [dw[4] for d, dw in desc if dw is not None and d[1] == _lib.MEM_DEVICE])
+
+    def _add_sampled(self, primitive_image, probs_image, weights_image, probs_dtype, mode):
+        """`add(..., resize="bilinear", sample_in_kernel=True)`: the views already deferred are handed over first (the order of
+        additions stays the caller's), then this view is one library call -- a render() plane that has not been rasterised yet is
+        never produced (`smesh_fuse_view_sampled` with its camera), any other index image goes to `smesh_aggregator_add_sampled`."""
+        streams = []
+        pp, pmem, (w, h, C), code, pstr, k1 = self._describe_sampled(probs_image, probs_dtype, streams)
+        wdesc = None if weights_image is None else self._describe_weights(weights_image, streams)
+        ishape = tuple(getattr(primitive_image, "shape", None) or np.shape(primitive_image))
+        if len(ishape) != 2 or (wdesc is not None and wdesc[2] != ishape):
+            raise ValueError("Primitive image %s and weights image %s must have the same width and height"
+                             % (ishape, None if wdesc is None else wdesc[2]))
+        lazy = getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
+        if lazy and (wdesc is None or (wdesc[3] == (ishape[1], 1) and wdesc[1] == pmem)):
+            pend = primitive_image._pending
+            if pend.W and pend.H:      # (an empty plane adds nothing and hands nothing over, like every other empty-image return)
+                self.flush()
+                _lib.check(_lib.lib().smesh_fuse_view_sampled(pend.renderer._h, self._handle, ctypes.byref(pend.pod), ctypes.c_void_p(pp), code,
+                                                              _c64(pstr), w, h, None if wdesc is None else ctypes.c_void_p(wdesc[0]), pmem, mode))
+                release_to(self.device, streams)
+                self._hold([k1 if pmem == _lib.MEM_DEVICE else None, wdesc[4] if (wdesc is not None and wdesc[1] == _lib.MEM_DEVICE) else None])
+            return
+        ip, imem, ishape, idt, istr, k0 = describe(primitive_image, 2, "primitive image", self.device, streams)
+        if idt not in _IDX_CODES:
+            raise ValueError("primitive image dtype must be one of uint32/int32/uint64/int64, got %s" % idt)
+        W, H = ishape
+        if W == 0 or H == 0:
+            return
+        rb = getattr(primitive_image, "_rendered_by", None)
+        if not (rb is not None and not primitive_image._exported and getattr(rb, "_h", None) is not None and rb._h.value
+                and rb.device == self.device):
+            rb = None
+        wp, wmem, wstr, k2 = (None, _lib.MEM_HOST, None, None) if wdesc is None else (wdesc[0], wdesc[1], wdesc[3], wdesc[4])
+        _lib.check(_lib.lib().smesh_aggregator_add_sampled(
+            self._h, None if rb is None else rb._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
+            ctypes.c_void_p(pp), code, _c64(pstr), pmem,
+            None if wp is None else ctypes.c_void_p(wp), None if wstr is None else _c64(wstr), wmem, w, h, W, H, mode))
+        release_to(self.device, streams)
+        self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if pmem == _lib.MEM_DEVICE else None,
+                    k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
+
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
         self._pending = []      # (views nobody can ask the result of any more)
@@ -287,21 +392,28 @@ class _MeshAggregator:
             except Exception:
                 pass
 
-    def add(self, primitive_image, probs_image, weights_image=None, probs_dtype=None, resize=None):
+    def add(self, primitive_image, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False):
         """Fuse one view: `primitive_image` (W,H) of uint32/int32/uint64/int64, `probs_image` (W,H,C) float32, float16 or bfloat16,
         optional `weights_image` (W,H) float32; host numpy or device arrays, any non-negative strides.  A 16-bit image gives what
         its exactly widened float32 copy gives, without that copy (include/smesh_half.h); `probs_dtype="bfloat16"` says that a
         uint16 array holds bfloat16 bits (see `probs_code`), None infers the dtype from the array.  `resize="bilinear"`: a
         `probs_image` (w,h,C) at the network's resolution is resampled to the index image's (W,H) on the device first (`_resampled`,
-        DESIGN.md 3.8); the weights image stays (W,H).  With `resize=None` such an image is refused."""
+        DESIGN.md 3.8); the weights image stays (W,H).  With `resize=None` such an image is refused.
+        `sample_in_kernel=True` (with `resize="bilinear"` only): the small image is not resampled beforehand -- the fusion kernel
+        samples it for the visible pixels (include/smesh_sampled.h), the same sums, and no (W,H,C) image exists.  The
+        caller-owned small image cannot wait for a deferred group, so such an add() first hands over the views already pending and
+        is then one library call and one fusion launch of its own; `fuse_views` with the keyword is the fast form."""
         from .resize import resize_mode
         mode = resize_mode(resize)
+        smode = self._sampling_mode(resize, sample_in_kernel, "add")
         if type(primitive_image).__name__ == "PyCapsule":
             # render() in capsule mode (the reference's return type) handed straight back, as python/scripts/colorize_cityscapes_mesh.py:65-67 does
             from . import dlpack
             own = dlpack.own_capsule_owner(primitive_image)
             if own is not None:
                 primitive_image = own
+        if smode is not None:
+            return self._add_sampled(primitive_image, probs_image, weights_image, probs_dtype, smode)
         if mode is not None:
             tshape = tuple(getattr(primitive_image, "shape", None) or np.shape(primitive_image))
             if len(tshape) == 2:      # (anything else is refused below, as without the keyword)
@@ -534,20 +646,35 @@ class _MeshAggregator:
         if first[1] == _lib.MEM_DEVICE:
             self._hold([d[4] for d, _ in desc] + [dw[4] for _, dw in desc if dw is not None])
 
-    def add_many(self, primitive_images, probs_images, weights_images=None, probs_dtype=None, resize=None):
+    def add_many(self, primitive_images, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False):
         """`add()` for a batch of views, in order (new functionality; the reference's loop adds one image per call).  Same sums as
         the calls one by one -- per accumulator row the same float32 additions in the same order -- but device-resident dense
         uint32 / int32 index images with dense float32 device class vectors, all of one size, share their kernel launches in groups
         of up to eight (`smesh_aggregator_add_many`).  Anything else in the batch is added image by image.  `resize="bilinear"`: see
-        add(); the batch is worked through in chunks of eight views, so at most eight resampled images are alive at once."""
+        add(); the batch is worked through in chunks of eight views, so at most eight resampled images are alive at once.
+        `sample_in_kernel=True`: see add(); render() planes that have not been rasterised yet go to the library as whole batches
+        (`fuse_views` with their cameras), anything else view by view."""
         from .resize import resize_mode
         mode = resize_mode(resize)
+        smode = self._sampling_mode(resize, sample_in_kernel, "add_many")
         prims, probs = list(primitive_images), list(probs_images)
         wts = None if weights_images is None else list(weights_images)
         n = len(prims)
         if len(probs) != n or (wts is not None and len(wts) != n):
             raise ValueError("add_many needs one probs image (and one weights image) per primitive image")
         if n == 0:
+            return
+        if smode is not None:
+            lazy = [getattr(p, "unrun", False) and p._which == 0 and p.device == self.device and p._pending.W and p._pending.H for p in prims]
+            if all(lazy) and len({id(p._pending.renderer) for p in prims}) == 1 and (wts is None or all(x is not None for x in wts)):
+                cams = [_PodCamera(p._pending.pod, p._pending.W, p._pending.H) for p in prims]
+                return self._fuse_views_sampled(prims[0]._pending.renderer, cams, probs, wts, probs_dtype, smode, "add_many")
+            streams = []
+            for i in range(n):      # (every image is checked before the first one is added)
+                self._describe_sampled(probs[i], probs_dtype, streams, "probs image %d" % i)
+            release_to(self.device, streams)
+            for i in range(n):
+                self._add_sampled(prims[i], probs[i], None if wts is None else wts[i], probs_dtype, smode)
             return
         if mode is not None:
             for lo in range(0, n, GROUP_VIEWS):
@@ -703,11 +830,16 @@ class _MeshAggregator:
         """`ModelAggregator::renderer()` (Mesh.h:124-129): snapshot of the fused annotations for image gathers."""
         return ModelRenderer(self)
 
-    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None):
+    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False):
         """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
         float32, float16 or bfloat16 (see add()); with `resize="bilinear"` any (w,h,C) image add() takes, resampled to the camera's
-        resolution on the device first."""
+        resolution on the device first -- or, with `sample_in_kernel=True`, sampled inside the fusion kernel (see add(); one library
+        call per view, after the views already deferred)."""
         from .resize import resize_mode
+        smode = self._sampling_mode(resize, sample_in_kernel, "fuse_view")
+        if smode is not None:
+            return self._fuse_views_sampled(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
+                                            probs_dtype, smode, "fuse_view")
         W, H = camera.resolution
         probs_image = self._resampled(probs_image, (W, H), resize_mode(resize), probs_dtype)
         dcode = None
@@ -777,16 +909,21 @@ class _MeshAggregator:
         return (pods, n, pptr, (None if weights_images is None else wptr), (mem if mem is not None else _lib.MEM_HOST), keep, streams,
                 _lib.PROBS_F32 if code is None else code)
 
-    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None):
+    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
         accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
         have one dtype: float32, float16 or bfloat16 (see add()).  `resize="bilinear"`: images at the network's resolution are
         resampled to their camera's on the device (see add()); when any image of the batch needs that, the batch is worked through in
         chunks of eight views -- the views of a fusion launch -- so at most eight resampled images are alive at once.  Same views in
-        the same order: the same sums."""
+        the same order: the same sums.  `sample_in_kernel=True` (with `resize="bilinear"`): the small images go to the library as
+        they are, as one batch; the fusion kernel samples them for the visible pixels (include/smesh_sampled.h) -- the same sums,
+        no (W,H,C) image anywhere.  This is the fast form of the keyword."""
         from .resize import image_size, resize_mode
         mode = resize_mode(resize)
+        smode = self._sampling_mode(resize, sample_in_kernel, "fuse_views")
+        if smode is not None:
+            return self._fuse_views_sampled(renderer, cameras, probs_images, weights_images, probs_dtype, smode, "fuse_views")
         if mode is not None:
             cameras, probs_images = list(cameras), list(probs_images)
             wts = None if weights_images is None else list(weights_images)
