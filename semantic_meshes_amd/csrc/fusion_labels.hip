@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "labels_scratch.hpp"
 #include "../../include/smesh_labels.h"
+#include "../../include/smesh_label_prep.h"
 
 #include <algorithm>
 #include <cmath>
@@ -412,9 +413,28 @@ bool plane_in_place(int dt, const int64_t* strides, int mem, uint64_t W, uint64_
 // The dense narrow plane of one label image, in device memory: the image itself where it is one already (dense uint8 / uint16 on the
 // device: the kernels treat label >= C as don't-care), else slot `slot` of the plane scratch (`slot_bytes` apart), filled on the main
 // stream -- a host image is staged first (*staged = true: the caller waits for the copies before it returns).
+// `prep` (smesh_label_prep.h): the image is (prep->w, prep->h) and goes through `map_dev` (the call's map in device memory, or null):
+// k_labels_prepare writes the plane -- always into the scratch, never in place --, a host image is staged at its own size and span.
 int narrow_plane(DeviceCtx* ctx, LabelScratch& ls, int slot, size_t slot_bytes, size_t stage_bytes, const void* src, int dt, const int64_t* strides,
-                 int mem, uint64_t W, uint64_t H, uint32_t C, const void** plane, int* label_bytes, bool* staged) {
+                 int mem, uint64_t W, uint64_t H, uint32_t C, const void** plane, int* label_bytes, bool* staged,
+                 const LabelPrep* prep = nullptr, const int32_t* map_dev = nullptr) {
   const uint64_t N = W * H;
+  if (prep) {
+    const int64_t own[2] = {(int64_t)prep->h, 1};
+    const int64_t* ps = strides ? strides : own;
+    *label_bytes = C <= 255u ? 1 : 2;
+    char* dst = static_cast<char*>(ls.plane.ptr) + (size_t)slot * slot_bytes;
+    if (mem == SMESH_MEM_HOST) {
+      *staged = true;
+      const size_t span = (1 + (prep->w - 1) * (uint64_t)ps[0] + (prep->h - 1) * (uint64_t)ps[1]) * label_itemsize(dt);
+      char* stage = static_cast<char*>(ls.stage.ptr) + (size_t)slot * stage_bytes;
+      SMESH_HIP(hipMemcpyAsync(stage, src, span, hipMemcpyHostToDevice, ctx->stream));
+      src = stage;
+    }
+    SMESH_TRY(smesh_label_prep_launch(ctx, src, dt, ps, prep->w, prep->h, map_dev, prep->map_len, C, dst, *label_bytes, W, H));
+    *plane = dst;
+    return SMESH_OK;
+  }
   const int64_t dense[2] = {(int64_t)H, 1};
   const int64_t* s = strides ? strides : dense;
   const bool is_dense = (s[0] == (int64_t)H || W == 1) && (s[1] == 1 || H == 1);
@@ -446,6 +466,18 @@ size_t stage_span_bytes(int dt, const int64_t* strides, uint64_t W, uint64_t H) 
   const int64_t dense[2] = {(int64_t)H, 1};
   const int64_t* s = strides ? strides : dense;
   return ((1 + (W - 1) * (uint64_t)s[0] + (H - 1) * (uint64_t)s[1]) * label_itemsize(dt) + 255) & ~(size_t)255;
+}
+
+// The map of a prepared call in device memory: itself, or its copy in the aggregator's scratch (a host map: *staged = true).
+int stage_map(DeviceCtx* ctx, LabelScratch& ls, const LabelPrep* prep, const int32_t** map_dev, bool* staged) {
+  *map_dev = nullptr;
+  if (!prep || !prep->map) return SMESH_OK;
+  if (prep->map_mem == SMESH_MEM_DEVICE) { *map_dev = prep->map; return SMESH_OK; }
+  SMESH_TRY(ls.map.reserve(prep->map_len * 4));
+  SMESH_HIP(hipMemcpyAsync(ls.map.ptr, prep->map, prep->map_len * 4, hipMemcpyHostToDevice, ctx->stream));
+  *map_dev = static_cast<const int32_t*>(ls.map.ptr);
+  *staged = true;
+  return SMESH_OK;
 }
 
 }  // namespace
@@ -533,11 +565,11 @@ int smesh_labels_expand(smesh_aggregator* a, const void* plane, int label_bytes,
   return SMESH_OK;
 }
 
-// ---- include/smesh_labels.h -----------------------------------------------------------------------------------------------------
-extern "C" {
-
-int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
-                            int label_dtype, const int64_t label_strides[2], const float* const* weights, int memkind) {
+// ---- the entry points, with and without preparation ------------------------------------------------------------------------------
+// `prep` null: smesh_labels.h; else smesh_label_prep.h -- the same call from narrow_plane() on.
+static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
+                                  int label_dtype, const int64_t label_strides[2], const float* const* weights, int memkind,
+                                  const LabelPrep* prep) {
   if (!r || !a || (n && (!cams || !labels))) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(check_label_args(label_dtype, label_strides));
   if (memkind != SMESH_MEM_HOST && memkind != SMESH_MEM_DEVICE) return fail(SMESH_ERR_INVALID, "bad memory kind");
@@ -551,6 +583,11 @@ int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const sm
   uint32_t C;
   smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
   SMESH_TRY(check_label_classes(C));
+  if (prep) {
+    for (uint64_t i = 0; i < n; i++) SMESH_TRY(smesh_label_prep_check(label_dtype, label_strides, memkind, *prep, cams[i].width, cams[i].height, C));
+  }
+  const int32_t* map_dev = nullptr;
+  bool map_staged = false;
   LabelScratch& ls = smesh_aggregator_label_scratch(a);
   std::lock_guard<std::mutex> g(ls.mu);
   // groups of up to eight views: their planes (and staged host images and weights) share the scratch, which the next group's copies
@@ -561,7 +598,8 @@ int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const sm
     for (int v = 0; v < m; v++) {
       const uint64_t N = cams[i + v].width * cams[i + v].height;
       slot_bytes = std::max<size_t>(slot_bytes, (N * 2 + 255) & ~(size_t)255);
-      stage_bytes = std::max(stage_bytes, stage_span_bytes(label_dtype, label_strides, cams[i + v].width, cams[i + v].height));
+      stage_bytes = std::max(stage_bytes, prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h)
+                                                  : stage_span_bytes(label_dtype, label_strides, cams[i + v].width, cams[i + v].height));
       w_bytes = std::max<size_t>(w_bytes, (N * 4 + 255) & ~(size_t)255);
     }
     const void* planes[kGroup];
@@ -571,7 +609,11 @@ int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const sm
     {
       std::lock_guard<std::recursive_mutex> lock(ctx->mu);
       SMESH_HIP(hipSetDevice(ctx->device));
-      bool in_place = true;   // nothing to narrow: no plane scratch
+      if (i == 0) {
+        SMESH_TRY(stage_map(ctx, ls, prep, &map_dev, &map_staged));
+        staged = map_staged;
+      }
+      bool in_place = !prep;   // nothing to narrow: no plane scratch (a prepared plane is always scratch)
       for (int v = 0; v < m; v++) in_place = in_place && plane_in_place(label_dtype, label_strides, memkind, cams[i + v].width, cams[i + v].height);
       if (!in_place) SMESH_TRY(ls.plane.reserve(slot_bytes * (size_t)m));
       if (memkind == SMESH_MEM_HOST) {
@@ -581,7 +623,7 @@ int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const sm
       for (int v = 0; v < m; v++) {
         const uint64_t W = cams[i + v].width, H = cams[i + v].height;
         SMESH_TRY(narrow_plane(ctx, ls, v, slot_bytes, stage_bytes, labels[i + v], label_dtype, label_strides, memkind, W, H, C, &planes[v],
-                               &label_bytes, &staged));
+                               &label_bytes, &staged, prep, map_dev));
         wts[v] = weights ? weights[i + v] : nullptr;
         if (wts[v] && memkind == SMESH_MEM_HOST) {
           float* d = reinterpret_cast<float*>(static_cast<char*>(ls.w.ptr) + (size_t)v * w_bytes);
@@ -597,26 +639,24 @@ int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const sm
   return SMESH_OK;
 }
 
-int smesh_fuse_view_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const void* labels, int label_dtype,
-                           const int64_t label_strides[2], const float* weights, int memkind) {
-  if (!cam) return fail(SMESH_ERR_INVALID, "NULL argument");
-  return smesh_fuse_views_labels(r, a, cam, 1, &labels, label_dtype, label_strides, weights ? &weights : nullptr, memkind);
-}
-
-int smesh_aggregator_add_labels(smesh_aggregator_t* a, smesh_renderer_t* r, const void* indices, int idx_dtype, const int64_t idx_strides[2],
-                                int idx_mem, const void* labels, int label_dtype, const int64_t label_strides[2], int label_mem,
-                                const float* weights, const int64_t w_strides[2], int w_mem, uint64_t W, uint64_t H) {
+static int add_labels_impl(smesh_aggregator_t* a, smesh_renderer_t* r, const void* indices, int idx_dtype, const int64_t idx_strides[2],
+                           int idx_mem, const void* labels, int label_dtype, const int64_t label_strides[2], int label_mem,
+                           const float* weights, const int64_t w_strides[2], int w_mem, uint64_t W, uint64_t H, const LabelPrep* prep) {
   if (!a || !indices || !labels) return fail(SMESH_ERR_INVALID, "NULL argument");
   if (idx_dtype < 0 || idx_dtype > 3) return fail(SMESH_ERR_INVALID, "bad index dtype");
   SMESH_TRY(check_label_args(label_dtype, label_strides));
   if ((idx_strides && (idx_strides[0] < 0 || idx_strides[1] < 0)) || (weights && w_strides && (w_strides[0] < 0 || w_strides[1] < 0)))
     return fail(SMESH_ERR_INVALID, "negative strides are not supported");
+  uint32_t C;
+  smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
+  if (prep) {
+    if (label_mem != SMESH_MEM_HOST && label_mem != SMESH_MEM_DEVICE) return fail(SMESH_ERR_INVALID, "bad memory kind");
+    SMESH_TRY(smesh_label_prep_check(label_dtype, label_strides, label_mem, *prep, W, H, C));
+  }
   if (W == 0 || H == 0) return SMESH_OK;
   if (W > 65536 || H > 65536 || W * H >= 0x7FFFFFFFull / 4) return fail(SMESH_ERR_INVALID, "image too large");
   DeviceCtx* ctx = smesh_aggregator_ctx(a);
   if (r && smesh_renderer_ctx(r) != ctx) r = nullptr;
-  uint32_t C;
-  smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
   const uint64_t N = W * H;
   const int64_t dense[2] = {(int64_t)H, 1};
   const int64_t* is = idx_strides ? idx_strides : dense;
@@ -633,9 +673,13 @@ int smesh_aggregator_add_labels(smesh_aggregator_t* a, smesh_renderer_t* r, cons
   {
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     SMESH_HIP(hipSetDevice(ctx->device));
-    if (!plane_in_place(label_dtype, label_strides, label_mem, W, H)) SMESH_TRY(ls.plane.reserve((N * 2 + 255) & ~(size_t)255));
-    if (label_mem == SMESH_MEM_HOST) SMESH_TRY(ls.stage.reserve(stage_span_bytes(label_dtype, label_strides, W, H)));
-    SMESH_TRY(narrow_plane(ctx, ls, 0, (N * 2 + 255) & ~(size_t)255, 0, labels, label_dtype, label_strides, label_mem, W, H, C, &plane, &label_bytes, &staged));
+    const int32_t* map_dev = nullptr;
+    SMESH_TRY(stage_map(ctx, ls, prep, &map_dev, &staged));
+    if (prep || !plane_in_place(label_dtype, label_strides, label_mem, W, H)) SMESH_TRY(ls.plane.reserve((N * 2 + 255) & ~(size_t)255));
+    if (label_mem == SMESH_MEM_HOST)
+      SMESH_TRY(ls.stage.reserve(prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h) : stage_span_bytes(label_dtype, label_strides, W, H)));
+    SMESH_TRY(narrow_plane(ctx, ls, 0, (N * 2 + 255) & ~(size_t)255, 0, labels, label_dtype, label_strides, label_mem, W, H, C, &plane, &label_bytes, &staged,
+                           prep, map_dev));
     if (rendered && weights && w_mem == SMESH_MEM_HOST) {   // (the triangle-order kernel wants the weights where the plane is)
       SMESH_TRY(ls.w.reserve(N * 4));
       SMESH_HIP(hipMemcpyAsync(ls.w.ptr, weights, N * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -658,6 +702,52 @@ int smesh_aggregator_add_labels(smesh_aggregator_t* a, smesh_renderer_t* r, cons
   }
   const int64_t ps[3] = {(int64_t)(H * C), (int64_t)C, 1};
   return smesh_aggregator_add_async(a, indices, idx_dtype, is, idx_mem, probs, ps, SMESH_MEM_DEVICE, weights, ws, w_mem, W, H);
+}
+
+// ---- include/smesh_labels.h, include/smesh_label_prep.h -----------------------------------------------------------------------
+extern "C" {
+
+int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
+                            int label_dtype, const int64_t label_strides[2], const float* const* weights, int memkind) {
+  return fuse_views_labels_impl(r, a, cams, n, labels, label_dtype, label_strides, weights, memkind, nullptr);
+}
+
+int smesh_fuse_view_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const void* labels, int label_dtype,
+                           const int64_t label_strides[2], const float* weights, int memkind) {
+  if (!cam) return fail(SMESH_ERR_INVALID, "NULL argument");
+  return fuse_views_labels_impl(r, a, cam, 1, &labels, label_dtype, label_strides, weights ? &weights : nullptr, memkind, nullptr);
+}
+
+int smesh_aggregator_add_labels(smesh_aggregator_t* a, smesh_renderer_t* r, const void* indices, int idx_dtype, const int64_t idx_strides[2],
+                                int idx_mem, const void* labels, int label_dtype, const int64_t label_strides[2], int label_mem,
+                                const float* weights, const int64_t w_strides[2], int w_mem, uint64_t W, uint64_t H) {
+  return add_labels_impl(a, r, indices, idx_dtype, idx_strides, idx_mem, labels, label_dtype, label_strides, label_mem, weights, w_strides, w_mem, W, H,
+                         nullptr);
+}
+
+int smesh_fuse_views_labels_prepared(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
+                                     int label_dtype, const int64_t label_strides[2], const float* const* weights, int memkind, uint64_t w,
+                                     uint64_t h, const int32_t* map, uint64_t map_len, int map_memkind) {
+  const LabelPrep prep{w, h, map, map_len, map_memkind};
+  return fuse_views_labels_impl(r, a, cams, n, labels, label_dtype, label_strides, weights, memkind, &prep);
+}
+
+int smesh_fuse_view_labels_prepared(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const void* labels, int label_dtype,
+                                    const int64_t label_strides[2], const float* weights, int memkind, uint64_t w, uint64_t h,
+                                    const int32_t* map, uint64_t map_len, int map_memkind) {
+  if (!cam) return fail(SMESH_ERR_INVALID, "NULL argument");
+  const LabelPrep prep{w, h, map, map_len, map_memkind};
+  return fuse_views_labels_impl(r, a, cam, 1, &labels, label_dtype, label_strides, weights ? &weights : nullptr, memkind, &prep);
+}
+
+int smesh_aggregator_add_labels_prepared(smesh_aggregator_t* a, smesh_renderer_t* r, const void* indices, int idx_dtype,
+                                         const int64_t idx_strides[2], int idx_mem, const void* labels, int label_dtype,
+                                         const int64_t label_strides[2], int label_mem, const float* weights, const int64_t w_strides[2],
+                                         int w_mem, uint64_t W, uint64_t H, uint64_t w, uint64_t h, const int32_t* map, uint64_t map_len,
+                                         int map_memkind) {
+  const LabelPrep prep{w, h, map, map_len, map_memkind};
+  return add_labels_impl(a, r, indices, idx_dtype, idx_strides, idx_mem, labels, label_dtype, label_strides, label_mem, weights, w_strides, w_mem, W, H,
+                         &prep);
 }
 
 }  // extern "C"

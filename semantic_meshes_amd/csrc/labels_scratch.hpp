@@ -21,7 +21,24 @@ constexpr uint32_t kLabelsLdsMaxC = 255;
 struct LabelScratch {
   std::mutex mu;
   Scratch stage, plane, w, onehot;
-  void release() { stage.release(); plane.release(); w.release(); onehot.release(); }
+  Scratch map;   // the staged host map of a prepared call (smesh_label_prep.h)
+  void release() { stage.release(); plane.release(); w.release(); onehot.release(); map.release(); }
+};
+
+// What the prepared entry points (smesh_label_prep.h) add to their smesh_labels.h counterparts: the label images are (w,h), and their
+// values go through `map` (int32 [map_len] in `map_mem` memory; NULL: none).
+struct LabelPrep {
+  uint64_t w, h;
+  const int32_t* map;
+  uint64_t map_len;
+  int map_mem;
 };
 
 }  // namespace smesh
+
+// label_prep.hip.  smesh_label_prep_check: the refusals of smesh_label_prep.h for one (w,h) -> (W,H) pair.  smesh_label_prep_launch:
+// k_labels_prepare on the context's main stream -- `src` and `map_dev` in device memory, `out` the dense (W,H) plane of `out_bytes`
+// (1 or 2) bytes per pixel; the caller has checked the arguments and holds the context's lock.
+int smesh_label_prep_check(int label_dtype, const int64_t* strides, int memkind, const smesh::LabelPrep& p, uint64_t W, uint64_t H, uint32_t C);
+int smesh_label_prep_launch(smesh::DeviceCtx* ctx, const void* src, int label_dtype, const int64_t* strides, uint64_t w, uint64_t h,
+                            const int32_t* map_dev, uint64_t map_len, uint32_t C, void* out, int out_bytes, uint64_t W, uint64_t H);

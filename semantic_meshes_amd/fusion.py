@@ -45,6 +45,105 @@ def narrow_labels(labels, classes):
     return np.ascontiguousarray(np.where(u < u.dtype.type(limit), u, u.dtype.type(code)).astype(out, copy=False))
 
 
+def label_resize_mode(resize):
+    """The `resize=` keyword of the LABEL entry points: None, or "nearest" -- nearest neighbour with half-pixel centres
+    (include/smesh_label_prep.h).  Its own validation: the class-vector keyword (`resize.resize_mode`) knows "bilinear" only."""
+    if resize is None:
+        return None
+    if resize == "bilinear":
+        raise ValueError('resize="bilinear": label images are sampled, not blended -- use resize="nearest"')
+    if resize != "nearest":
+        raise ValueError('resize must be None or "nearest" for label images, got %r' % (resize,))
+    return "nearest"
+
+
+def check_label_map(label_map):
+    """`label_map` of the label entry points as the library takes it: None, or a one-dimensional, non-empty integer table as a dense
+    int32 array -- host numpy, or this library's own int32 DeviceArray as it is.  Source value v in [0, len) becomes map[v]; every
+    other value is don't care, and so is every entry outside [0, classes)."""
+    if label_map is None:
+        return None
+    if isinstance(label_map, DeviceArray):
+        if label_map.ndim != 1 or label_map.dtype != np.int32 or (label_map.shape[0] > 1 and label_map.strides[0] != 1):
+            raise ValueError("a label map on the device must be a dense one-dimensional int32 array, got %s %s" % (label_map.dtype, label_map.shape))
+        m = label_map
+    else:
+        a = np.asarray(label_map)
+        if a.ndim != 1:
+            raise ValueError("label map must be one-dimensional, got shape %s" % (a.shape,))
+        if a.dtype.kind not in "iu":
+            raise ValueError("label map must be an integer table, got %s" % a.dtype)
+        # (entries that int32 cannot hold are no class of any aggregator: -1 keeps them don't care)
+        if a.size and a.dtype.itemsize >= 4:
+            bad = (a > 0x7FFFFFFF) | (a < 0)
+            a = a.astype(np.int64)
+            a[bad] = -1
+        m = np.ascontiguousarray(a, dtype=np.int32)
+    if m.shape[0] == 0:
+        raise ValueError("label map is empty")
+    if m.shape[0] > 1 << 24:
+        raise ValueError("label map has more than 2^24 entries")
+    return m
+
+
+def _map_args(m):
+    """(pointer, length, memkind) of `check_label_map`'s result for the C ABI."""
+    if m is None:
+        return None, 0, _lib.MEM_HOST
+    if isinstance(m, DeviceArray):
+        return ctypes.c_void_p(m.ptr), int(m.shape[0]), _lib.MEM_DEVICE
+    return m.ctypes.data_as(ctypes.c_void_p), int(m.shape[0]), _lib.MEM_HOST
+
+
+def _describe_label_source(labels, device, streams, what="label image"):
+    """(pointer, memkind, (w, h), dtype code, element strides, keep-alive) of a label image that the library is to prepare: it goes
+    over as it is (the map sees the raw values).  A one-dimensional array is (n, 1)."""
+    if isinstance(labels, np.ndarray) and labels.ndim == 1:
+        labels = labels.reshape(-1, 1)
+    elif isinstance(labels, DeviceArray) and labels.ndim == 1:
+        labels = DeviceArray(labels.ptr, (labels.shape[0], 1), labels.dtype, labels.device, (labels.strides[0], 1), owner=labels)
+    lp, lmem, lshape, ldt, lstr, keep = describe(labels, 2, what, device, streams)
+    if ldt.name not in _lib.LBL_CODES:
+        raise ValueError("%s dtype must be one of %s, got %s" % (what, "/".join(_lib.LBL_CODES), ldt))
+    return lp, lmem, (int(lshape[0]), int(lshape[1])), _lib.LBL_CODES[ldt.name], tuple(lstr), keep
+
+
+def prepare_labels_device(labels, classes, size=None, resize=None, label_map=None, device=0):
+    """The dense (W,H) plane the label fusion and the confusion matrices read, built ON THE DEVICE from a label image at its own
+    resolution and in the dataset's ids (`smesh_labels_prepare`, include/smesh_label_prep.h): `labels` integer (w,h), host numpy or
+    device array, any non-negative strides; `size` = (W,H), None: the image's own; `resize="nearest"` samples a (w,h) != (W,H) image
+    with half-pixel centres (without it such a pair is refused); `label_map`, a one-dimensional integer table, turns source value v
+    into map[v] AFTER sampling (v outside the table: don't care).  Every value outside [0, classes) becomes the all-ones code.
+    Returns a `DeviceArray`, uint8 for up to 255 classes, else uint16."""
+    from .device import DeviceBuffer
+    mode = label_resize_mode(resize)
+    m = check_label_map(label_map)
+    classes = int(classes)
+    if not 0 < classes <= 65535:
+        raise ValueError("classes must be in [1, 65535]")
+    if isinstance(labels, DeviceArray):
+        device = labels.device
+    streams = []
+    lp, lmem, (w, h), lcode, lstr, keep = _describe_label_source(labels, int(device), streams)
+    W, H = (w, h) if size is None else (int(size[0]), int(size[1]))
+    if (W, H) != (w, h) and mode is None:
+        raise ValueError('label image is %s, the target %s: pass resize="nearest" to sample it' % ((w, h), (W, H)))
+    if W and H and not (w and h):
+        raise ValueError("an empty label image %s cannot be resampled to %s" % ((w, h), (W, H)))
+    dt = np.dtype(np.uint8 if classes <= 255 else np.uint16)
+    out = DeviceBuffer(max(W * H * dt.itemsize, 1), int(device)).view((W, H), dt)
+    mp, mlen, mmem = _map_args(m)
+    _lib.check(_lib.lib().smesh_labels_prepare(ctypes.c_void_p(lp), lcode, _c64(lstr), lmem, w, h, mp, mlen, mmem, classes,
+                                               ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], W, H, int(device)))
+    release_to(int(device), streams)
+    return out
+
+
+def prepare_labels(labels, classes, size=None, resize=None, label_map=None, device=0):
+    """`prepare_labels_device` copied to the host: a numpy array."""
+    return prepare_labels_device(labels, classes, size, resize, label_map, device).numpy()
+
+
 def probs_code(dtype, keep=None, probs_dtype=None, what="probs image"):
     """The SMESH_PROBS_* code (include/smesh_half.h) of a class-vector image of numpy dtype `dtype`, or None for a dtype the fusion
     does not read.  float16 is recognised from the dtype.  numpy has no bfloat16: it is a dtype NAMED bfloat16 (ml_dtypes) where one
@@ -538,19 +637,89 @@ class _MeshAggregator:
                 raise ValueError("weights image must be float32, got %s" % wdt)
         return wp, wmem, tuple(wshape), wstr, k2
 
-    def add_labels(self, primitive_image, label_image, weights_image=None):
+    # ---- label images at their own resolution and in the dataset's ids (include/smesh_label_prep.h) ---------------------------------
+    @staticmethod
+    def _shape_of(image):
+        return tuple(getattr(image, "shape", None) or np.shape(image))
+
+    def _prep_weights(self, weights_image, W, H, lmem, streams, what="weights image"):
+        """(pointer or None, keep-alive) of the weights of a prepared fuse_view(s)_labels call: dense float32 (W,H) where the labels are."""
+        if weights_image is None:
+            return None, None
+        wp, wmem, wshape, wstr, k2 = self._describe_weights(weights_image, streams)
+        if wshape != (W, H) or wstr != (H, 1) or wmem != lmem:
+            raise ValueError("%s must be contiguous float32 (W,H) in the same memory as the labels" % what)
+        return wp, k2
+
+    def _add_labels_prepared(self, primitive_image, label_image, weights_image, mode, m):
+        """`add_labels(..., resize=, label_map=)` with a map or a label image of another size: the views already deferred are handed
+        over first (the order of additions stays the caller's), then this view is one library call -- a render() plane that has not
+        been rasterised yet is never produced (`smesh_fuse_view_labels_prepared` with its camera), any other index image goes to
+        `smesh_aggregator_add_labels_prepared`.  Returns False for a call that needs no preparation (equal sizes, no map)."""
+        ishape = self._shape_of(primitive_image)
+        if m is None and self._shape_of(label_image) == ishape:
+            return False
+        streams = []
+        lp, lmem, (w, h), lcode, lstr, k1 = _describe_label_source(label_image, self.device, streams)
+        wdesc = None if weights_image is None else self._describe_weights(weights_image, streams)
+        if len(ishape) != 2 or (mode is None and (w, h) != ishape) or (wdesc is not None and wdesc[2] != ishape):
+            raise ValueError("Primitive image %s, label image %s and weights image %s must have the same width and height"
+                             % (ishape, (w, h), None if wdesc is None else wdesc[2]))
+        if ishape[0] and ishape[1] and not (w and h):
+            raise ValueError("an empty label image %s cannot be resampled to %s" % ((w, h), ishape))
+        mp, mlen, mmem = _map_args(m)
+        lazy = getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
+        if lazy and (wdesc is None or (wdesc[3] == (ishape[1], 1) and wdesc[1] == lmem)):
+            pend = primitive_image._pending
+            if pend.W and pend.H:
+                self.flush()
+                _lib.check(_lib.lib().smesh_fuse_view_labels_prepared(
+                    pend.renderer._h, self._handle, ctypes.byref(pend.pod), ctypes.c_void_p(lp), lcode, _c64(lstr),
+                    None if wdesc is None else ctypes.c_void_p(wdesc[0]), lmem, w, h, mp, mlen, mmem))
+                release_to(self.device, streams)
+                self._hold([k1 if lmem == _lib.MEM_DEVICE else None, wdesc[4] if (wdesc is not None and wdesc[1] == _lib.MEM_DEVICE) else None])
+            return True
+        ip, imem, ishape, idt, istr, k0 = describe(primitive_image, 2, "primitive image", self.device, streams)
+        if idt not in _IDX_CODES:
+            raise ValueError("primitive image dtype must be one of uint32/int32/uint64/int64, got %s" % idt)
+        W, H = ishape
+        if W == 0 or H == 0:
+            return True
+        rb = getattr(primitive_image, "_rendered_by", None)
+        if not (rb is not None and not primitive_image._exported and getattr(rb, "_h", None) is not None and rb._h.value
+                and rb.device == self.device):
+            rb = None
+        wp, wmem, wstr, k2 = (None, _lib.MEM_HOST, None, None) if wdesc is None else (wdesc[0], wdesc[1], wdesc[3], wdesc[4])
+        _lib.check(_lib.lib().smesh_aggregator_add_labels_prepared(
+            self._h, None if rb is None else rb._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
+            ctypes.c_void_p(lp), lcode, _c64(lstr), lmem,
+            None if wp is None else ctypes.c_void_p(wp), None if wstr is None else _c64(wstr), wmem, W, H, w, h, mp, mlen, mmem))
+        release_to(self.device, streams)
+        self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if lmem == _lib.MEM_DEVICE else None,
+                    k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
+        return True
+
+    def add_labels(self, primitive_image, label_image, weights_image=None, resize=None, label_map=None):
         """`add(primitive_image, one_hot(label_image), weights_image)` without the one-hot: `label_image` is (W,H) of uint8 / int8 /
         uint16 / int16 / uint32 / int32 / uint64 / int64 -- a class index per pixel, host numpy or device array, any non-negative strides
         (a mask decoded as (H,W) and passed as its transposed view is fine).  `one_hot` is tf.one_hot: a label outside [0, classes),
         negative values included, is the all-zero "don't care" vector.  On the untouched index plane of `render()` (lazy or not) of a
         triangle renderer and a Sum / Summax aggregator the view takes the label kernel (one addition per visible pixel); everything
         else expands the labels on the device and takes add()'s path.  Equal to the one-hot call for finite weights (with a non-finite
-        weight that call computes 0 * inf = NaN for the pixel's other classes; this one does not)."""
+        weight that call computes 0 * inf = NaN for the pixel's other classes; this one does not).
+
+        `resize="nearest"`: a `label_image` (w,h) of another size than the index image is sampled at half-pixel centres on the device;
+        `label_map`: a one-dimensional integer table, source value v becomes map[v] after sampling (`prepare_labels_device` states
+        the rule).  With either in play the views already deferred are handed over first and this view is a call of its own; with
+        equal sizes and no map the call is the plain one.  Without `resize` a mask of another size is refused."""
+        mode, m = label_resize_mode(resize), check_label_map(label_map)
         if type(primitive_image).__name__ == "PyCapsule":
             from . import dlpack
             own = dlpack.own_capsule_owner(primitive_image)
             if own is not None:
                 primitive_image = own
+        if (mode is not None or m is not None) and self._add_labels_prepared(primitive_image, label_image, weights_image, mode, m):
+            return
         if (getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
                 and self._deferrable_labels(label_image, weights_image, *primitive_image.shape)):
             pend = primitive_image._pending      # (render()'s plane, not rasterised yet: the view joins the group, see add())
@@ -589,9 +758,26 @@ class _MeshAggregator:
         self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if lmem == _lib.MEM_DEVICE else None,
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
 
-    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None):
-        """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels)."""
+    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None):
+        """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`
+        and `label_map`)."""
+        mode, m = label_resize_mode(resize), check_label_map(label_map)
         W, H = camera.resolution
+        if m is not None or (mode is not None and self._shape_of(label_image) != (W, H)):
+            streams = []
+            lp, lmem, (w, h), lcode, lstr, k1 = _describe_label_source(label_image, self.device, streams)
+            if mode is None and (w, h) != (W, H):
+                raise ValueError("%s must be (W,H) = %s, got %s" % ("label image", (W, H), (w, h)))
+            if W and H and not (w and h):
+                raise ValueError("an empty label image %s cannot be resampled to %s" % ((w, h), (W, H)))
+            wp, k2 = self._prep_weights(weights_image, W, H, lmem, streams)
+            mp, mlen, mmem = _map_args(m)
+            _lib.check(_lib.lib().smesh_fuse_view_labels_prepared(
+                renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(lp), lcode, _c64(lstr),
+                None if wp is None else ctypes.c_void_p(wp), lmem, w, h, mp, mlen, mmem))
+            release_to(self.device, streams)
+            self._hold([k1 if lmem == _lib.MEM_DEVICE else None, k2 if lmem == _lib.MEM_DEVICE else None])
+            return
         if (W > 0 and H > 0 and W <= 65536 and H <= 65536 and W * H < 0x7FFFFFFF // 4 and renderer.device == self.device
                 and self._deferrable_labels(label_image, weights_image, W, H)):
             self._defer(renderer, _lib.CameraPOD.from_buffer_copy(camera._pod), W, H, label_image, weights_image, labels=True)
@@ -610,16 +796,53 @@ class _MeshAggregator:
         if lmem == _lib.MEM_DEVICE:
             self._hold([k1, k2])
 
-    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None):
+    def _fuse_views_labels_prepared(self, renderer, cameras, label_images, weights_images, resize, mode, m):
+        """`fuse_views_labels(..., resize=, label_map=)` with a map or images of another size: every image is checked first; images
+        that share size, dtype, strides and memory go to `smesh_fuse_views_labels_prepared` as one batch -- the library prepares and
+        fuses them in groups of eight --, a mixed list is fused view by view."""
+        n = len(cameras)
+        streams, desc = [], []
+        for i, cam in enumerate(cameras):
+            W, H = cam.resolution
+            d = _describe_label_source(label_images[i], self.device, streams, "label image %d" % i)
+            if mode is None and d[2] != (W, H):
+                raise ValueError("%s must be (W,H) = %s, got %s" % ("label image %d" % i, (W, H), d[2]))
+            if W and H and not (d[2][0] and d[2][1]):
+                raise ValueError("an empty label image %d %s cannot be resampled to %s" % (i, d[2], (W, H)))
+            w = None if weights_images is None else weights_images[i]
+            desc.append((d, self._prep_weights(w, W, H, d[1], streams, "weights image %d" % i)))
+        first = desc[0][0]
+        if not all(d[1:5] == first[1:5] and (dw[0] is None) == (desc[0][1][0] is None) for d, dw in desc):
+            release_to(self.device, streams)
+            for i in range(n):
+                self.fuse_view_labels(renderer, cameras[i], label_images[i], None if weights_images is None else weights_images[i],
+                                      resize, m)
+            return
+        pods = (_lib.CameraPOD * n)(*[cam._pod for cam in cameras])
+        lptr = (ctypes.c_void_p * n)(*[d[0] for d, _ in desc])
+        wptr = None if desc[0][1][0] is None else (ctypes.c_void_p * n)(*[dw[0] for _, dw in desc])
+        mp, mlen, mmem = _map_args(m)
+        _lib.check(_lib.lib().smesh_fuse_views_labels_prepared(renderer._h, self._h, pods, n, lptr, first[3], _c64(first[4]), wptr, first[1],
+                                                                first[2][0], first[2][1], mp, mlen, mmem))
+        release_to(self.device, streams)
+        if first[1] == _lib.MEM_DEVICE:
+            self._hold([d[5] for d, _ in desc] + [dw[1] for _, dw in desc])
+
+    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None):
         """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
         views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
-        and memory go to the library as one batch; a mixed list is fused view by view."""
+        and memory go to the library as one batch; a mixed list is fused view by view.  `resize="nearest"` / `label_map` (see
+        add_labels): the fast form for masks at the network's resolution or in the dataset's ids -- images that also share their
+        size are prepared and fused by the library in batches of eight."""
+        mode, m = label_resize_mode(resize), check_label_map(label_map)
         cameras, label_images = list(cameras), list(label_images)
         n = len(cameras)
         if len(label_images) != n or (weights_images is not None and len(weights_images) != n):
             raise ValueError("fuse_views_labels needs one label image (and one weights image or None) per camera")
         if n == 0:
             return
+        if m is not None or (mode is not None and any(self._shape_of(label_images[i]) != tuple(cam.resolution) for i, cam in enumerate(cameras))):
+            return self._fuse_views_labels_prepared(renderer, cameras, label_images, weights_images, resize, mode, m)
         streams, desc = [], []
         for i, cam in enumerate(cameras):
             W, H = cam.resolution

@@ -7,8 +7,10 @@ resampling is defined to the bit: half-pixel centres, no antiali
 
 `resize_probs_device` / `resize_probs` give the dense (W,H,C) image; `argmax_labels(..., size=, resize=)`,
 `ConfusionMatrix.add_probs(..., resize=)` and `MeshAggregator.add / add_many / fuse_view / fuse_views(..., resize=)` (evaluation.py,
-fusion.py) use it where their image's width and height differ from the target's.  Nearest-neighbour resampling, label images and
-`fuse_views_ranged` are not served.
+fusion.py) use it where their image's width and height differ from the target's.  Nearest-neighbour resampling of class vectors
+and `fuse_views_ranged` are not served.  Label images have a keyword of their own -- `resize="nearest"` on `add_labels` /
+`fuse_view(s)_labels`, `gt_resize=` on `ConfusionMatrix` -- with its own rule and validation (include/smesh_label_prep.h,
+`fusion.prepare_labels_device`): they are sampled, not blended.
 """
 import ctypes
 
