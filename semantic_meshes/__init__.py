@@ -8,7 +8,7 @@ import semantic_meshes_amd as _impl
 from semantic_meshes_amd import data, fusion  # noqa: F401
 from semantic_meshes_amd import render as _render_impl
 
-for _name in ("data", "fusion", "distributed", "synth", "device"):
+for _name in ("data", "fusion", "distributed", "synth", "device", "label_colors"):
     _sys.modules[__name__ + "." + _name] = __import__("semantic_meshes_amd." + _name, fromlist=[_name])
 
 # Under the REFERENCE's package name render() returns what the reference returns: a tuple of "dltensor" PyCapsules

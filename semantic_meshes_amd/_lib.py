@@ -249,6 +249,20 @@ LABEL_PREP_SIGNATURES = {
     "smesh_aggregator_add_labels_prepared": (c_int, EXT_SIGNATURES["smesh_aggregator_add_labels"][1] + _PREP_TAIL),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_label_colors.h: label images that are colour images,
+# product-only like the tables above.  Each fusion entry point is its EXT_SIGNATURES counterpart (with three label strides) plus
+# (w, h, channels, keys, classes, K).
+LABEL_COLORS_LDS_MAX = 4096        # SMESH_LABEL_COLORS_LDS_MAX
+_COLORS_TAIL = [c_u64, c_u64, c_int, c_void_p, c_void_p, c_u64]
+LABEL_COLORS_SIGNATURES = {
+    "smesh_colors_unique": (c_int, [P(c_void_p), c_u64, c_int, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_void_p, c_u64, c_void_p, c_int]),
+    "smesh_labels_prepare_colors": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_void_p, c_void_p, c_u64, c_u32,
+                                            c_void_p, c_int, c_u64, c_u64, c_int]),
+    "smesh_fuse_views_labels_colors": (c_int, EXT_SIGNATURES["smesh_fuse_views_labels"][1] + _COLORS_TAIL),
+    "smesh_fuse_view_labels_colors": (c_int, EXT_SIGNATURES["smesh_fuse_view_labels"][1] + _COLORS_TAIL),
+    "smesh_aggregator_add_labels_colors": (c_int, EXT_SIGNATURES["smesh_aggregator_add_labels"][1] + _COLORS_TAIL),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -376,7 +390,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

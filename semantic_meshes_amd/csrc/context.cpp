@@ -3,6 +3,7 @@
 #include "labels_scratch.hpp"
 #include "half_scratch.hpp"
 #include "../../include/smesh_label_prep.h"
+#include "../../include/smesh_label_colors.h"
 
 #include <algorithm>
 #include <atomic>
@@ -42,6 +43,7 @@ static std::atomic<int> g_resize_vector{1};   // (off: the generic path everywhe
 bool opt_resize_vector() { return g_resize_vector.load() != 0; }
 
 uint64_t smesh_label_prep_launches();      // label_prep.hip
+uint64_t smesh_label_colors_launches();    // label_colors.hip
 
 // "fuse_sampled" (fusion_sampled.hip): 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- a test hook, like
 // SMESH_FUSE_H16=0.  -1: not set by smesh_set_option -- the environment's SMESH_FUSE_SAMPLED, read at every call, else on.
@@ -385,6 +387,9 @@ int smesh_get_option(const char* name, int64_t* value) {
   // read-only (smesh_label_prep.h): the largest map kept in LDS and this process's launches of k_labels_prepare
   if (!strcmp(name, "labels_prepare_map_lds_max")) { *value = (int64_t)SMESH_LABEL_PREP_MAP_LDS_MAX; return SMESH_OK; }
   if (!strcmp(name, "labels_prepare_launches")) { *value = (int64_t)smesh_label_prep_launches(); return SMESH_OK; }
+  // read-only (smesh_label_colors.h): the largest colour table kept in LDS and this process's launches of k_labels_prepare_colors
+  if (!strcmp(name, "labels_colors_lds_max")) { *value = (int64_t)SMESH_LABEL_COLORS_LDS_MAX; return SMESH_OK; }
+  if (!strcmp(name, "labels_colors_launches")) { *value = (int64_t)smesh_label_colors_launches(); return SMESH_OK; }
   // read-only (smesh_probs_labels.h): the largest class count the tiled path serves
   if (!strcmp(name, "probs_labels_tile_max_classes")) { *value = (int64_t)kProbsLabelsTileMaxC; return SMESH_OK; }
   // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --

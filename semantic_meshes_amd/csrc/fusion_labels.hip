@@ -17,6 +17,7 @@
 #include "labels_scratch.hpp"
 #include "../../include/smesh_labels.h"
 #include "../../include/smesh_label_prep.h"
+#include "../../include/smesh_label_colors.h"
 
 #include <algorithm>
 #include <cmath>
@@ -417,21 +418,23 @@ bool plane_in_place(int dt, const int64_t* strides, int mem, uint64_t W, uint64_
 // k_labels_prepare writes the plane -- always into the scratch, never in place --, a host image is staged at its own size and span.
 int narrow_plane(DeviceCtx* ctx, LabelScratch& ls, int slot, size_t slot_bytes, size_t stage_bytes, const void* src, int dt, const int64_t* strides,
                  int mem, uint64_t W, uint64_t H, uint32_t C, const void** plane, int* label_bytes, bool* staged,
-                 const LabelPrep* prep = nullptr, const int32_t* map_dev = nullptr) {
+                 const LabelPrep* prep = nullptr, const LabelTableDev& table = LabelTableDev()) {
   const uint64_t N = W * H;
   if (prep) {
-    const int64_t own[2] = {(int64_t)prep->h, 1};
+    const int ch = prep->channels;   // colour images (smesh_label_colors.h): three strides, uint8
+    const int64_t own[3] = {(int64_t)prep->h * (ch ? ch : 1), ch ? ch : 1, 1};
     const int64_t* ps = strides ? strides : own;
     *label_bytes = C <= 255u ? 1 : 2;
     char* dst = static_cast<char*>(ls.plane.ptr) + (size_t)slot * slot_bytes;
     if (mem == SMESH_MEM_HOST) {
       *staged = true;
-      const size_t span = (1 + (prep->w - 1) * (uint64_t)ps[0] + (prep->h - 1) * (uint64_t)ps[1]) * label_itemsize(dt);
+      const size_t span = (1 + (prep->w - 1) * (uint64_t)ps[0] + (prep->h - 1) * (uint64_t)ps[1] + (ch ? 2 * (uint64_t)ps[2] : 0)) * label_itemsize(dt);
       char* stage = static_cast<char*>(ls.stage.ptr) + (size_t)slot * stage_bytes;
       SMESH_HIP(hipMemcpyAsync(stage, src, span, hipMemcpyHostToDevice, ctx->stream));
       src = stage;
     }
-    SMESH_TRY(smesh_label_prep_launch(ctx, src, dt, ps, prep->w, prep->h, map_dev, prep->map_len, C, dst, *label_bytes, W, H));
+    if (ch) SMESH_TRY(smesh_label_colors_launch(ctx, src, ps, prep->w, prep->h, table.keys, table.map, prep->table_len, C, dst, *label_bytes, W, H));
+    else SMESH_TRY(smesh_label_prep_launch(ctx, src, dt, ps, prep->w, prep->h, table.map, prep->map_len, C, dst, *label_bytes, W, H));
     *plane = dst;
     return SMESH_OK;
   }
@@ -462,20 +465,33 @@ int narrow_plane(DeviceCtx* ctx, LabelScratch& ls, int slot, size_t slot_bytes, 
   return SMESH_OK;
 }
 
-size_t stage_span_bytes(int dt, const int64_t* strides, uint64_t W, uint64_t H) {
-  const int64_t dense[2] = {(int64_t)H, 1};
+// (`channels`: a colour image of smesh_label_colors.h, three strides; its fourth channel is never read)
+size_t stage_span_bytes(int dt, const int64_t* strides, uint64_t W, uint64_t H, int channels = 0) {
+  const int64_t dense[3] = {(int64_t)H * (channels ? channels : 1), channels ? channels : 1, 1};
   const int64_t* s = strides ? strides : dense;
-  return ((1 + (W - 1) * (uint64_t)s[0] + (H - 1) * (uint64_t)s[1]) * label_itemsize(dt) + 255) & ~(size_t)255;
+  return ((1 + (W - 1) * (uint64_t)s[0] + (H - 1) * (uint64_t)s[1] + (channels ? 2 * (uint64_t)s[2] : 0)) * label_itemsize(dt) + 255) & ~(size_t)255;
 }
 
 // The map of a prepared call in device memory: itself, or its copy in the aggregator's scratch (a host map: *staged = true).
-int stage_map(DeviceCtx* ctx, LabelScratch& ls, const LabelPrep* prep, const int32_t** map_dev, bool* staged) {
-  *map_dev = nullptr;
+// A colour table (always host memory) is staged as [keys][classes].
+int stage_map(DeviceCtx* ctx, LabelScratch& ls, const LabelPrep* prep, LabelTableDev* table, bool* staged) {
+  *table = LabelTableDev();
+  if (prep && prep->channels) {
+    const size_t kb = prep->table_len * 4;
+    SMESH_TRY(ls.map.reserve(kb * 2));
+    char* d = static_cast<char*>(ls.map.ptr);
+    SMESH_HIP(hipMemcpyAsync(d, prep->keys, kb, hipMemcpyHostToDevice, ctx->stream));
+    SMESH_HIP(hipMemcpyAsync(d + kb, prep->classes, kb, hipMemcpyHostToDevice, ctx->stream));
+    table->keys = reinterpret_cast<const uint32_t*>(d);
+    table->map = reinterpret_cast<const int32_t*>(d + kb);
+    *staged = true;
+    return SMESH_OK;
+  }
   if (!prep || !prep->map) return SMESH_OK;
-  if (prep->map_mem == SMESH_MEM_DEVICE) { *map_dev = prep->map; return SMESH_OK; }
+  if (prep->map_mem == SMESH_MEM_DEVICE) { table->map = prep->map; return SMESH_OK; }
   SMESH_TRY(ls.map.reserve(prep->map_len * 4));
   SMESH_HIP(hipMemcpyAsync(ls.map.ptr, prep->map, prep->map_len * 4, hipMemcpyHostToDevice, ctx->stream));
-  *map_dev = static_cast<const int32_t*>(ls.map.ptr);
+  table->map = static_cast<const int32_t*>(ls.map.ptr);
   *staged = true;
   return SMESH_OK;
 }
@@ -573,6 +589,7 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
   if (!r || !a || (n && (!cams || !labels))) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(check_label_args(label_dtype, label_strides));
   if (memkind != SMESH_MEM_HOST && memkind != SMESH_MEM_DEVICE) return fail(SMESH_ERR_INVALID, "bad memory kind");
+  if (prep && prep->channels) SMESH_TRY(smesh_label_colors_check(label_dtype, label_strides, *prep));
   for (uint64_t i = 0; i < n; i++) {
     if (!labels[i]) return fail(SMESH_ERR_INVALID, "NULL label image");
     if (cams[i].width == 0 || cams[i].height == 0 || cams[i].width > 65536 || cams[i].height > 65536)
@@ -586,7 +603,7 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
   if (prep) {
     for (uint64_t i = 0; i < n; i++) SMESH_TRY(smesh_label_prep_check(label_dtype, label_strides, memkind, *prep, cams[i].width, cams[i].height, C));
   }
-  const int32_t* map_dev = nullptr;
+  LabelTableDev table;
   bool map_staged = false;
   LabelScratch& ls = smesh_aggregator_label_scratch(a);
   std::lock_guard<std::mutex> g(ls.mu);
@@ -598,7 +615,7 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
     for (int v = 0; v < m; v++) {
       const uint64_t N = cams[i + v].width * cams[i + v].height;
       slot_bytes = std::max<size_t>(slot_bytes, (N * 2 + 255) & ~(size_t)255);
-      stage_bytes = std::max(stage_bytes, prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h)
+      stage_bytes = std::max(stage_bytes, prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h, prep->channels)
                                                   : stage_span_bytes(label_dtype, label_strides, cams[i + v].width, cams[i + v].height));
       w_bytes = std::max<size_t>(w_bytes, (N * 4 + 255) & ~(size_t)255);
     }
@@ -610,7 +627,7 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
       std::lock_guard<std::recursive_mutex> lock(ctx->mu);
       SMESH_HIP(hipSetDevice(ctx->device));
       if (i == 0) {
-        SMESH_TRY(stage_map(ctx, ls, prep, &map_dev, &map_staged));
+        SMESH_TRY(stage_map(ctx, ls, prep, &table, &map_staged));
         staged = map_staged;
       }
       bool in_place = !prep;   // nothing to narrow: no plane scratch (a prepared plane is always scratch)
@@ -623,7 +640,7 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
       for (int v = 0; v < m; v++) {
         const uint64_t W = cams[i + v].width, H = cams[i + v].height;
         SMESH_TRY(narrow_plane(ctx, ls, v, slot_bytes, stage_bytes, labels[i + v], label_dtype, label_strides, memkind, W, H, C, &planes[v],
-                               &label_bytes, &staged, prep, map_dev));
+                               &label_bytes, &staged, prep, table));
         wts[v] = weights ? weights[i + v] : nullptr;
         if (wts[v] && memkind == SMESH_MEM_HOST) {
           float* d = reinterpret_cast<float*>(static_cast<char*>(ls.w.ptr) + (size_t)v * w_bytes);
@@ -651,6 +668,7 @@ static int add_labels_impl(smesh_aggregator_t* a, smesh_renderer_t* r, const voi
   smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
   if (prep) {
     if (label_mem != SMESH_MEM_HOST && label_mem != SMESH_MEM_DEVICE) return fail(SMESH_ERR_INVALID, "bad memory kind");
+    if (prep->channels) SMESH_TRY(smesh_label_colors_check(label_dtype, label_strides, *prep));
     SMESH_TRY(smesh_label_prep_check(label_dtype, label_strides, label_mem, *prep, W, H, C));
   }
   if (W == 0 || H == 0) return SMESH_OK;
@@ -673,13 +691,13 @@ static int add_labels_impl(smesh_aggregator_t* a, smesh_renderer_t* r, const voi
   {
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     SMESH_HIP(hipSetDevice(ctx->device));
-    const int32_t* map_dev = nullptr;
-    SMESH_TRY(stage_map(ctx, ls, prep, &map_dev, &staged));
+    LabelTableDev table;
+    SMESH_TRY(stage_map(ctx, ls, prep, &table, &staged));
     if (prep || !plane_in_place(label_dtype, label_strides, label_mem, W, H)) SMESH_TRY(ls.plane.reserve((N * 2 + 255) & ~(size_t)255));
     if (label_mem == SMESH_MEM_HOST)
-      SMESH_TRY(ls.stage.reserve(prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h) : stage_span_bytes(label_dtype, label_strides, W, H)));
+      SMESH_TRY(ls.stage.reserve(prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h, prep->channels) : stage_span_bytes(label_dtype, label_strides, W, H)));
     SMESH_TRY(narrow_plane(ctx, ls, 0, (N * 2 + 255) & ~(size_t)255, 0, labels, label_dtype, label_strides, label_mem, W, H, C, &plane, &label_bytes, &staged,
-                           prep, map_dev));
+                           prep, table));
     if (rendered && weights && w_mem == SMESH_MEM_HOST) {   // (the triangle-order kernel wants the weights where the plane is)
       SMESH_TRY(ls.w.reserve(N * 4));
       SMESH_HIP(hipMemcpyAsync(ls.w.ptr, weights, N * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -704,7 +722,14 @@ static int add_labels_impl(smesh_aggregator_t* a, smesh_renderer_t* r, const voi
   return smesh_aggregator_add_async(a, indices, idx_dtype, is, idx_mem, probs, ps, SMESH_MEM_DEVICE, weights, ws, w_mem, W, H);
 }
 
-// ---- include/smesh_labels.h, include/smesh_label_prep.h -----------------------------------------------------------------------
+// ---- include/smesh_labels.h, include/smesh_label_prep.h, include/smesh_label_colors.h -----------------------------------------------
+static LabelPrep color_prep(uint64_t w, uint64_t h, int channels, const uint32_t* keys, const int32_t* classes, uint64_t K) {
+  LabelPrep p{w, h, nullptr, 0, SMESH_MEM_HOST};
+  p.channels = channels ? channels : -1;   // (0 is "no colour image" inside: a refused count either way)
+  p.keys = keys; p.classes = classes; p.table_len = K;
+  return p;
+}
+
 extern "C" {
 
 int smesh_fuse_views_labels(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
@@ -746,6 +771,30 @@ int smesh_aggregator_add_labels_prepared(smesh_aggregator_t* a, smesh_renderer_t
                                          int w_mem, uint64_t W, uint64_t H, uint64_t w, uint64_t h, const int32_t* map, uint64_t map_len,
                                          int map_memkind) {
   const LabelPrep prep{w, h, map, map_len, map_memkind};
+  return add_labels_impl(a, r, indices, idx_dtype, idx_strides, idx_mem, labels, label_dtype, label_strides, label_mem, weights, w_strides, w_mem, W, H,
+                         &prep);
+}
+
+int smesh_fuse_views_labels_colors(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const void* const* labels,
+                                   int label_dtype, const int64_t label_strides[3], const float* const* weights, int memkind, uint64_t w,
+                                   uint64_t h, int channels, const uint32_t* keys, const int32_t* classes, uint64_t K) {
+  const LabelPrep prep = color_prep(w, h, channels, keys, classes, K);
+  return fuse_views_labels_impl(r, a, cams, n, labels, label_dtype, label_strides, weights, memkind, &prep);
+}
+
+int smesh_fuse_view_labels_colors(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const void* labels, int label_dtype,
+                                  const int64_t label_strides[3], const float* weights, int memkind, uint64_t w, uint64_t h, int channels,
+                                  const uint32_t* keys, const int32_t* classes, uint64_t K) {
+  if (!cam) return fail(SMESH_ERR_INVALID, "NULL argument");
+  const LabelPrep prep = color_prep(w, h, channels, keys, classes, K);
+  return fuse_views_labels_impl(r, a, cam, 1, &labels, label_dtype, label_strides, weights ? &weights : nullptr, memkind, &prep);
+}
+
+int smesh_aggregator_add_labels_colors(smesh_aggregator_t* a, smesh_renderer_t* r, const void* indices, int idx_dtype, const int64_t idx_strides[2],
+                                       int idx_mem, const void* labels, int label_dtype, const int64_t label_strides[3], int label_mem,
+                                       const float* weights, const int64_t w_strides[2], int w_mem, uint64_t W, uint64_t H, uint64_t w,
+                                       uint64_t h, int channels, const uint32_t* keys, const int32_t* classes, uint64_t K) {
+  const LabelPrep prep = color_prep(w, h, channels, keys, classes, K);
   return add_labels_impl(a, r, indices, idx_dtype, idx_strides, idx_mem, labels, label_dtype, label_strides, label_mem, weights, w_strides, w_mem, W, H,
                          &prep);
 }

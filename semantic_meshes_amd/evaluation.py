@@ -221,14 +221,23 @@ class ConfusionMatrix:
             ptr, mem, gshape, dt, strides, keep = describe(keep, ndim, what, self.device, streams)
         return ptr, mem, _lib.LBL_CODES[dt.name], tuple(strides), keep
 
-    def _prepared_gt(self, gt, shape, gt_resize, gt_map, what):
+    def _prepared_gt(self, gt, shape, gt_resize, gt_map, what, gt_palette=None):
         """The ground truth of a call with `gt_resize=` / `gt_map=` (include/smesh_label_prep.h, `fusion.prepare_labels_device`): `gt`
         itself where neither is in play -- no map, and its shape is `shape` (None: whatever it is) already --, else its prepared dense
         uint8 / uint16 plane on the device, which the entry points below take as they take any ground truth: every value >= classes,
-        the plane's don't-care code included, enters no cell and counts in `ignored`."""
-        from .fusion import check_label_map, label_resize_mode, prepare_labels_device
+        the plane's don't-care code included, enters no cell and counts in `ignored`.  `gt_palette=` (include/smesh_label_colors.h):
+        `gt` is a (W,H,3) / (W,H,4) uint8 colour image, `gt_palette` a (K,3) uint8 array (class = row) or a `fusion.ColorTable` -- ground
+        truth has a known palette --; a colour outside it is ignored."""
+        from .fusion import check_label_map, check_palette, label_resize_mode, prepare_labels_device
         mode, m = label_resize_mode(gt_resize), check_label_map(gt_map)
         gshape = tuple(getattr(gt, "shape", None) or np.shape(gt))
+        pal = check_palette(gt_palette, m, remap_ok=False, what="gt_palette")
+        if pal is not None:
+            if self.classes > 65535:
+                raise ValueError("gt_palette needs a confusion matrix of at most 65535 classes")
+            if shape is not None and mode is None and gshape[:2] != tuple(shape):
+                raise ValueError("%s must have shape %s + (3 or 4,), got %s" % (what, tuple(shape), gshape))
+            return prepare_labels_device(gt, self.classes, shape, gt_resize, None, self.device, pal)
         if m is None and (mode is None or shape is None or gshape == tuple(shape)):
             return gt
         if self.classes > 65535:
@@ -277,37 +286,40 @@ class ConfusionMatrix:
         _lib.check(_lib.lib().smesh_confusion_add_labels(self._h, ctypes.c_void_p(pp), pmem, ctypes.c_void_p(gp), gcode, gmem, n))
         self._done(streams, [k0, k1])
 
-    def add_image(self, primitive_indices, labels, gt, gt_resize=None, gt_map=None):
+    def add_image(self, primitive_indices, labels, gt, gt_resize=None, gt_map=None, gt_palette=None):
         """Score an index image that already exists: `primitive_indices` (W,H) of uint32 / int32 / uint64 / int64 (background and
         indices >= P: don't care), `labels` int32 [P], `gt` integer (W,H).  `gt_resize="nearest"`: a `gt` of another size is sampled
         at half-pixel centres on the device; `gt_map`: ground-truth value v counts as map[v], after sampling (the rule of
-        `fusion.prepare_labels_device`; eval_scannet.py's tf.gather(scannet_to_nyu40, gt) is `gt_map=scannet_to_nyu40 - 1`)."""
+        `fusion.prepare_labels_device`; eval_scannet.py's tf.gather(scannet_to_nyu40, gt) is `gt_map=scannet_to_nyu40 - 1`).
+        `gt_palette`: `gt` is a colour image (W,H,3) / (W,H,4) uint8 and counts as the class of its colour -- a (K,3) uint8 array
+        (class = row) or a `fusion.ColorTable`; a colour outside the palette is ignored."""
         streams = []
         ip, imem, ishape, idt, istr, k0 = describe(primitive_indices, 2, "primitive image", self.device, streams)
         if idt not in _IDX_CODES:
             raise ValueError("primitive image dtype must be one of uint32/int32/uint64/int64, got %s" % idt)
         lp, lmem, P, k1 = self._labels(labels, "labels", streams, False)
-        gt = self._prepared_gt(gt, tuple(ishape), gt_resize, gt_map, "ground truth")
+        gt = self._prepared_gt(gt, tuple(ishape), gt_resize, gt_map, "ground truth", gt_palette)
         gp, gmem, gcode, gstr, k2 = self._gt(gt, 2, ishape, "ground truth", streams)
         W, H = ishape
         _lib.check(_lib.lib().smesh_confusion_add_image(self._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
                                                         ctypes.c_void_p(lp), P, lmem, ctypes.c_void_p(gp), gcode, _c64(gstr), gmem, W, H))
         self._done(streams, [k0, k1, k2])
 
-    def add_view(self, renderer, camera, labels, gt, gt_resize=None, gt_map=None):
-        """Rasterise `camera` with `renderer` and score the view against `gt` (W,H) = camera.resolution (`gt_resize`, `gt_map`: see
-        add_image)."""
-        self.add_views(renderer, [camera], labels, [gt], gt_resize, gt_map)
+    def add_view(self, renderer, camera, labels, gt, gt_resize=None, gt_map=None, gt_palette=None):
+        """Rasterise `camera` with `renderer` and score the view against `gt` (W,H) = camera.resolution (`gt_resize`, `gt_map`,
+        `gt_palette`: see add_image)."""
+        self.add_views(renderer, [camera], labels, [gt], gt_resize, gt_map, gt_palette)
 
-    def add_views(self, renderer, cameras, labels, gt_images, gt_resize=None, gt_map=None):
+    def add_views(self, renderer, cameras, labels, gt_images, gt_resize=None, gt_map=None, gt_palette=None):
         """`add_view` for a batch: up to eight views share their rasteriser launches.  Ground-truth images that share dtype, strides
-        and memory go to the library as one batch; a mixed list is scored view by view.  `gt_resize`, `gt_map`: see add_image."""
+        and memory go to the library as one batch; a mixed list is scored view by view.  `gt_resize`, `gt_map`, `gt_palette`: see
+        add_image."""
         cameras, gt_images = list(cameras), list(gt_images)
         n = len(cameras)
         if len(gt_images) != n:
             raise ValueError("add_views needs one ground-truth image per camera")
-        if gt_resize is not None or gt_map is not None:
-            gt_images = [self._prepared_gt(gt_images[i], tuple(cam.resolution), gt_resize, gt_map, "ground truth %d" % i)
+        if gt_resize is not None or gt_map is not None or gt_palette is not None:
+            gt_images = [self._prepared_gt(gt_images[i], tuple(cam.resolution), gt_resize, gt_map, "ground truth %d" % i, gt_palette)
                          for i, cam in enumerate(cameras)]
         streams = []
         lp, lmem, P, k0 = self._labels(labels, "labels", streams, True)
@@ -328,17 +340,18 @@ class ConfusionMatrix:
                                                             first[2], _c64(first[3]), first[1]))
         self._done(streams, [k0] + [d[4] for d in desc])
 
-    def add_probs(self, probs, gt, dont_care_threshold=None, probs_dtype=None, labels_out=False, resize=None, gt_map=None):
+    def add_probs(self, probs, gt, dont_care_threshold=None, probs_dtype=None, labels_out=False, resize=None, gt_map=None, gt_palette=None):
         """Score a class-vector image itself -- the network's own prediction, the baseline the fused mesh is compared with: `probs`
         (W,H,C) with C = classes (what `MeshAggregator.add` takes), arg-maxed by the rule of `argmax_labels_device` and counted against
         `gt` integer (W,H) in the same pass.  With `dont_care_threshold` a pixel whose class sum is below it counts as don't care.
         `labels_out=True` returns the label image of that pass as a (W,H) `DeviceArray`.  With `resize="bilinear"` a `probs` image
         whose (w,h) is not `gt`'s (W,H) is scored as `resize_probs(probs, (W,H))` would be (resize.py), without that image being
         built; with `resize=None` such a pair is refused.  `gt_map`: ground-truth value v counts as map[v] (see add_image; the ground
-        truth defines the target size, so there is nothing to resample on its side)."""
+        truth defines the target size, so there is nothing to resample on its side); `gt_palette`: a colour image as ground truth (see
+        add_image)."""
         from .resize import resize_mode
         mode = resize_mode(resize)
-        gt = self._prepared_gt(gt, None, None, gt_map, "ground truth")
+        gt = self._prepared_gt(gt, None, None, gt_map, "ground truth", gt_palette)
         streams = []
         thr = _threshold(dont_care_threshold)
         pp, pmem, (W, H, C), code, pstr, k0 = _describe_probs(probs, probs_dtype, self.device, streams)
@@ -378,12 +391,13 @@ class ConfusionMatrix:
         self._done(streams, [k0, k1])
         return out
 
-    def add_probs_many(self, probs_images, gt_images, dont_care_threshold=None, probs_dtype=None, labels_out=False, resize=None, gt_map=None):
+    def add_probs_many(self, probs_images, gt_images, dont_care_threshold=None, probs_dtype=None, labels_out=False, resize=None, gt_map=None,
+                       gt_palette=None):
         """`add_probs` for a batch: a loop.  Returns the list of label images with `labels_out=True`."""
         probs_images, gt_images = list(probs_images), list(gt_images)
         if len(probs_images) != len(gt_images):
             raise ValueError("add_probs_many needs one ground-truth image per class-vector image")
-        outs = [self.add_probs(p, g, dont_care_threshold, probs_dtype, labels_out, resize, gt_map) for p, g in zip(probs_images, gt_images)]
+        outs = [self.add_probs(p, g, dont_care_threshold, probs_dtype, labels_out, resize, gt_map, gt_palette) for p, g in zip(probs_images, gt_images)]
         return outs if labels_out else None
 
     def add_counts(self, M, ignored=0):

@@ -95,9 +95,12 @@ def _map_args(m):
     return m.ctypes.data_as(ctypes.c_void_p), int(m.shape[0]), _lib.MEM_HOST
 
 
-def _describe_label_source(labels, device, streams, what="label image"):
-    """(pointer, memkind, (w, h), dtype code, element strides, keep-alive) of a label image that the library is to prepare: it goes
-    over as it is (the map sees the raw values).  A one-dimensional array is (n, 1)."""
+def _describe_label_source(labels, device, streams, what="label image", m=None):
+    """(pointer, memkind, (w, h), dtype code, element strides, keep-alive, channels) of a label image that the library is to prepare:
+    it goes over as it is (the map sees the raw values).  A one-dimensional array is (n, 1).  With a `ColorTable` as `m` the image is
+    a (w,h,3) / (w,h,4) colour image with three strides; else `channels` is 0."""
+    if isinstance(m, ColorTable):
+        return describe_color_source(labels, device, streams, what)
     if isinstance(labels, np.ndarray) and labels.ndim == 1:
         labels = labels.reshape(-1, 1)
     elif isinstance(labels, DeviceArray) and labels.ndim == 1:
@@ -105,26 +108,49 @@ def _describe_label_source(labels, device, streams, what="label image"):
     lp, lmem, lshape, ldt, lstr, keep = describe(labels, 2, what, device, streams)
     if ldt.name not in _lib.LBL_CODES:
         raise ValueError("%s dtype must be one of %s, got %s" % (what, "/".join(_lib.LBL_CODES), ldt))
-    return lp, lmem, (int(lshape[0]), int(lshape[1])), _lib.LBL_CODES[ldt.name], tuple(lstr), keep
+    return lp, lmem, (int(lshape[0]), int(lshape[1])), _lib.LBL_CODES[ldt.name], tuple(lstr), keep, 0
 
 
-def prepare_labels_device(labels, classes, size=None, resize=None, label_map=None, device=0):
+def _prepared_entry(name, m, w, h, channels):
+    """(function, trailing arguments) of the entry point `name` that prepares label images: its `_colors` form (smesh_label_colors.h)
+    for a `ColorTable`, else its `_prepared` form (smesh_label_prep.h) for `check_label_map`'s result."""
+    if isinstance(m, ColorTable):
+        return getattr(_lib.lib(), name + "_colors"), (w, h, channels) + m._args()
+    return getattr(_lib.lib(), name + "_prepared"), (w, h) + _map_args(m)
+
+
+def _palette_or_map(palette, label_map, images, classes, device):
+    """`palette=` and `label_map=` of a label entry point as ONE value for the code below: None, `check_label_map`'s result, or a
+    `ColorTable`.  A `ColorRemap` is first updated with the call's images (label_colors.resolve_palette) and then stands for its
+    table -- for 2-D masks a label map, key = value."""
+    m = check_label_map(label_map)
+    pal = check_palette(palette, m)
+    if pal is None:
+        return m
+    table, remapped = resolve_palette(pal, images, classes, device)
+    return table if table is not None else check_label_map(remapped)
+
+
+def prepare_labels_device(labels, classes, size=None, resize=None, label_map=None, device=0, palette=None):
     """The dense (W,H) plane the label fusion and the confusion matrices read, built ON THE DEVICE from a label image at its own
     resolution and in the dataset's ids (`smesh_labels_prepare`, include/smesh_label_prep.h): `labels` integer (w,h), host numpy or
     device array, any non-negative strides; `size` = (W,H), None: the image's own; `resize="nearest"` samples a (w,h) != (W,H) image
     with half-pixel centres (without it such a pair is refused); `label_map`, a one-dimensional integer table, turns source value v
     into map[v] AFTER sampling (v outside the table: don't care).  Every value outside [0, classes) becomes the all-ones code.
+    `palette` (instead of `label_map`): `labels` is a (w,h,3) / (w,h,4) uint8 COLOUR image and a pixel gets the class of its colour
+    -- a (K,3) uint8 array (class = row), a `ColorTable`, or a `ColorRemap`, which is first updated with this image and also takes a
+    2-D mask (`smesh_labels_prepare_colors`, include/smesh_label_colors.h); a colour outside the palette is don't care.
     Returns a `DeviceArray`, uint8 for up to 255 classes, else uint16."""
     from .device import DeviceBuffer
     mode = label_resize_mode(resize)
-    m = check_label_map(label_map)
     classes = int(classes)
     if not 0 < classes <= 65535:
         raise ValueError("classes must be in [1, 65535]")
     if isinstance(labels, DeviceArray):
         device = labels.device
+    m = _palette_or_map(palette, label_map, [labels], classes, int(device))
     streams = []
-    lp, lmem, (w, h), lcode, lstr, keep = _describe_label_source(labels, int(device), streams)
+    lp, lmem, (w, h), lcode, lstr, keep, ch = _describe_label_source(labels, int(device), streams, m=m)
     W, H = (w, h) if size is None else (int(size[0]), int(size[1]))
     if (W, H) != (w, h) and mode is None:
         raise ValueError('label image is %s, the target %s: pass resize="nearest" to sample it' % ((w, h), (W, H)))
@@ -132,16 +158,21 @@ def prepare_labels_device(labels, classes, size=None, resize=None, label_map=Non
         raise ValueError("an empty label image %s cannot be resampled to %s" % ((w, h), (W, H)))
     dt = np.dtype(np.uint8 if classes <= 255 else np.uint16)
     out = DeviceBuffer(max(W * H * dt.itemsize, 1), int(device)).view((W, H), dt)
-    mp, mlen, mmem = _map_args(m)
-    _lib.check(_lib.lib().smesh_labels_prepare(ctypes.c_void_p(lp), lcode, _c64(lstr), lmem, w, h, mp, mlen, mmem, classes,
-                                               ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], W, H, int(device)))
+    if isinstance(m, ColorTable):
+        kp, cp, K = m._args()
+        _lib.check(_lib.lib().smesh_labels_prepare_colors(ctypes.c_void_p(lp), ch, _c64(lstr), lmem, w, h, kp, cp, K, classes,
+                                                          ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], W, H, int(device)))
+    else:
+        mp, mlen, mmem = _map_args(m)
+        _lib.check(_lib.lib().smesh_labels_prepare(ctypes.c_void_p(lp), lcode, _c64(lstr), lmem, w, h, mp, mlen, mmem, classes,
+                                                   ctypes.c_void_p(out.ptr), _lib.LBL_CODES[dt.name], W, H, int(device)))
     release_to(int(device), streams)
     return out
 
 
-def prepare_labels(labels, classes, size=None, resize=None, label_map=None, device=0):
+def prepare_labels(labels, classes, size=None, resize=None, label_map=None, device=0, palette=None):
     """`prepare_labels_device` copied to the host: a numpy array."""
-    return prepare_labels_device(labels, classes, size, resize, label_map, device).numpy()
+    return prepare_labels_device(labels, classes, size, resize, label_map, device, palette).numpy()
 
 
 def probs_code(dtype, keep=None, probs_dtype=None, what="probs image"):
@@ -660,22 +691,21 @@ class _MeshAggregator:
         if m is None and self._shape_of(label_image) == ishape:
             return False
         streams = []
-        lp, lmem, (w, h), lcode, lstr, k1 = _describe_label_source(label_image, self.device, streams)
+        lp, lmem, (w, h), lcode, lstr, k1, ch = _describe_label_source(label_image, self.device, streams, m=m)
         wdesc = None if weights_image is None else self._describe_weights(weights_image, streams)
         if len(ishape) != 2 or (mode is None and (w, h) != ishape) or (wdesc is not None and wdesc[2] != ishape):
             raise ValueError("Primitive image %s, label image %s and weights image %s must have the same width and height"
                              % (ishape, (w, h), None if wdesc is None else wdesc[2]))
         if ishape[0] and ishape[1] and not (w and h):
             raise ValueError("an empty label image %s cannot be resampled to %s" % ((w, h), ishape))
-        mp, mlen, mmem = _map_args(m)
         lazy = getattr(primitive_image, "unrun", False) and primitive_image._which == 0 and primitive_image.device == self.device
         if lazy and (wdesc is None or (wdesc[3] == (ishape[1], 1) and wdesc[1] == lmem)):
             pend = primitive_image._pending
             if pend.W and pend.H:
                 self.flush()
-                _lib.check(_lib.lib().smesh_fuse_view_labels_prepared(
-                    pend.renderer._h, self._handle, ctypes.byref(pend.pod), ctypes.c_void_p(lp), lcode, _c64(lstr),
-                    None if wdesc is None else ctypes.c_void_p(wdesc[0]), lmem, w, h, mp, mlen, mmem))
+                fn, tail = _prepared_entry("smesh_fuse_view_labels", m, w, h, ch)
+                _lib.check(fn(pend.renderer._h, self._handle, ctypes.byref(pend.pod), ctypes.c_void_p(lp), lcode, _c64(lstr),
+                              None if wdesc is None else ctypes.c_void_p(wdesc[0]), lmem, *tail))
                 release_to(self.device, streams)
                 self._hold([k1 if lmem == _lib.MEM_DEVICE else None, wdesc[4] if (wdesc is not None and wdesc[1] == _lib.MEM_DEVICE) else None])
             return True
@@ -690,16 +720,16 @@ class _MeshAggregator:
                 and rb.device == self.device):
             rb = None
         wp, wmem, wstr, k2 = (None, _lib.MEM_HOST, None, None) if wdesc is None else (wdesc[0], wdesc[1], wdesc[3], wdesc[4])
-        _lib.check(_lib.lib().smesh_aggregator_add_labels_prepared(
-            self._h, None if rb is None else rb._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
-            ctypes.c_void_p(lp), lcode, _c64(lstr), lmem,
-            None if wp is None else ctypes.c_void_p(wp), None if wstr is None else _c64(wstr), wmem, W, H, w, h, mp, mlen, mmem))
+        fn, tail = _prepared_entry("smesh_aggregator_add_labels", m, w, h, ch)
+        _lib.check(fn(self._h, None if rb is None else rb._h, ctypes.c_void_p(ip), _IDX_CODES[idt], _c64(istr), imem,
+                      ctypes.c_void_p(lp), lcode, _c64(lstr), lmem,
+                      None if wp is None else ctypes.c_void_p(wp), None if wstr is None else _c64(wstr), wmem, W, H, *tail))
         release_to(self.device, streams)
         self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if lmem == _lib.MEM_DEVICE else None,
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
         return True
 
-    def add_labels(self, primitive_image, label_image, weights_image=None, resize=None, label_map=None):
+    def add_labels(self, primitive_image, label_image, weights_image=None, resize=None, label_map=None, palette=None):
         """`add(primitive_image, one_hot(label_image), weights_image)` without the one-hot: `label_image` is (W,H) of uint8 / int8 /
         uint16 / int16 / uint32 / int32 / uint64 / int64 -- a class index per pixel, host numpy or device array, any non-negative strides
         (a mask decoded as (H,W) and passed as its transposed view is fine).  `one_hot` is tf.one_hot: a label outside [0, classes),
@@ -711,8 +741,12 @@ class _MeshAggregator:
         `resize="nearest"`: a `label_image` (w,h) of another size than the index image is sampled at half-pixel centres on the device;
         `label_map`: a one-dimensional integer table, source value v becomes map[v] after sampling (`prepare_labels_device` states
         the rule).  With either in play the views already deferred are handed over first and this view is a call of its own; with
-        equal sizes and no map the call is the plain one.  Without `resize` a mask of another size is refused."""
-        mode, m = label_resize_mode(resize), check_label_map(label_map)
+        equal sizes and no map the call is the plain one.  Without `resize` a mask of another size is refused.
+        `palette` (instead of `label_map`): `label_image` is a (w,h,3) / (w,h,4) uint8 colour image, a decoded (H,W,3) PNG passed as
+        `image.transpose(1, 0, 2)`; a (K,3) uint8 array (class = row), a `ColorTable`, or a `ColorRemap` that this call first updates
+        with the image -- more colours than classes afterwards is a ValueError -- and that also takes a 2-D mask
+        (include/smesh_label_colors.h).  A call of its own, like `label_map`."""
+        mode, m = label_resize_mode(resize), _palette_or_map(palette, label_map, [label_image], self.classes, self.device)
         if type(primitive_image).__name__ == "PyCapsule":
             from . import dlpack
             own = dlpack.own_capsule_owner(primitive_image)
@@ -758,23 +792,22 @@ class _MeshAggregator:
         self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if lmem == _lib.MEM_DEVICE else None,
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
 
-    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None):
-        """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`
-        and `label_map`)."""
-        mode, m = label_resize_mode(resize), check_label_map(label_map)
+    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None, palette=None):
+        """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`,
+        `label_map` and `palette`)."""
+        mode, m = label_resize_mode(resize), _palette_or_map(palette, label_map, [label_image], self.classes, self.device)
         W, H = camera.resolution
         if m is not None or (mode is not None and self._shape_of(label_image) != (W, H)):
             streams = []
-            lp, lmem, (w, h), lcode, lstr, k1 = _describe_label_source(label_image, self.device, streams)
+            lp, lmem, (w, h), lcode, lstr, k1, ch = _describe_label_source(label_image, self.device, streams, m=m)
             if mode is None and (w, h) != (W, H):
                 raise ValueError("%s must be (W,H) = %s, got %s" % ("label image", (W, H), (w, h)))
             if W and H and not (w and h):
                 raise ValueError("an empty label image %s cannot be resampled to %s" % ((w, h), (W, H)))
             wp, k2 = self._prep_weights(weights_image, W, H, lmem, streams)
-            mp, mlen, mmem = _map_args(m)
-            _lib.check(_lib.lib().smesh_fuse_view_labels_prepared(
-                renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(lp), lcode, _c64(lstr),
-                None if wp is None else ctypes.c_void_p(wp), lmem, w, h, mp, mlen, mmem))
+            fn, tail = _prepared_entry("smesh_fuse_view_labels", m, w, h, ch)
+            _lib.check(fn(renderer._h, self._h, ctypes.byref(camera._pod), ctypes.c_void_p(lp), lcode, _c64(lstr),
+                          None if wp is None else ctypes.c_void_p(wp), lmem, *tail))
             release_to(self.device, streams)
             self._hold([k1 if lmem == _lib.MEM_DEVICE else None, k2 if lmem == _lib.MEM_DEVICE else None])
             return
@@ -804,7 +837,7 @@ class _MeshAggregator:
         streams, desc = [], []
         for i, cam in enumerate(cameras):
             W, H = cam.resolution
-            d = _describe_label_source(label_images[i], self.device, streams, "label image %d" % i)
+            d = _describe_label_source(label_images[i], self.device, streams, "label image %d" % i, m=m)
             if mode is None and d[2] != (W, H):
                 raise ValueError("%s must be (W,H) = %s, got %s" % ("label image %d" % i, (W, H), d[2]))
             if W and H and not (d[2][0] and d[2][1]):
@@ -812,35 +845,39 @@ class _MeshAggregator:
             w = None if weights_images is None else weights_images[i]
             desc.append((d, self._prep_weights(w, W, H, d[1], streams, "weights image %d" % i)))
         first = desc[0][0]
-        if not all(d[1:5] == first[1:5] and (dw[0] is None) == (desc[0][1][0] is None) for d, dw in desc):
+        if not all(d[1:5] == first[1:5] and d[6] == first[6] and (dw[0] is None) == (desc[0][1][0] is None) for d, dw in desc):
             release_to(self.device, streams)
+            table = m if isinstance(m, ColorTable) else None
             for i in range(n):
                 self.fuse_view_labels(renderer, cameras[i], label_images[i], None if weights_images is None else weights_images[i],
-                                      resize, m)
+                                      resize, None if table is not None else m, table)
             return
         pods = (_lib.CameraPOD * n)(*[cam._pod for cam in cameras])
         lptr = (ctypes.c_void_p * n)(*[d[0] for d, _ in desc])
         wptr = None if desc[0][1][0] is None else (ctypes.c_void_p * n)(*[dw[0] for _, dw in desc])
-        mp, mlen, mmem = _map_args(m)
-        _lib.check(_lib.lib().smesh_fuse_views_labels_prepared(renderer._h, self._h, pods, n, lptr, first[3], _c64(first[4]), wptr, first[1],
-                                                                first[2][0], first[2][1], mp, mlen, mmem))
+        fn, tail = _prepared_entry("smesh_fuse_views_labels", m, first[2][0], first[2][1], first[6])
+        _lib.check(fn(renderer._h, self._h, pods, n, lptr, first[3], _c64(first[4]), wptr, first[1], *tail))
         release_to(self.device, streams)
         if first[1] == _lib.MEM_DEVICE:
             self._hold([d[5] for d, _ in desc] + [dw[1] for _, dw in desc])
 
-    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None):
+    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None, palette=None):
         """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
         views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
         and memory go to the library as one batch; a mixed list is fused view by view.  `resize="nearest"` / `label_map` (see
         add_labels): the fast form for masks at the network's resolution or in the dataset's ids -- images that also share their
-        size are prepared and fused by the library in batches of eight."""
+        size are prepared and fused by the library in batches of eight.  `palette` (see add_labels): colour images; a `ColorRemap`
+        is first updated with all the call's images, in their order -- their distinct colours are found on the device, eight images
+        per synchronisation -- and must then hold no more colours than the aggregator has classes."""
         mode, m = label_resize_mode(resize), check_label_map(label_map)
         cameras, label_images = list(cameras), list(label_images)
         n = len(cameras)
         if len(label_images) != n or (weights_images is not None and len(weights_images) != n):
             raise ValueError("fuse_views_labels needs one label image (and one weights image or None) per camera")
         if n == 0:
+            check_palette(palette, m)
             return
+        m = _palette_or_map(palette, m, label_images, self.classes, self.device)
         if m is not None or (mode is not None and any(self._shape_of(label_images[i]) != tuple(cam.resolution) for i, cam in enumerate(cameras))):
             return self._fuse_views_labels_prepared(renderer, cameras, label_images, weights_images, resize, mode, m)
         streams, desc = [], []
@@ -1426,3 +1463,5 @@ from .evaluation import ConfusionMatrix, confusion_accuracy, confusion_iou, conf
 from .evaluation import argmax_labels, argmax_labels_device  # noqa: E402,F401
 from .label_images import LabelRenderer  # noqa: E402,F401
 from .resize import resize_probs, resize_probs_device  # noqa: E402,F401
+from .label_colors import (ColorRemap, ColorTable, check_palette, describe_color_source, resolve_palette,  # noqa: E402,F401
+                           unique_colors)
