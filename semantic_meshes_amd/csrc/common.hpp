@@ -205,8 +205,8 @@ struct RenderedView {
   bool no_big = false;          // PROVEN on the host (raster.hip no_big_possible): no triangle of this view has a box over 8 x 8 pixels -- big_queue is empty
   const uint8_t* kinds = nullptr;   // texel renderers: TriFrag::kind of every triangle again, a byte each (RasterArgs::kinds)
   bool fine = false;            // bounded on the host (raster.hip box_extent_bound <= 48 pixels): a finely tessellated mesh seen from outside -- few or no queued triangles
-  const void* labels = nullptr; // label views (fusion_labels.hip): the dense uint8 / uint16 label plane [W][H] that stands in for `probs`
-  const void* probs16 = nullptr;   // 16-bit class-vector views (fusion_half.hip): the float16 / bfloat16 image [W][H][C] that stands in for `probs` (strides: ps0, ps1)
+  const void* image = nullptr;  // what stands in for `probs` in the views of k_fuse_tri_labels, k_fuse_tri_h16 and k_fuse_tri_sampled: the dense label
+                                // plane [W][H], the 16-bit image [W][H][C] (strides: ps0, ps1), the network's (w,h,C) image (view_input.hpp)
 };
 
 // Medium triangles: a bounding box over 8 x 8 pixels of at most kMidBox pixels (16 x 16: beyond that a whole wave per triangle --

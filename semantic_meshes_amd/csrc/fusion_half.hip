@@ -22,6 +22,7 @@
 #include <cmath>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 using namespace smesh;
 
@@ -32,17 +33,19 @@ bool smesh_aggregator_can_fuse_triangles(smesh_aggregator* a, uint64_t F);
 int smesh_aggregator_refuse_scattered(smesh_aggregator* a, const char* what);
 void smesh_aggregator_label_target(smesh_aggregator* a, float** acc, uint64_t* P, uint32_t* C, int* kind, float* iew);
 HalfScratch& smesh_aggregator_half_scratch(smesh_aggregator* a);
+void smesh_set_last_fuse_instance(int slot, int views);
 // raster.hip
 struct smesh_renderer;
 DeviceCtx* smesh_renderer_ctx(smesh_renderer* r);
 int smesh_renderer_fuse_views_half(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
-                                   const float* const* weights, int probs_dtype);
-int smesh_renderer_add_rendered_half(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* probs, int probs_dtype,
-                                     int64_t ps0, int64_t ps1, const float* weights, uint64_t W, uint64_t H, int* done);
+                                   const float* const* weights, const ViewInput& in);
+int smesh_renderer_add_rendered_input(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const ViewInput& in, const float* weights,
+                                      uint64_t W, uint64_t H, int* done);
 
 namespace {
 
 #include "fuse_tri.inc.hpp"
+#include "fuse_rows.inc.hpp"
 
 // One view as k_fuse_tri_h16 sees it (TriView with 16-bit class vectors).
 struct HalfView {
@@ -71,14 +74,7 @@ struct HalfFuseArgs {
 };
 
 // A row is 2 * C bytes at 2-byte alignment (38 bytes at 19 classes).  It is loaded in the widest pieces its length allows -- 16 bytes
-// per eight classes, then 8, 4 and 2 for what is left -- through pointer types that state the alignment there really is; gfx950
-// global memory takes them at any address.  Never past the row's end: the last pixel's row ends the allocation.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4_a2 __attribute__((aligned(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef u32x2 u32x2_a2 __attribute__((aligned(2)));
-typedef uint32_t u32_a2 __attribute__((aligned(2)));
-
+// per eight classes, then 8, 4 and 2 for what is left (load_part16) -- through fuse_rows.inc.hpp's pointer types.
 // The row at `pr` into CT float32 registers, C <= CT run-time classes with CT = the multiple of eight at or above C: every chunk of
 // eight but the last is full.  Elements c >= C come out as +0.
 template <int CT>
@@ -95,147 +91,11 @@ __device__ __forceinline__ void load_row16(const uint16_t* __restrict__ pr, int 
     const u32x4 q = *reinterpret_cast<const u32x4_a2*>(pr + L);
     w[L / 2] = q.x; w[L / 2 + 1] = q.y; w[L / 2 + 2] = q.z; w[L / 2 + 3] = q.w;
   } else {
-    const int r = C - L;        // 1 .. 7 (wave-uniform)
-    u32x2 t8 = {0u, 0u};
-    uint32_t t4 = 0u, t2 = 0u;
-    if (r & 4) t8 = *reinterpret_cast<const u32x2_a2*>(pr + L);
-    if (r & 2) t4 = *reinterpret_cast<const u32_a2*>(pr + L + (r & 4));
-    if (r & 1) t2 = (uint32_t)pr[L + (r & 6)];
-    const uint32_t rest0 = (r & 2) ? t4 : t2, rest1 = (r & 2) ? t2 : 0u;   // what follows the 8-byte piece, if there is one
-    w[L / 2] = (r & 4) ? t8.x : rest0;
-    w[L / 2 + 1] = (r & 4) ? t8.y : rest1;
-    w[L / 2 + 2] = (r & 4) ? rest0 : 0u;
-    w[L / 2 + 3] = (r & 4) ? rest1 : 0u;
+    const u32x4 q = load_part16(pr + L, C - L);   // 1 .. 7 elements (wave-uniform)
+    w[L / 2] = q.x; w[L / 2 + 1] = q.y; w[L / 2 + 2] = q.z; w[L / 2 + 3] = q.w;
   }
 #pragma unroll
   for (int c = 0; c < CT; c += 2) unpack2(w[c / 2], bf, p[c], p[c + 1]);
-}
-
-// Mesh.h:94-106 for one pixel's widened class vector `p` with weight `w` into `dst` (a row in registers, or a tail wave's partial sums).
-template <int CT, int KIND>
-__device__ __forceinline__ void add_pixel(const float (&p)[CT], int C, float w, float (&dst)[CT]) {
-  if (KIND == SMESH_AGG_SUMMAX) {
-    int am = 0;
-    float best = p[0];   // (not p[am]: a run-time register index would go through scratch)
-#pragma unroll
-    for (int c = 1; c < CT; c++) if (c < C) if (p[c] > best) { best = p[c]; am = c; }
-#pragma unroll
-    for (int c = 0; c < CT; c++) if (c < C) if (c == am) dst[c] = dst[c] + p[c] * w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < CT; c++) if (c < C) dst[c] = dst[c] + p[c] * w;
-  }
-}
-
-template <int CT>
-__device__ __forceinline__ float row_sum(const float (&p)[CT], int C) {
-  float sum = 0.0f;
-#pragma unroll
-  for (int c = 0; c < CT; c++) if (c < C) sum = sum + p[c];   // tt::sum, sequential float32
-  return sum;
-}
-
-// One queued triangle `f` in one view: one WAVE, lanes over the pixels of the box [x0, x1] x [y0, y1] of the view's index plane,
-// per-lane partial sums combined by a butterfly; lane c then adds class c to the row, which nobody else touches in this launch.  A
-// tree order: the 1e-5 path, like fuse_box.
-template <int CT, int KIND>
-__device__ __forceinline__ void fuse_box16(const HalfFuseArgs& a, const HalfView& vw, const uint32_t f, const int x0, const int y0, const int x1,
-                                           const int y1) {
-  const int C = (int)a.C;
-  const int l = threadIdx.x;
-  const bool bf = a.bf16 != 0u;
-  const uint32_t bh = (uint32_t)(y1 - y0 + 1);
-  const uint32_t npx = (uint32_t)(x1 - x0 + 1) * bh;   // (W, H <= 65536 and W * H < 2^29: fits)
-  const uint32_t* __restrict__ idx = vw.idx;
-  uint32_t cnt = 0;
-  for (uint32_t i = l; i < npx; i += kWave) cnt += idx[(uint64_t)((uint32_t)x0 + i / bh) * vw.H + ((uint32_t)y0 + i % bh)] == f ? 1u : 0u;
-  const uint32_t n = wave_sum_u(cnt);
-  if (n == 0) return;
-  const float w0 = a.iew * (1.0f / (float)n) + (1 - a.iew) * 1.0f;
-  float part[CT];
-#pragma unroll
-  for (int c = 0; c < CT; c++) part[c] = 0.0f;
-  for (uint32_t i = l; i < npx; i += kWave) {
-    const uint32_t x = (uint32_t)x0 + i / bh, y = (uint32_t)y0 + i % bh;
-    const uint64_t pix = (uint64_t)x * vw.H + y;
-    if (idx[pix] != f) continue;
-    float p[CT];
-    load_row16<CT>(vw.probs + ((uint64_t)x * vw.ps0 + (uint64_t)y * vw.ps1), C, bf, p);
-    if (!(row_sum<CT>(p, C) > 0.5f)) continue;                                  // Mesh.h:98
-    const float w = w0 * (vw.weights ? vw.weights[pix] : 1.0f);                 // :103
-    add_pixel<CT, KIND>(p, C, w, part);
-  }
-  float mine = 0.0f;
-#pragma unroll
-  for (int c = 0; c < CT; c++) if (c < C) {
-    const float v = wave_sum(part[c]);
-    if (l == c) mine = v;
-  }
-  if (l < C) {
-    float* __restrict__ row = a.acc + (uint64_t)f * C;
-    row[l] = row[l] + mine;
-  }
-}
-
-// Triangles with a box over 8 x 8 pixels in some view of the launch: one wave per queued triangle for ALL its views, first view first,
-// so that no other wave touches its row (the main waves leave such triangles alone).  The views in which the triangle is small are
-// scanned as 8 x 8 boxes of THEIR index planes -- which is why the raster launch ahead of this kernel writes all planes as soon as one
-// view has a queued triangle (raster.hip, kLabelsPlaneLevel).  The walk over the concatenated queues is fuse_big_triangles'.
-template <int CT, int KIND, int NV>
-__device__ __forceinline__ void fuse_big16(const HalfFuseArgs& a, const HalfViews<NV>& vw, uint32_t worker, uint32_t nworkers) {
-  uint32_t len[NV], total = 0u;
-#pragma unroll
-  for (int v = 0; v < NV; v++) { len[v] = min(*vw.v[v].big_len, a.big_capacity); total += len[v]; }
-  const int l = threadIdx.x;
-  const uint32_t chunk = max(1u, min((uint32_t)kWave, total / max(nworkers, 1u)));
-  const uint32_t steps = (total + chunk - 1u) / chunk;
-  for (uint32_t step = worker; step < steps; step += nworkers) {
-    const uint32_t q = (uint32_t)l < chunk ? (uint32_t)l * steps + step : total;
-    uint32_t fi = 0u;
-    bool take = false;
-    {
-      uint32_t qq = q;
-      bool located = q >= total;
-      int jsel = -1;
-#pragma unroll
-      for (int j = 0; j < NV; j++) {
-        if (!located) {
-          if (qq < len[j]) { fi = vw.v[j].big_queue[qq]; jsel = j; located = true; }
-          else qq -= len[j];
-        }
-      }
-      if (jsel >= 0 && fi < a.F) {
-        bool mine = false, earlier = false;
-#pragma unroll
-        for (int i = 0; i < NV; i++) {
-          if (i <= jsel) {
-            const bool counts = vw.v[i].frags[fi].kind == 2;
-            if (i < jsel) earlier = earlier || counts;
-            else mine = counts;
-          }
-        }
-        take = mine && !earlier;   // a triangle queued by several views is taken from the queue of the first of them
-      }
-    }
-    unsigned long long todo = __ballot(take);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fi, src);   // wave-uniform; row = triangle (no re-ordered meshes here)
-#pragma unroll
-      for (int j = 0; j < NV; j++) {
-        const TriFrag rec = vw.v[j].frags[f];
-        if (rec.kind == 0) continue;
-        const int x0 = rec.x0, y0 = rec.y0;
-        int x1, y1;
-        if (rec.kind == 2) { x1 = (int)(rec.mask & 0xFFFFu); y1 = (int)((rec.mask >> 16) & 0xFFFFu); }
-        else { x1 = x0 + 7; y1 = y0 + 7; }
-        x1 = min(x1, (int)vw.v[j].W - 1); y1 = min(y1, (int)vw.v[j].H - 1);
-        if (x1 < x0 || y1 < y0) continue;
-        fuse_box16<CT, KIND>(a, vw.v[j], f, x0, y0, x1, y1);
-      }
-    }
-  }
 }
 
 // NV views (1, 2, 4 or 8) of 16-bit class vectors into the accumulator in ONE launch, in order: k_fuse_tri's structure.  Lane =
@@ -251,53 +111,26 @@ template <int CT, int KIND, int NV>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(fuse_h16_min_waves(CT)))) void k_fuse_tri_h16(HalfFuseArgs a, HalfViews<NV> vw) {
   const int C = (int)a.C;
   constexpr int PB = CT <= 16 ? 2 : 1;        // pixels whose class vectors are in flight together (k_fuse_tri: two up to 24 slots; here see the budget above)
-  constexpr int KV = (kWave * CT / 4 + kWave - 1) / kWave;   // float4 per lane of the 64-row block
+  constexpr int KV = rows_quads(CT);
   __shared__ __attribute__((aligned(16))) float srow[kWave * CT + 4];   // the wave's 64 accumulator rows
   const int l = threadIdx.x;
   const bool bf = a.bf16 != 0u;
   if (blockIdx.x >= a.tri_blocks) {
-    fuse_big16<CT, KIND, NV>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks);
+    for_each_queued_triangle<NV, true>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks,
+                                       [&](const uint32_t f, const int j, const int x0, const int y0, const int x1, const int y1) __attribute__((always_inline)) {
+      const HalfView& view = vw.v[j];
+      fuse_box_rows<CT, KIND>(a, view, f, x0, y0, x1, y1, [&](const uint32_t x, const uint32_t y, float (&p)[CT]) __attribute__((always_inline)) {
+        load_row16<CT>(view.probs + ((uint64_t)x * view.ps0 + (uint64_t)y * view.ps1), C, bf, p);
+      });
+    });
     return;
   }
   const uint64_t f0 = (uint64_t)blockIdx.x * kWave;
   const uint64_t f = f0 + l;
-  // per view: box origin (x0 | y0 << 16) and the mask of this triangle's VISIBLE pixels inside its <= 8 x 8 box
   uint32_t org[NV];
   unsigned long long msk[NV];
-  bool big = false;   // a box over 8 x 8 in some view: the triangle is a tail wave's for all its views, and so is its row
-#pragma unroll
-  for (int v = 0; v < NV; v++) { org[v] = 0u; msk[v] = 0ull; }
-  if (f < a.F) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      const TriFrag rec = vw.v[v].frags[f];
-      org[v] = (uint32_t)rec.x0 | ((uint32_t)rec.y0 << 16);
-      msk[v] = rec.kind == 1 ? rec.mask : 0ull;
-      big = big || rec.kind == 2;
-    }
-  }
-  if (big) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) msk[v] = 0ull;
-  }
-  // the masks of a view whose render says they need checking (fragment-queue overflow, direct rasteriser) are checked against that
-  // view's index plane, which such a view always writes (k_fuse_tri's pass 1)
-#pragma unroll
-  for (int v = 0; v < NV; v++) {
-    if (vw.v[v].big_len[1] == 0u) continue;
-    const uint32_t* __restrict__ idx = vw.v[v].idx;
-    unsigned long long m = msk[v], win = 0ull;
-    while (m) {
-      const int k = __ffsll((long long)m) - 1;
-      m &= m - 1ull;
-      const uint64_t pix = (uint64_t)((org[v] & 0xFFFFu) + (uint32_t)(k >> 3)) * vw.v[v].H + (org[v] >> 16) + (uint32_t)(k & 7);
-      if (idx[pix] == (uint32_t)f) win |= 1ull << k;
-    }
-    msk[v] = win;
-  }
-  unsigned long long any_win = 0ull;
-#pragma unroll
-  for (int v = 0; v < NV; v++) any_win |= msk[v];
+  bool big;
+  const unsigned long long any_win = visible_masks<NV>(a, vw, f, org, msk, big);
   if (__ballot(any_win != 0ull) == 0ull) return;   // nothing of these 64 triangles is visible: rows untouched
 
   // ---- issue together: the wave's 64 accumulator rows (one contiguous block) and the first PB pixels' class vectors of every lane
@@ -361,24 +194,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(fuse_h16_
       }
     }
   }
-  // each lane parks its row ...
-#pragma unroll
-  for (int c = 0; c < CT; c++) if (c < C) srow[l * C + c] = accr[c];
-  wave_sync();
-  if (nrows != kWave || __ballot(big) != 0ull) {
-    // some of these 64 rows belong to queued triangles, which the tail waves of this launch update meanwhile (or the block is the
-    // mesh's last, partial one): every lane that added something stores its own row
-    if (any_win) {
-      float* __restrict__ row = a.acc + f * C;
-      const float* __restrict__ mine = srow + l * C;
-      for (int c = 0; c < C; c++) row[c] = mine[c];
-    }
-    return;
-  }
-  // ... and the block goes back as it came
-  f4* b4 = reinterpret_cast<f4*>(blk);
-  const f4* s4 = reinterpret_cast<const f4*>(srow);
-  for (int q = l; q < kWave * C / 4; q += kWave) b4[q] = s4[q];
+  store_rows<CT>(a.acc, srow, blk, f, nrows, C, big, any_win != 0ull, accr);
 }
 
 // Any strided (W,H,C) 16-bit image -> the dense float32 one the float32 kernels read.  DENSE (class stride 1, rows back to back):
@@ -433,8 +249,6 @@ __global__ __launch_bounds__(256) void k_narrow_probs(const float* __restrict__ 
   }
 }
 
-constexpr int kGroup = 8;   // views whose staged images share the aggregator's scratch: a group of smesh_fuse_views
-
 int check_half_dtype(int dt) {
   if (dt == SMESH_PROBS_F16 || dt == SMESH_PROBS_BF16) return SMESH_OK;
   if (dt == SMESH_PROBS_F32) return fail(SMESH_ERR_INVALID, "SMESH_PROBS_F32: float32 class vectors go through the entry points of smesh.h");
@@ -444,8 +258,6 @@ int check_half_dtype(int dt) {
 // Test hook SMESH_FUSE_H16=0: every 16-bit image takes the widening route.  Read at every call (one getenv beside a kernel launch), so
 // that tools/half_probs_bench.py measures both routes in one process.
 bool h16_enabled() { return env_int("SMESH_FUSE_H16", 1) != 0; }
-
-size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -463,67 +275,32 @@ bool smesh_half_native(smesh_aggregator* a, uint64_t F) {
 // Can k_fuse_tri_h16 read an image with these element strides in place?  (Class stride 1; x and y strides fit the kernel's 32 bits.)
 bool smesh_half_takes_strides(int64_t ps0, int64_t ps1) { return ps0 > 0 && ps1 > 0 && ps0 <= 0xFFFFFFFFll && ps1 <= 0xFFFFFFFFll; }
 
-// views[v].probs16: (W,H,C) images of `probs_dtype` in device memory, x / y strides views[v].ps0 / ps1 (0, 0: dense).  `nviews` = 1, 2, 4 or 8.
+// views[v].image: (W,H,C) images of `probs_dtype` in device memory, x / y strides views[v].ps0 / ps1 (0, 0: dense).  `nviews` = 1, 2, 4 or 8.
 int smesh_half_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int probs_dtype) {
   DeviceCtx* ctx = smesh_aggregator_ctx(a);
   hipStream_t st = ctx->stream;
   if (F == 0) return SMESH_OK;
-  SMESH_TRY(smesh_aggregator_refuse_scattered(a, "fuse_view_probs16()"));
-  SMESH_TRY(check_half_dtype(probs_dtype));
-  if (nviews != 1 && nviews != 2 && nviews != 4 && nviews != 8) return fail(SMESH_ERR_INVALID, "fuse_triangles_half: unsupported view count");
   HalfFuseArgs t;
-  uint64_t P;
   int kind;
-  smesh_aggregator_label_target(a, &t.acc, &P, &t.C, &kind, &t.iew);
-  if (kind == SMESH_AGG_MUL || P != F || t.C == 0 || t.C > kHalfMaxClasses)
-    return fail(SMESH_ERR_INVALID, "fuse_triangles_half: Sum / Summax over the renderer's triangles, at most 48 classes");
+  SMESH_TRY(check_half_dtype(probs_dtype));
+  SMESH_TRY(check_fuse_rows("fuse_triangles_half", "fuse_view_probs16()", a, F, nviews, kHalfMaxClasses, &t, &kind));
   HalfViews<8> tv;
-  bool no_big = true;   // every view PROVEN free of triangles over 8 x 8 pixels (RenderedView::no_big): no tail waves at all
   for (int v = 0; v < 8; v++) {
     const RenderedView& rv = views[v < nviews ? v : 0];
-    if (rv.W == 0 || rv.H == 0 || !rv.probs16) return fail(SMESH_ERR_INVALID, "fuse_triangles_half: class-vector image missing");
-    if (reinterpret_cast<uintptr_t>(rv.probs16) & 1) return fail(SMESH_ERR_INVALID, "fuse_triangles_half: 16-bit class vectors must be 2-byte aligned");
+    if (rv.W == 0 || rv.H == 0 || !rv.image) return fail(SMESH_ERR_INVALID, "fuse_triangles_half: class-vector image missing");
+    if (reinterpret_cast<uintptr_t>(rv.image) & 1) return fail(SMESH_ERR_INVALID, "fuse_triangles_half: 16-bit class vectors must be 2-byte aligned");
     const int64_t ps0 = (rv.ps0 || rv.ps1) ? rv.ps0 : (int64_t)(rv.H * t.C), ps1 = (rv.ps0 || rv.ps1) ? rv.ps1 : (int64_t)t.C;
     if (!smesh_half_takes_strides(ps0, ps1)) return fail(SMESH_ERR_INVALID, "fuse_triangles_half: class-vector strides out of range");
-    tv.v[v] = HalfView{rv.frags, rv.idx, static_cast<const uint16_t*>(rv.probs16), rv.weights, rv.big_queue, rv.big_len,
+    tv.v[v] = HalfView{rv.frags, rv.idx, static_cast<const uint16_t*>(rv.image), rv.weights, rv.big_queue, rv.big_len,
                        (uint32_t)rv.W, (uint32_t)rv.H, (uint32_t)ps0, (uint32_t)ps1};
-    no_big = no_big && rv.no_big;
   }
-  t.F = F;
-  t.big_capacity = big_capacity;
-  t.tri_blocks = (uint32_t)div_up(F, kWave);
-  t.big_blocks = no_big ? 0u : 16u * (uint32_t)std::max(1, ctx->num_cus);
+  const dim3 grid = fuse_rows_grid(ctx, F, big_capacity, views, nviews, &t), block(kWave);
   t.bf16 = probs_dtype == SMESH_PROBS_BF16 ? 1u : 0u;
-  const dim3 grid(t.tri_blocks + t.big_blocks), block(kWave);
-  const int ct = (int)((t.C + 7u) / 8u) * 8;
   ProfScope prof(ctx, SMESH_PROF_FUSE_SCATTER);
   prof_note(ctx, SMESH_PROF_FUSE_SCATTER, 1, (uint64_t)nviews);
-#define SMESH_FH(CT, KIND, NV)                                                      \
-  {                                                                                 \
-    HalfViews<NV> w;                                                                \
-    for (int v = 0; v < NV; v++) w.v[v] = tv.v[v];                                  \
-    hipLaunchKernelGGL((k_fuse_tri_h16<CT, KIND, NV>), grid, block, 0, st, t, w);   \
-  }
-#define SMESH_FHV(CT, KIND)                    \
-  switch (nviews) {                            \
-    case 1: SMESH_FH(CT, KIND, 1) break;       \
-    case 2: SMESH_FH(CT, KIND, 2) break;       \
-    case 4: SMESH_FH(CT, KIND, 4) break;       \
-    default: SMESH_FH(CT, KIND, 8) break;      \
-  }
-#define SMESH_FHK(CT)                                                                     \
-  if (kind == SMESH_AGG_SUMMAX) { SMESH_FHV(CT, SMESH_AGG_SUMMAX) } else { SMESH_FHV(CT, SMESH_AGG_SUM) }
-  switch (ct) {
-    case 8:  SMESH_FHK(8) break;
-    case 16: SMESH_FHK(16) break;
-    case 24: SMESH_FHK(24) break;
-    case 32: SMESH_FHK(32) break;
-    case 40: SMESH_FHK(40) break;
-    default: SMESH_FHK(48) break;
-  }
-#undef SMESH_FHK
-#undef SMESH_FHV
-#undef SMESH_FH
+  launch_fuse_rows<true>((int)((t.C + 7u) / 8u) * 8, kind, nviews, [&](auto CT, auto KIND, auto NV) {
+    hipLaunchKernelGGL((k_fuse_tri_h16<CT(), KIND(), NV()>), grid, block, 0, st, t, (first_views<HalfViews, NV()>(tv)));
+  });
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }
@@ -578,7 +355,7 @@ int smesh_fuse_views_probs16(smesh_renderer_t* r, smesh_aggregator_t* a, const s
   smesh_aggregator_label_target(a, nullptr, nullptr, &C, nullptr, nullptr);
   HalfScratch& hs = smesh_aggregator_half_scratch(a);
   std::lock_guard<std::mutex> g(hs.mu);
-  if (memkind == SMESH_MEM_DEVICE) return smesh_renderer_fuse_views_half(r, a, cams, n, probs, weights, probs_dtype);
+  if (memkind == SMESH_MEM_DEVICE) return smesh_renderer_fuse_views_half(r, a, cams, n, probs, weights, ViewInput::half(nullptr, probs_dtype));
   // host images, in groups of up to eight views: they cross PCIe at 16 bits into the scratch, which the next group's copies overwrite
   // behind this group's fusion on the main stream
   for (uint64_t i = 0; i < n; i += kGroup) {
@@ -596,21 +373,10 @@ int smesh_fuse_views_probs16(smesh_renderer_t* r, smesh_aggregator_t* a, const s
       SMESH_HIP(hipSetDevice(ctx->device));
       SMESH_TRY(hs.stage.reserve(slot_bytes * (size_t)m));
       if (weights) SMESH_TRY(hs.w.reserve(w_bytes * (size_t)m));
-      for (int v = 0; v < m; v++) {
-        const uint64_t N = cams[i + v].width * cams[i + v].height;
-        char* d = static_cast<char*>(hs.stage.ptr) + (size_t)v * slot_bytes;
-        SMESH_HIP(hipMemcpyAsync(d, probs[i + v], N * C * 2, hipMemcpyHostToDevice, ctx->stream));
-        dev[v] = d;
-        wts[v] = weights ? weights[i + v] : nullptr;
-        if (wts[v]) {
-          float* dw = reinterpret_cast<float*>(static_cast<char*>(hs.w.ptr) + (size_t)v * w_bytes);
-          SMESH_HIP(hipMemcpyAsync(dw, wts[v], N * 4, hipMemcpyHostToDevice, ctx->stream));
-          wts[v] = dw;
-        }
-      }
-      SMESH_HIP(hipStreamSynchronize(ctx->stream));   // the caller may reuse its host arrays once we return
+      SMESH_TRY(stage_host_group(ctx, &cams[i], m, &probs[i], weights ? &weights[i] : nullptr, &hs.stage, slot_bytes,
+                                 [&](int v) { return (size_t)(cams[i + v].width * cams[i + v].height * C * 2); }, hs.w, w_bytes, dev, wts));
     }
-    SMESH_TRY(smesh_renderer_fuse_views_half(r, a, &cams[i], (uint64_t)m, dev, weights ? wts : nullptr, probs_dtype));
+    SMESH_TRY(smesh_renderer_fuse_views_half(r, a, &cams[i], (uint64_t)m, dev, weights ? wts : nullptr, ViewInput::half(nullptr, probs_dtype)));
   }
   return SMESH_OK;
 }
@@ -655,7 +421,7 @@ int smesh_aggregator_add_probs16(smesh_aggregator_t* a, smesh_renderer_t* r, con
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     SMESH_HIP(hipSetDevice(ctx->device));
     if (probs_mem == SMESH_MEM_HOST) {   // the image's span crosses PCIe as it is, at 16 bits, and keeps its strides
-      const uint64_t span = 1 + (W - 1) * (uint64_t)ps[0] + (H - 1) * (uint64_t)ps[1] + (C - 1) * (uint64_t)ps[2];
+      const uint64_t span = source_span(ps, W, H, C);
       SMESH_TRY(hs.stage.reserve(span * 2));
       SMESH_HIP(hipMemcpyAsync(hs.stage.ptr, probs, span * 2, hipMemcpyHostToDevice, ctx->stream));
       d_probs = hs.stage.ptr;
@@ -669,7 +435,7 @@ int smesh_aggregator_add_probs16(smesh_aggregator_t* a, smesh_renderer_t* r, con
   }
   if (rendered && (ps[2] == 1 || C == 1) && smesh_half_takes_strides(ps[0], ps[1])) {
     int done = 0;
-    SMESH_TRY(smesh_renderer_add_rendered_half(a, r, static_cast<const uint32_t*>(indices), d_probs, probs_dtype, ps[0], ps[1], d_w, W, H, &done));
+    SMESH_TRY(smesh_renderer_add_rendered_input(a, r, static_cast<const uint32_t*>(indices), ViewInput::half(d_probs, probs_dtype, ps[0], ps[1]), d_w, W, H, &done));
     if (done) return SMESH_OK;
   }
   // everything else: the image widened on the device, then the float32 path unchanged (asynchronous for device images)

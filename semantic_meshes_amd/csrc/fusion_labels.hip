@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "labels_scratch.hpp"
+#include "view_input.hpp"
 #include "../../include/smesh_labels.h"
 #include "../../include/smesh_label_prep.h"
 #include "../../include/smesh_label_colors.h"
@@ -37,14 +38,16 @@ LabelScratch& smesh_aggregator_label_scratch(smesh_aggregator* a);
 // raster.hip
 struct smesh_renderer;
 DeviceCtx* smesh_renderer_ctx(smesh_renderer* r);
+void smesh_set_last_fuse_instance(int slot, int views);
 int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* planes,
-                                     const float* const* weights, int label_bytes);
-int smesh_renderer_add_rendered_labels(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* plane, int label_bytes,
-                                       const float* weights, uint64_t W, uint64_t H, int* done);
+                                     const float* const* weights, const ViewInput& in);
+int smesh_renderer_add_rendered_input(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const ViewInput& in, const float* weights,
+                                      uint64_t W, uint64_t H, int* done);
 
 namespace {
 
 #include "fuse_tri.inc.hpp"
+#include "fuse_rows.inc.hpp"
 
 // (kLabelsLdsMaxC, the class count up to which the main waves keep their rows in LDS: labels_scratch.hpp)
 
@@ -94,103 +97,47 @@ struct LabelRun<uint16_t> {
   __device__ __forceinline__ uint32_t pick(uint32_t i) const { return (uint32_t)((i < 4u ? lo : hi) >> (16u * (i & 3u))) & 0xFFFFu; }
 };
 
-// Triangles with a box over 8 x 8 pixels in some view of the launch: one wave per queued triangle for ALL its views, first view first,
-// so that no other wave touches its row (the main waves leave such triangles alone).  Lanes go over the box of each view (the record's
-// box, or the 8 x 8 box of a view in which the triangle is small) and test the index plane -- every view of the launch, which is why
-// the raster launch ahead of this kernel writes all planes as soon as one view has a queued triangle (raster.hip, kLabelsPlaneLevel).
-// IN_LDS: a view's hits go to a C-float LDS histogram by LDS float adds, which lane c then adds to element c of the row; else by
+// One queued triangle `f` in view `vw` (for_each_queued_triangle): lanes go over the box [x0, x1] x [y0, y1] of the view's index plane.
+// IN_LDS: the view's hits go to a C-float LDS histogram by LDS float adds, which lane c then adds to element c of the row; else by
 // float atomics to the row itself.  Either way a tree / atomic order: the 1e-5 path, like fuse_box.
-template <typename LT, int NV, bool IN_LDS>
-__device__ __forceinline__ void fuse_big_labels(const LabelFuseArgs& a, const LabelViews<NV>& vw, uint32_t worker, uint32_t nworkers,
-                                                float* __restrict__ hist) {
-  uint32_t len[NV], total = 0u;
-#pragma unroll
-  for (int v = 0; v < NV; v++) { len[v] = min(*vw.v[v].big_len, a.big_capacity); total += len[v]; }
+template <typename LT, bool IN_LDS>
+__device__ __forceinline__ void fuse_box_labels(const LabelFuseArgs& a, const LabelView& vw, const uint32_t f, const int x0, const int y0, const int x1,
+                                                const int y1, float* __restrict__ hist) {
   const int l = threadIdx.x;
   const uint32_t C = a.C;
-  // (the walk over the concatenated queues is fuse_big_triangles': `chunk` entries per step, one per lane; a triangle queued by several
-  // views is taken from the queue of the first of them)
-  const uint32_t chunk = max(1u, min((uint32_t)kWave, total / max(nworkers, 1u)));
-  const uint32_t steps = (total + chunk - 1u) / chunk;
-  for (uint32_t step = worker; step < steps; step += nworkers) {
-    const uint32_t q = (uint32_t)l < chunk ? (uint32_t)l * steps + step : total;
-    uint32_t fi = 0u;
-    bool take = false;
-    {
-      uint32_t qq = q;
-      bool located = q >= total;
-      int jsel = -1;
-#pragma unroll
-      for (int j = 0; j < NV; j++) {
-        if (!located) {
-          if (qq < len[j]) { fi = vw.v[j].big_queue[qq]; jsel = j; located = true; }
-          else qq -= len[j];
-        }
-      }
-      if (jsel >= 0 && fi < a.F) {
-        bool mine = false, earlier = false;
-#pragma unroll
-        for (int i = 0; i < NV; i++) {
-          if (i <= jsel) {
-            const bool counts = vw.v[i].frags[fi].kind == 2;
-            if (i < jsel) earlier = earlier || counts;
-            else mine = counts;
-          }
-        }
-        take = mine && !earlier;
-      }
+  float* __restrict__ row = a.acc + (uint64_t)f * C;
+  const uint32_t H = vw.H;
+  const uint32_t bh = (uint32_t)(y1 - y0 + 1);
+  const uint32_t npx = (uint32_t)(x1 - x0 + 1) * bh;
+  const uint32_t* __restrict__ idx = vw.idx;
+  auto pix_of = [&](uint32_t i) -> uint64_t { return (uint64_t)((uint32_t)x0 + i / bh) * H + ((uint32_t)y0 + i % bh); };
+  uint32_t cnt = 0;
+  for (uint32_t i = l; i < npx; i += kWave) cnt += idx[pix_of(i)] == f ? 1u : 0u;
+  const uint32_t n = wave_sum_u(cnt);
+  if (n == 0) return;
+  const float w0 = a.iew * (1.0f / (float)n) + (1 - a.iew) * 1.0f;
+  const LT* __restrict__ lab = static_cast<const LT*>(vw.labels);
+  const float* __restrict__ wts = vw.weights;
+  if (IN_LDS) {
+    for (uint32_t c = l; c < C; c += kWave) hist[c] = 0.0f;
+    wave_sync();
+  }
+  for (uint32_t i = l; i < npx; i += kWave) {
+    const uint64_t pix = pix_of(i);
+    if (idx[pix] != f) continue;
+    const uint32_t c = (uint32_t)lab[pix];
+    if (c >= C) continue;
+    const float w = w0 * (wts ? wts[pix] : 1.0f);
+    if (IN_LDS) __hip_atomic_fetch_add(&hist[c], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else unsafeAtomicAdd(&row[c], w);
+  }
+  if (IN_LDS) {
+    wave_sync();
+    for (uint32_t c = l; c < C; c += kWave) {
+      const float h = hist[c];
+      if (h != 0.0f) row[c] = row[c] + h;
     }
-    unsigned long long todo = __ballot(take);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fi, src);   // wave-uniform; row = triangle (no re-ordered meshes here)
-      float* __restrict__ row = a.acc + (uint64_t)f * C;
-#pragma unroll
-      for (int j = 0; j < NV; j++) {
-        const TriFrag rec = vw.v[j].frags[f];
-        if (rec.kind == 0) continue;
-        const uint32_t W = vw.v[j].W, H = vw.v[j].H;
-        const int x0 = rec.x0, y0 = rec.y0;
-        int x1, y1;
-        if (rec.kind == 2) { x1 = (int)(rec.mask & 0xFFFFu); y1 = (int)((rec.mask >> 16) & 0xFFFFu); }
-        else { x1 = x0 + 7; y1 = y0 + 7; }
-        x1 = min(x1, (int)W - 1); y1 = min(y1, (int)H - 1);
-        if (x1 < x0 || y1 < y0) continue;
-        const uint32_t bh = (uint32_t)(y1 - y0 + 1);
-        const uint32_t npx = (uint32_t)(x1 - x0 + 1) * bh;
-        const uint32_t* __restrict__ idx = vw.v[j].idx;
-        auto pix_of = [&](uint32_t i) -> uint64_t { return (uint64_t)((uint32_t)x0 + i / bh) * H + ((uint32_t)y0 + i % bh); };
-        uint32_t cnt = 0;
-        for (uint32_t i = l; i < npx; i += kWave) cnt += idx[pix_of(i)] == f ? 1u : 0u;
-        const uint32_t n = wave_sum_u(cnt);
-        if (n == 0) continue;
-        const float w0 = a.iew * (1.0f / (float)n) + (1 - a.iew) * 1.0f;
-        const LT* __restrict__ lab = static_cast<const LT*>(vw.v[j].labels);
-        const float* __restrict__ wts = vw.v[j].weights;
-        if (IN_LDS) {
-          for (uint32_t c = l; c < C; c += kWave) hist[c] = 0.0f;
-          wave_sync();
-        }
-        for (uint32_t i = l; i < npx; i += kWave) {
-          const uint64_t pix = pix_of(i);
-          if (idx[pix] != f) continue;
-          const uint32_t c = (uint32_t)lab[pix];
-          if (c >= C) continue;
-          const float w = w0 * (wts ? wts[pix] : 1.0f);
-          if (IN_LDS) __hip_atomic_fetch_add(&hist[c], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          else unsafeAtomicAdd(&row[c], w);
-        }
-        if (IN_LDS) {
-          wave_sync();
-          for (uint32_t c = l; c < C; c += kWave) {
-            const float h = hist[c];
-            if (h != 0.0f) row[c] = row[c] + h;
-          }
-          wave_sync();   // the histogram is cleared for this wave's next view
-        }
-      }
-    }
+    wave_sync();   // the histogram is cleared for this wave's next view
   }
 }
 
@@ -206,11 +153,16 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_labels(LabelFuseArgs a, Labe
   const int l = threadIdx.x;
   const uint32_t C = a.C;
   if (blockIdx.x >= a.tri_blocks) {
-    fuse_big_labels<LT, NV, IN_LDS>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks, srow);
+    for_each_queued_triangle<NV, true>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks,
+                                       [&](const uint32_t f, const int j, const int x0, const int y0, const int x1, const int y1) __attribute__((always_inline)) {
+      fuse_box_labels<LT, IN_LDS>(a, vw.v[j], f, x0, y0, x1, y1, srow);
+    });
     return;
   }
   const uint64_t f0 = (uint64_t)blockIdx.x * kWave;
   const uint64_t f = f0 + l;
+  // (the prologue of fuse_rows.inc.hpp's visible_masks, written out: as that helper it costs this kernel's eight-view instances 50 more
+  // SGPRs spilled into VGPR lanes -- 133 against 82 -- and 5 % of the kernel's time on cfg2, profiles/fuse_rows_refactor.md)
   // per view: box origin (x0 | y0 << 16) and the mask of this triangle's VISIBLE pixels inside its <= 8 x 8 box
   uint32_t org[NV];
   unsigned long long msk[NV];
@@ -373,8 +325,6 @@ __global__ __launch_bounds__(256) void k_labels_onehot(const LT* __restrict__ la
   out[e] = (uint32_t)lab[i] == (uint32_t)(e - i * C) ? 1.0f : 0.0f;
 }
 
-constexpr int kGroup = 8;   // views whose planes share the aggregator's label scratch (labels_scratch.hpp): a group of smesh_fuse_views
-
 size_t label_itemsize(int dt) { return (size_t)1 << (dt >> 1); }
 
 template <typename OUT>
@@ -509,54 +459,36 @@ bool smesh_labels_native(smesh_aggregator* a, uint64_t F, uint64_t N) {
   return kind != SMESH_AGG_MUL && F != 0 && N >= 8 && smesh_aggregator_can_fuse_triangles(a, F);
 }
 
-// views[v].labels: dense narrow planes of `label_bytes` (1 or 2) bytes per pixel in device memory.  `nviews` = 1, 2, 4 or 8.
+// views[v].image: dense narrow planes of `label_bytes` (1 or 2) bytes per pixel in device memory.  `nviews` = 1, 2, 4 or 8.
 int smesh_labels_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int label_bytes) {
   DeviceCtx* ctx = smesh_aggregator_ctx(a);
   hipStream_t st = ctx->stream;
   if (F == 0) return SMESH_OK;
-  SMESH_TRY(smesh_aggregator_refuse_scattered(a, "fuse_view_labels()"));
-  if (nviews != 1 && nviews != 2 && nviews != 4 && nviews != 8) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: unsupported view count");
-  if (label_bytes != 1 && label_bytes != 2) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: label planes are uint8 or uint16");
   LabelFuseArgs t;
-  uint64_t P;
   int kind;
-  smesh_aggregator_label_target(a, &t.acc, &P, &t.C, &kind, &t.iew);
-  if (kind == SMESH_AGG_MUL || P != F) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: Sum / Summax over the renderer's triangles only");
+  SMESH_TRY(check_fuse_rows("fuse_triangles_labels", "fuse_view_labels()", a, F, nviews, 0, &t, &kind));
+  if (label_bytes != 1 && label_bytes != 2) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: label planes are uint8 or uint16");
   LabelViews<8> tv;
-  bool no_big = true;   // every view PROVEN free of triangles over 8 x 8 pixels (RenderedView::no_big): no tail waves at all
   for (int v = 0; v < 8; v++) {
     const RenderedView& rv = views[v < nviews ? v : 0];
-    if (rv.W * rv.H < 8 || !rv.labels) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: label plane missing or under 8 pixels");
-    tv.v[v] = LabelView{rv.frags, rv.idx, rv.labels, rv.weights, rv.big_queue, rv.big_len, (uint32_t)rv.W, (uint32_t)rv.H};
-    no_big = no_big && rv.no_big;
+    if (rv.W * rv.H < 8 || !rv.image) return fail(SMESH_ERR_INVALID, "fuse_triangles_labels: label plane missing or under 8 pixels");
+    tv.v[v] = LabelView{rv.frags, rv.idx, rv.image, rv.weights, rv.big_queue, rv.big_len, (uint32_t)rv.W, (uint32_t)rv.H};
   }
   const bool in_lds = t.C <= kLabelsLdsMaxC;
-  t.F = F;
-  t.big_capacity = big_capacity;
-  t.tri_blocks = (uint32_t)div_up(F, kWave);
-  t.big_blocks = no_big ? 0u : 16u * (uint32_t)std::max(1, ctx->num_cus);
+  const dim3 grid = fuse_rows_grid(ctx, F, big_capacity, views, nviews, &t), block(kWave);
   t.stride = t.C | 1u;
   const size_t lds = in_lds ? (size_t)kWave * t.stride * 4 : 0;
-  const dim3 grid(t.tri_blocks + t.big_blocks), block(kWave);
   ProfScope prof(ctx, SMESH_PROF_FUSE_SCATTER);
   prof_note(ctx, SMESH_PROF_FUSE_SCATTER, 1, (uint64_t)nviews);
-#define SMESH_FL(LT, NV)                                                                                        \
-  {                                                                                                             \
-    LabelViews<NV> w;                                                                                           \
-    for (int v = 0; v < NV; v++) w.v[v] = tv.v[v];                                                              \
-    if (in_lds) hipLaunchKernelGGL((k_fuse_tri_labels<LT, NV, true>), grid, block, lds, st, t, w);              \
-    else hipLaunchKernelGGL((k_fuse_tri_labels<LT, NV, false>), grid, block, 0, st, t, w);                      \
-  }
-#define SMESH_FLV(LT)                                     \
-  switch (nviews) {                                       \
-    case 1: SMESH_FL(LT, 1) break;                        \
-    case 2: SMESH_FL(LT, 2) break;                        \
-    case 4: SMESH_FL(LT, 4) break;                        \
-    default: SMESH_FL(LT, 8) break;                       \
-  }
-  if (label_bytes == 1) { SMESH_FLV(uint8_t) } else { SMESH_FLV(uint16_t) }
-#undef SMESH_FLV
-#undef SMESH_FL
+  auto launch = [&](auto lt, auto NV) {   // (one kind, no class slots: the class count is a run-time value, the row an LDS block or memory)
+    using LT = decltype(lt);
+    if (in_lds) hipLaunchKernelGGL((k_fuse_tri_labels<LT, NV(), true>), grid, block, lds, st, t, (first_views<LabelViews, NV()>(tv)));
+    else hipLaunchKernelGGL((k_fuse_tri_labels<LT, NV(), false>), grid, block, 0, st, t, (first_views<LabelViews, NV()>(tv)));
+  };
+  launch_fuse_rows<false>(0, kind, nviews, [&](auto, auto, auto NV) {
+    if (label_bytes == 1) launch(uint8_t(), NV);
+    else launch(uint16_t(), NV);
+  });
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }
@@ -614,10 +546,10 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
     size_t slot_bytes = 0, stage_bytes = 0, w_bytes = 0;
     for (int v = 0; v < m; v++) {
       const uint64_t N = cams[i + v].width * cams[i + v].height;
-      slot_bytes = std::max<size_t>(slot_bytes, (N * 2 + 255) & ~(size_t)255);
+      slot_bytes = std::max(slot_bytes, round256(N * 2));
       stage_bytes = std::max(stage_bytes, prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h, prep->channels)
                                                   : stage_span_bytes(label_dtype, label_strides, cams[i + v].width, cams[i + v].height));
-      w_bytes = std::max<size_t>(w_bytes, (N * 4 + 255) & ~(size_t)255);
+      w_bytes = std::max(w_bytes, round256(N * 4));
     }
     const void* planes[kGroup];
     const float* wts[kGroup];
@@ -651,7 +583,7 @@ static int fuse_views_labels_impl(smesh_renderer_t* r, smesh_aggregator_t* a, co
       }
       if (staged) SMESH_HIP(hipStreamSynchronize(ctx->stream));   // the caller may reuse its host arrays once we return
     }
-    SMESH_TRY(smesh_renderer_fuse_views_labels(r, a, &cams[i], (uint64_t)m, planes, weights ? wts : nullptr, label_bytes));
+    SMESH_TRY(smesh_renderer_fuse_views_labels(r, a, &cams[i], (uint64_t)m, planes, weights ? wts : nullptr, ViewInput::labels(nullptr, label_bytes)));
   }
   return SMESH_OK;
 }
@@ -693,10 +625,10 @@ static int add_labels_impl(smesh_aggregator_t* a, smesh_renderer_t* r, const voi
     SMESH_HIP(hipSetDevice(ctx->device));
     LabelTableDev table;
     SMESH_TRY(stage_map(ctx, ls, prep, &table, &staged));
-    if (prep || !plane_in_place(label_dtype, label_strides, label_mem, W, H)) SMESH_TRY(ls.plane.reserve((N * 2 + 255) & ~(size_t)255));
+    if (prep || !plane_in_place(label_dtype, label_strides, label_mem, W, H)) SMESH_TRY(ls.plane.reserve(round256(N * 2)));
     if (label_mem == SMESH_MEM_HOST)
       SMESH_TRY(ls.stage.reserve(prep ? stage_span_bytes(label_dtype, label_strides, prep->w, prep->h, prep->channels) : stage_span_bytes(label_dtype, label_strides, W, H)));
-    SMESH_TRY(narrow_plane(ctx, ls, 0, (N * 2 + 255) & ~(size_t)255, 0, labels, label_dtype, label_strides, label_mem, W, H, C, &plane, &label_bytes, &staged,
+    SMESH_TRY(narrow_plane(ctx, ls, 0, round256(N * 2), 0, labels, label_dtype, label_strides, label_mem, W, H, C, &plane, &label_bytes, &staged,
                            prep, table));
     if (rendered && weights && w_mem == SMESH_MEM_HOST) {   // (the triangle-order kernel wants the weights where the plane is)
       SMESH_TRY(ls.w.reserve(N * 4));
@@ -708,7 +640,7 @@ static int add_labels_impl(smesh_aggregator_t* a, smesh_renderer_t* r, const voi
   }
   if (rendered) {
     int done = 0;
-    SMESH_TRY(smesh_renderer_add_rendered_labels(a, r, static_cast<const uint32_t*>(indices), plane, label_bytes, d_w, W, H, &done));
+    SMESH_TRY(smesh_renderer_add_rendered_input(a, r, static_cast<const uint32_t*>(indices), ViewInput::labels(plane, label_bytes), d_w, W, H, &done));
     if (done) return SMESH_OK;
   }
   // everything else: the labels expanded on the device, then the class-vector path unchanged (asynchronous for device images)

@@ -25,6 +25,7 @@
 #include <cmath>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 using namespace smesh;
 
@@ -41,13 +42,14 @@ struct smesh_renderer;
 DeviceCtx* smesh_renderer_ctx(smesh_renderer* r);
 bool smesh_renderer_sampled_native(smesh_renderer* r, smesh_aggregator* a);
 int smesh_renderer_fuse_views_sampled(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
-                                      const float* const* weights, const SampledSrc* src);
-int smesh_renderer_add_rendered_sampled(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* probs, const SampledSrc* src,
-                                        const float* weights, uint64_t W, uint64_t H, int* done);
+                                      const float* const* weights, const ViewInput& in);
+int smesh_renderer_add_rendered_input(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const ViewInput& in, const float* weights,
+                                      uint64_t W, uint64_t H, int* done);
 
 namespace {
 
 #include "fuse_tri.inc.hpp"
+#include "fuse_rows.inc.hpp"
 
 // One view as k_fuse_tri_sampled sees it.  The source image's size, strides and dtype are the call's (SampArgs).
 struct SampView {
@@ -77,18 +79,8 @@ struct SampArgs {
   uint32_t ps0, ps1;
 };
 
-// Pieces of a row through pointer types that state the alignment there really is -- the element's -- which gfx950 global memory
-// takes at any address.  Never past the row's end: the last pixel's row ends the allocation.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef u32x4 u32x4_a2 __attribute__((aligned(2)));
-typedef u32x2 u32x2_a2 __attribute__((aligned(2)));
-typedef uint32_t u32_a2 __attribute__((aligned(2)));
-typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
-typedef u32x2 u32x2_a4 __attribute__((aligned(4)));
-
 // Eight classes of a row from `p` on, `r` = 1 .. 8 of them inside the row (wave-uniform), widened exactly; the others come out as +0.
-// float32: 16-byte pieces of four classes, then 8 and 4 bytes for what is left; 16 bits: load_row16's pieces of 16, 8, 4 and 2 bytes.
+// float32: 16-byte pieces of four classes, then 8 and 4 bytes for what is left; 16 bits: 16 bytes, or load_part16's pieces.
 // EB: bytes per element; `bf`: the 16-bit elements are bfloat16.
 template <int EB>
 __device__ __forceinline__ void load_chunk(const char* __restrict__ p, int r, bool bf, float (&v)[8]) {
@@ -116,16 +108,7 @@ __device__ __forceinline__ void load_chunk(const char* __restrict__ p, int r, bo
     if (r == 8) {
       a = *reinterpret_cast<const u32x4_a2*>(q);
     } else {
-      u32x2 t8 = {0u, 0u};
-      uint32_t t4 = 0u, t2 = 0u;
-      if (r & 4) t8 = *reinterpret_cast<const u32x2_a2*>(q);
-      if (r & 2) t4 = *reinterpret_cast<const u32_a2*>(q + (r & 4));
-      if (r & 1) t2 = (uint32_t)q[r & 6];
-      const uint32_t rest0 = (r & 2) ? t4 : t2, rest1 = (r & 2) ? t2 : 0u;   // what follows the 8-byte piece, if there is one
-      a.x = (r & 4) ? t8.x : rest0;
-      a.y = (r & 4) ? t8.y : rest1;
-      a.z = (r & 4) ? rest0 : 0u;
-      a.w = (r & 4) ? rest1 : 0u;
+      a = load_part16(q, r);
     }
     unpack2(a.x, bf, v[0], v[1]); unpack2(a.y, bf, v[2], v[3]); unpack2(a.z, bf, v[4], v[5]); unpack2(a.w, bf, v[6], v[7]);
   }
@@ -172,131 +155,6 @@ __device__ __forceinline__ void sample_row(const SampArgs& a, const SampView& vw
   else sample_row_as<CT, 2>(a, vw, X, Y, a.dt == SMESH_PROBS_BF16, p);
 }
 
-// Mesh.h:94-106 for one pixel's class vector `p` with weight `w` into `dst` (a row in registers, or a tail wave's partial sums).
-template <int CT, int KIND>
-__device__ __forceinline__ void add_pixel(const float (&p)[CT], int C, float w, float (&dst)[CT]) {
-  if (KIND == SMESH_AGG_SUMMAX) {
-    int am = 0;
-    float best = p[0];   // (not p[am]: a run-time register index would go through scratch)
-#pragma unroll
-    for (int c = 1; c < CT; c++) if (c < C) if (p[c] > best) { best = p[c]; am = c; }
-#pragma unroll
-    for (int c = 0; c < CT; c++) if (c < C) if (c == am) dst[c] = dst[c] + p[c] * w;
-  } else {
-#pragma unroll
-    for (int c = 0; c < CT; c++) if (c < C) dst[c] = dst[c] + p[c] * w;
-  }
-}
-
-template <int CT>
-__device__ __forceinline__ float row_sum(const float (&p)[CT], int C) {
-  float sum = 0.0f;
-#pragma unroll
-  for (int c = 0; c < CT; c++) if (c < C) sum = sum + p[c];   // tt::sum, sequential float32
-  return sum;
-}
-
-// One queued triangle `f` in one view: one WAVE, lanes over the pixels of the box [x0, x1] x [y0, y1] of the view's index plane, each
-// lane samples its own pixels' rows, per-lane partial sums combined by a butterfly; lane c then adds class c to the row, which nobody
-// else touches in this launch.  A tree order: the 1e-5 path, like fuse_box16.
-template <int CT, int KIND>
-__device__ __forceinline__ void fuse_box_sampled(const SampArgs& a, const SampView& vw, const uint32_t f, const int x0, const int y0, const int x1,
-                                                 const int y1) {
-  const int C = (int)a.C;
-  const int l = threadIdx.x;
-  const uint32_t bh = (uint32_t)(y1 - y0 + 1);
-  const uint32_t npx = (uint32_t)(x1 - x0 + 1) * bh;   // (W, H <= 65536 and W * H < 2^29: fits)
-  const uint32_t* __restrict__ idx = vw.idx;
-  uint32_t cnt = 0;
-  for (uint32_t i = l; i < npx; i += kWave) cnt += idx[(uint64_t)((uint32_t)x0 + i / bh) * vw.H + ((uint32_t)y0 + i % bh)] == f ? 1u : 0u;
-  const uint32_t n = wave_sum_u(cnt);
-  if (n == 0) return;
-  const float w0 = a.iew * (1.0f / (float)n) + (1 - a.iew) * 1.0f;
-  float part[CT];
-#pragma unroll
-  for (int c = 0; c < CT; c++) part[c] = 0.0f;
-  for (uint32_t i = l; i < npx; i += kWave) {
-    const uint32_t x = (uint32_t)x0 + i / bh, y = (uint32_t)y0 + i % bh;
-    const uint64_t pix = (uint64_t)x * vw.H + y;
-    if (idx[pix] != f) continue;
-    float p[CT];
-    sample_row<CT>(a, vw, x, y, p);
-    if (!(row_sum<CT>(p, C) > 0.5f)) continue;                                  // Mesh.h:98
-    const float w = w0 * (vw.weights ? vw.weights[pix] : 1.0f);                 // :103
-    add_pixel<CT, KIND>(p, C, w, part);
-  }
-  float mine = 0.0f;
-#pragma unroll
-  for (int c = 0; c < CT; c++) if (c < C) {
-    const float v = wave_sum(part[c]);
-    if (l == c) mine = v;
-  }
-  if (l < C) {
-    float* __restrict__ row = a.acc + (uint64_t)f * C;
-    row[l] = row[l] + mine;
-  }
-}
-
-// Triangles with a box over 8 x 8 pixels in some view of the launch: one wave per queued triangle for ALL its views, first view first
-// (fuse_big16's walk over the concatenated queues).  The views in which the triangle is small are scanned as 8 x 8 boxes of THEIR
-// index planes, which is why the raster launch ahead of this kernel runs at kLabelsPlaneLevel (raster.hip).
-template <int CT, int KIND, int NV>
-__device__ __forceinline__ void fuse_big_sampled(const SampArgs& a, const SampViews<NV>& vw, uint32_t worker, uint32_t nworkers) {
-  uint32_t len[NV], total = 0u;
-#pragma unroll
-  for (int v = 0; v < NV; v++) { len[v] = min(*vw.v[v].big_len, a.big_capacity); total += len[v]; }
-  const int l = threadIdx.x;
-  const uint32_t chunk = max(1u, min((uint32_t)kWave, total / max(nworkers, 1u)));
-  const uint32_t steps = (total + chunk - 1u) / chunk;
-  for (uint32_t step = worker; step < steps; step += nworkers) {
-    const uint32_t q = (uint32_t)l < chunk ? (uint32_t)l * steps + step : total;
-    uint32_t fi = 0u;
-    bool take = false;
-    {
-      uint32_t qq = q;
-      bool located = q >= total;
-      int jsel = -1;
-#pragma unroll
-      for (int j = 0; j < NV; j++) {
-        if (!located) {
-          if (qq < len[j]) { fi = vw.v[j].big_queue[qq]; jsel = j; located = true; }
-          else qq -= len[j];
-        }
-      }
-      if (jsel >= 0 && fi < a.F) {
-        bool mine = false, earlier = false;
-#pragma unroll
-        for (int i = 0; i < NV; i++) {
-          if (i <= jsel) {
-            const bool counts = vw.v[i].frags[fi].kind == 2;
-            if (i < jsel) earlier = earlier || counts;
-            else mine = counts;
-          }
-        }
-        take = mine && !earlier;   // a triangle queued by several views is taken from the queue of the first of them
-      }
-    }
-    unsigned long long todo = __ballot(take);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      const uint32_t f = (uint32_t)__builtin_amdgcn_readlane((int)fi, src);   // wave-uniform; row = triangle (no re-ordered meshes here)
-#pragma nounroll
-      for (int j = 0; j < NV; j++) {   // (a loop, not NV copies of the sampling code: j is wave-uniform, the view comes from the kernel arguments)
-        const TriFrag rec = vw.v[j].frags[f];
-        if (rec.kind == 0) continue;
-        const int x0 = rec.x0, y0 = rec.y0;
-        int x1, y1;
-        if (rec.kind == 2) { x1 = (int)(rec.mask & 0xFFFFu); y1 = (int)((rec.mask >> 16) & 0xFFFFu); }
-        else { x1 = x0 + 7; y1 = y0 + 7; }
-        x1 = min(x1, (int)vw.v[j].W - 1); y1 = min(y1, (int)vw.v[j].H - 1);
-        if (x1 < x0 || y1 < y0) continue;
-        fuse_box_sampled<CT, KIND>(a, vw.v[j], f, x0, y0, x1, y1);
-      }
-    }
-  }
-}
-
 // NV views (1, 2, 4 or 8) of (w,h,C) class vectors into the accumulator in ONE launch, in order: k_fuse_tri_h16's structure.  Lane =
 // triangle, wave = 64 consecutive rows parked in LDS (one round trip of the block for all views), a visible pixel's row sampled from
 // the source image in registers, the float32 additions in pixel order, view 0 first -- the oracle's.  CT: class-vector register slots
@@ -307,52 +165,26 @@ __device__ __forceinline__ void fuse_big_sampled(const SampArgs& a, const SampVi
 template <int CT, int KIND, int NV>
 __global__ __launch_bounds__(kWave) void k_fuse_tri_sampled(SampArgs a, SampViews<NV> vw) {
   const int C = (int)a.C;
-  constexpr int KV = (kWave * CT / 4 + kWave - 1) / kWave;   // float4 per lane of the 64-row block
+  constexpr int KV = rows_quads(CT);
   __shared__ __attribute__((aligned(16))) float srow[kWave * CT + 4];   // the wave's 64 accumulator rows
   const int l = threadIdx.x;
   if (blockIdx.x >= a.tri_blocks) {
-    fuse_big_sampled<CT, KIND, NV>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks);
+    // (a loop over the views, not NV copies of the sampling code)
+    for_each_queued_triangle<NV, false>(a, vw, blockIdx.x - a.tri_blocks, a.big_blocks,
+                                        [&](const uint32_t f, const int j, const int x0, const int y0, const int x1, const int y1) __attribute__((always_inline)) {
+      const SampView& view = vw.v[j];
+      fuse_box_rows<CT, KIND>(a, view, f, x0, y0, x1, y1, [&](const uint32_t x, const uint32_t y, float (&p)[CT]) __attribute__((always_inline)) {
+        sample_row<CT>(a, view, x, y, p);
+      });
+    });
     return;
   }
   const uint64_t f0 = (uint64_t)blockIdx.x * kWave;
   const uint64_t f = f0 + l;
-  // per view: box origin (x0 | y0 << 16) and the mask of this triangle's VISIBLE pixels inside its <= 8 x 8 box
   uint32_t org[NV];
   unsigned long long msk[NV];
-  bool big = false;   // a box over 8 x 8 in some view: the triangle is a tail wave's for all its views, and so is its row
-#pragma unroll
-  for (int v = 0; v < NV; v++) { org[v] = 0u; msk[v] = 0ull; }
-  if (f < a.F) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) {
-      const TriFrag rec = vw.v[v].frags[f];
-      org[v] = (uint32_t)rec.x0 | ((uint32_t)rec.y0 << 16);
-      msk[v] = rec.kind == 1 ? rec.mask : 0ull;
-      big = big || rec.kind == 2;
-    }
-  }
-  if (big) {
-#pragma unroll
-    for (int v = 0; v < NV; v++) msk[v] = 0ull;
-  }
-  // the masks of a view whose render says they need checking (fragment-queue overflow, direct rasteriser) are checked against that
-  // view's index plane, which such a view always writes (k_fuse_tri's pass 1)
-#pragma unroll
-  for (int v = 0; v < NV; v++) {
-    if (vw.v[v].big_len[1] == 0u) continue;
-    const uint32_t* __restrict__ idx = vw.v[v].idx;
-    unsigned long long m = msk[v], win = 0ull;
-    while (m) {
-      const int k = __ffsll((long long)m) - 1;
-      m &= m - 1ull;
-      const uint64_t pix = (uint64_t)((org[v] & 0xFFFFu) + (uint32_t)(k >> 3)) * vw.v[v].H + (org[v] >> 16) + (uint32_t)(k & 7);
-      if (idx[pix] == (uint32_t)f) win |= 1ull << k;
-    }
-    msk[v] = win;
-  }
-  unsigned long long any_win = 0ull;
-#pragma unroll
-  for (int v = 0; v < NV; v++) any_win |= msk[v];
+  bool big;
+  const unsigned long long any_win = visible_masks<NV>(a, vw, f, org, msk, big);
   if (__ballot(any_win != 0ull) == 0ull) return;   // nothing of these 64 triangles is visible: rows untouched
 
   // (k_fuse_tri_h16 issues the wave's 64 rows into registers together with the first pixel's loads; here four corner rows per pixel are
@@ -406,30 +238,10 @@ __global__ __launch_bounds__(kWave) void k_fuse_tri_sampled(SampArgs a, SampView
       if (have && sum > 0.5f) add_pixel<CT, KIND>(p, C, w0 * wt, accr);    // :98, :103
     }
   }
-  // each lane parks its row ...
-#pragma unroll
-  for (int c = 0; c < CT; c++) if (c < C) srow[l * C + c] = accr[c];
-  wave_sync();
-  if (nrows != kWave || __ballot(big) != 0ull) {
-    // some of these 64 rows belong to queued triangles, which the tail waves of this launch update meanwhile (or the block is the
-    // mesh's last, partial one): every lane that added something stores its own row
-    if (any_win) {
-      float* __restrict__ row = a.acc + f * C;
-      const float* __restrict__ mine = srow + l * C;
-      for (int c = 0; c < C; c++) row[c] = mine[c];
-    }
-    return;
-  }
-  // ... and the block goes back as it came
-  f4* b4 = reinterpret_cast<f4*>(blk);
-  const f4* s4 = reinterpret_cast<const f4*>(srow);
-  for (int q = l; q < kWave * C / 4; q += kWave) b4[q] = s4[q];
+  store_rows<CT>(a.acc, srow, blk, f, nrows, C, big, any_win != 0ull, accr);
 }
 
-constexpr int kGroup = 8;   // views whose staged or resampled images share the aggregator's scratch: a group of smesh_fuse_views
-
 size_t itemsize(int dt) { return dt == SMESH_PROBS_F32 ? 4 : 2; }
-size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // The checks the entry points share.  `s`: the caller's strides or null.
 int check_sampled_source(const char* who, int dt, const int64_t* s, uint64_t w, uint64_t h, int mode) {
@@ -448,11 +260,6 @@ bool takes_strides(const int64_t* s, uint32_t C) {
   return (s[2] == 1 || C == 1) && s[0] <= 0xFFFFFFFFll && s[1] <= 0xFFFFFFFFll;
 }
 
-// Elements that the strides of a (w,h,C) source cover.
-uint64_t source_span(const int64_t* s, uint64_t w, uint64_t h, uint32_t C) {
-  return 1 + (w - 1) * (uint64_t)s[0] + (h - 1) * (uint64_t)s[1] + (uint64_t)(C - 1) * (uint64_t)s[2];
-}
-
 }  // namespace
 
 // ---- what raster.hip calls --------------------------------------------------------------------------------------------------
@@ -466,72 +273,35 @@ bool smesh_sampled_native(smesh_aggregator* a, uint64_t F) {
   return opt_fuse_sampled() && kind != SMESH_AGG_MUL && F != 0 && C <= kHalfMaxClasses && smesh_aggregator_can_fuse_triangles(a, F);
 }
 
-// views[v].probs16: the (w,h,C) source image of view v in device memory (`src`: dtype, size and strides of them all); views[v].W, H:
+// views[v].image: the (w,h,C) source image of view v in device memory (`src`: dtype, size and strides of them all); views[v].W, H:
 // the view's own size.  `nviews` = 1, 2, 4 or 8.
-int smesh_sampled_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, const SampledSrc* src) {
+int smesh_sampled_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, const SampledSrc& src) {
   DeviceCtx* ctx = smesh_aggregator_ctx(a);
   hipStream_t st = ctx->stream;
   if (F == 0) return SMESH_OK;
-  SMESH_TRY(smesh_aggregator_refuse_scattered(a, "fuse_view_sampled()"));
-  if (!src) return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: source description missing");
-  if (nviews != 1 && nviews != 2 && nviews != 4 && nviews != 8) return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: unsupported view count");
   SampArgs t;
-  uint64_t P;
   int kind;
-  smesh_aggregator_label_target(a, &t.acc, &P, &t.C, &kind, &t.iew);
-  if (kind == SMESH_AGG_MUL || P != F || t.C == 0 || t.C > kHalfMaxClasses)
-    return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: Sum / Summax over the renderer's triangles, at most 48 classes");
-  if (src->w == 0 || src->h == 0 || src->s0 < 0 || src->s1 < 0 || src->s0 > 0xFFFFFFFFll || src->s1 > 0xFFFFFFFFll)
+  SMESH_TRY(check_fuse_rows("fuse_triangles_sampled", "fuse_view_sampled()", a, F, nviews, kHalfMaxClasses, &t, &kind));
+  if (src.w == 0 || src.h == 0 || src.s0 < 0 || src.s1 < 0 || src.s0 > 0xFFFFFFFFll || src.s1 > 0xFFFFFFFFll)
     return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: source size or strides out of range");
   SampViews<8> tv;
-  bool no_big = true;   // every view PROVEN free of triangles over 8 x 8 pixels (RenderedView::no_big): no tail waves at all
   for (int v = 0; v < 8; v++) {
     const RenderedView& rv = views[v < nviews ? v : 0];
-    if (rv.W == 0 || rv.H == 0 || !rv.probs16) return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: class-vector image missing");
-    if (reinterpret_cast<uintptr_t>(rv.probs16) % itemsize(src->dtype)) return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: the image is not aligned to its element size");
-    tv.v[v] = SampView{rv.frags, rv.idx, static_cast<const char*>(rv.probs16), rv.weights, rv.big_queue, rv.big_len,
-                       (double)src->w / (double)rv.W, (double)src->h / (double)rv.H, (uint32_t)rv.W, (uint32_t)rv.H};
-    no_big = no_big && rv.no_big;
+    if (rv.W == 0 || rv.H == 0 || !rv.image) return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: class-vector image missing");
+    if (reinterpret_cast<uintptr_t>(rv.image) % itemsize(src.dtype)) return fail(SMESH_ERR_INVALID, "fuse_triangles_sampled: the image is not aligned to its element size");
+    tv.v[v] = SampView{rv.frags, rv.idx, static_cast<const char*>(rv.image), rv.weights, rv.big_queue, rv.big_len,
+                       (double)src.w / (double)rv.W, (double)src.h / (double)rv.H, (uint32_t)rv.W, (uint32_t)rv.H};
   }
-  t.F = F;
-  t.big_capacity = big_capacity;
-  t.tri_blocks = (uint32_t)div_up(F, kWave);
-  t.big_blocks = no_big ? 0u : 16u * (uint32_t)std::max(1, ctx->num_cus);
-  t.dt = (uint32_t)src->dtype;
-  t.w = src->w; t.h = src->h;
-  t.ps0 = (uint32_t)src->s0; t.ps1 = (uint32_t)src->s1;
-  const dim3 grid(t.tri_blocks + t.big_blocks), block(kWave);
-  const int ct = (int)((t.C + 7u) / 8u) * 8;
+  const dim3 grid = fuse_rows_grid(ctx, F, big_capacity, views, nviews, &t), block(kWave);
+  t.dt = (uint32_t)src.dtype;
+  t.w = src.w; t.h = src.h;
+  t.ps0 = (uint32_t)src.s0; t.ps1 = (uint32_t)src.s1;
   ProfScope prof(ctx, SMESH_PROF_FUSE_SCATTER);
   prof_note(ctx, SMESH_PROF_FUSE_SCATTER, 1, (uint64_t)nviews);
-#define SMESH_FS(CT, KIND, NV)                                                          \
-  {                                                                                     \
-    SampViews<NV> w;                                                                    \
-    for (int v = 0; v < NV; v++) w.v[v] = tv.v[v];                                      \
-    hipLaunchKernelGGL((k_fuse_tri_sampled<CT, KIND, NV>), grid, block, 0, st, t, w);   \
-  }
-#define SMESH_FSV(CT, KIND)                    \
-  switch (nviews) {                            \
-    case 1: SMESH_FS(CT, KIND, 1) break;       \
-    case 2: SMESH_FS(CT, KIND, 2) break;       \
-    case 4: SMESH_FS(CT, KIND, 4) break;       \
-    default: SMESH_FS(CT, KIND, 8) break;      \
-  }
-#define SMESH_FSK(CT)                                                                     \
-  if (kind == SMESH_AGG_SUMMAX) { SMESH_FSV(CT, SMESH_AGG_SUMMAX) } else { SMESH_FSV(CT, SMESH_AGG_SUM) }
-  switch (ct) {
-    case 8:  SMESH_FSK(8) break;
-    case 16: SMESH_FSK(16) break;
-    case 24: SMESH_FSK(24) break;
-    case 32: SMESH_FSK(32) break;
-    case 40: SMESH_FSK(40) break;
-    default: SMESH_FSK(48) break;
-  }
-#undef SMESH_FSK
-#undef SMESH_FSV
-#undef SMESH_FS
+  launch_fuse_rows<true>((int)((t.C + 7u) / 8u) * 8, kind, nviews, [&](auto CT, auto KIND, auto NV) {
+    hipLaunchKernelGGL((k_fuse_tri_sampled<CT(), KIND(), NV()>), grid, block, 0, st, t, (first_views<SampViews, NV()>(tv)));
+  });
   SMESH_HIP(hipGetLastError());
-  smesh_set_last_fuse_instance(ct, nviews);   // (reporting only)
   return SMESH_OK;
 }
 
@@ -599,22 +369,12 @@ int smesh_fuse_views_sampled(smesh_renderer_t* r, smesh_aggregator_t* a, const s
     if (memkind == SMESH_MEM_HOST && (native || weights)) {
       std::lock_guard<std::recursive_mutex> lock(ctx->mu);
       SMESH_HIP(hipSetDevice(ctx->device));
-      for (int v = 0; v < m; v++) {
-        if (native) {   // the span the strides cover, as it is: the staged image keeps its strides
-          char* d = static_cast<char*>(hs.smp_stage.ptr) + (size_t)v * stage_bytes;
-          SMESH_HIP(hipMemcpyAsync(d, probs[i + v], span * eb, hipMemcpyHostToDevice, ctx->stream));
-          dev[v] = d;
-        }
-        if (wts[v]) {
-          float* dw = reinterpret_cast<float*>(static_cast<char*>(hs.smp_w.ptr) + (size_t)v * w_bytes);
-          SMESH_HIP(hipMemcpyAsync(dw, wts[v], cams[i + v].width * cams[i + v].height * 4, hipMemcpyHostToDevice, ctx->stream));
-          wts[v] = dw;
-        }
-      }
-      SMESH_HIP(hipStreamSynchronize(ctx->stream));   // the caller may reuse its host arrays once we return
+      // (the span the strides cover, as it is: the staged image keeps its strides)
+      SMESH_TRY(stage_host_group(ctx, &cams[i], m, &probs[i], weights ? &weights[i] : nullptr, native ? &hs.smp_stage : nullptr, stage_bytes,
+                                 [&](int) { return (size_t)(span * eb); }, hs.smp_w, w_bytes, dev, wts));
     }
     if (native) {
-      SMESH_TRY(smesh_renderer_fuse_views_sampled(r, a, &cams[i], (uint64_t)m, dev, weights ? wts : nullptr, &src));
+      SMESH_TRY(smesh_renderer_fuse_views_sampled(r, a, &cams[i], (uint64_t)m, dev, weights ? wts : nullptr, ViewInput::sampled(nullptr, src)));
       continue;
     }
     // what the kernel does not serve: each image resampled into its scratch slot (a host image is staged and consumed by that call),
@@ -689,7 +449,7 @@ int smesh_aggregator_add_sampled(smesh_aggregator_t* a, smesh_renderer_t* r, con
     }
     const SampledSrc src{probs_dtype, (uint32_t)w, (uint32_t)h, ps[0], ps[1]};
     int done = 0;
-    SMESH_TRY(smesh_renderer_add_rendered_sampled(a, r, static_cast<const uint32_t*>(indices), d_probs, &src, d_w, W, H, &done));
+    SMESH_TRY(smesh_renderer_add_rendered_input(a, r, static_cast<const uint32_t*>(indices), ViewInput::sampled(d_probs, src), d_w, W, H, &done));
     if (done) return SMESH_OK;
   }
   // everything else: the image resampled on the device, then the existing entry points unchanged (asynchronous for device images)

@@ -1,31 +1,18 @@
-// half_scratch.hpp -- what the 16-bit class-vector entry points (fusion_half.hip, include/smesh_half.h) share with the rest of the
-// library: the aggregator-owned device scratch (allocated on first use, released by smesh_aggregator_destroy, like LabelScratch)
-// and how a view's dtype rides through raster.hip's view-batch driver.
+// half_scratch.hpp -- what the 16-bit and sampled class-vector entry points (fusion_half.hip, fusion_sampled.hip) share with the rest
+// of the library: the aggregator-owned device scratch (allocated on first use, released by smesh_aggregator_destroy, like
+// LabelScratch), the staging of a group of host images into it, and the exact 16-bit conversions.
 #pragma once
 
 #include <mutex>
 
 #include "common.hpp"
+#include "view_input.hpp"
 
 namespace smesh {
 
 // Largest class count k_fuse_tri_h16 serves: run-time class counts in 8 / 16 .. 48 register slots, as k_fuse_tri's run-time-C
 // instances.  Read-only option "half_max_classes" (smesh_get_option).
 constexpr uint32_t kHalfMaxClasses = 48;
-
-// raster.hip's drivers carry one int per call that says what the `probs` pointers are: 0 = float32 class vectors, 1 / 2 = label
-// planes of that many bytes per pixel, kHalfMode | SMESH_PROBS_F16 / _BF16 = 16-bit class vectors.
-constexpr int kHalfMode = 0x10;
-inline int half_dtype_of(int mode) { return (mode & kHalfMode) ? (mode & 0xF) : 0; }
-// kSampledMode | SMESH_PROBS_*: (w,h,C) class vectors at the network's resolution, sampled inside the fusion kernel
-// (fusion_sampled.hip, include/smesh_sampled.h); the drivers then carry a SampledSrc beside the int.
-constexpr int kSampledMode = 0x20;
-inline bool sampled_mode(int mode) { return (mode & kSampledMode) != 0; }
-struct SampledSrc {
-  int dtype;          // SMESH_PROBS_* of every image of the call
-  uint32_t w, h;      // their width and height
-  int64_t s0, s1;     // element strides of x and y (class stride 1)
-};
 
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 
@@ -67,5 +54,30 @@ struct HalfScratch {
   Scratch smp_stage, smp_w, smp_full;
   void release() { stage.release(); w.release(); wide.release(); smp_stage.release(); smp_w.release(); smp_full.release(); }
 };
+
+// The host images and host weights of a group of m <= kGroup views into reserved scratch, on the main stream, and the wait for the
+// copies (the caller may reuse its host arrays once its call returns).  `stage` (null: the images stay where they are): image v, of
+// image_bytes(v) bytes, goes to slot v, the slots slot_bytes apart; `w`: the same for the (W,H) float32 weights of the views that have
+// some.  dev[v] / wts[v]: where view v's image and weights are now.  The context is locked and its device current.
+template <typename ImageBytes>
+int stage_host_group(DeviceCtx* ctx, const smesh_camera_t* cams, int m, const void* const* probs, const float* const* weights, Scratch* stage,
+                     size_t slot_bytes, ImageBytes image_bytes, Scratch& w, size_t w_bytes, const void** dev, const float** wts) {
+  for (int v = 0; v < m; v++) {
+    dev[v] = probs[v];
+    wts[v] = weights ? weights[v] : nullptr;
+    if (stage) {
+      char* d = static_cast<char*>(stage->ptr) + (size_t)v * slot_bytes;
+      SMESH_HIP(hipMemcpyAsync(d, probs[v], image_bytes(v), hipMemcpyHostToDevice, ctx->stream));
+      dev[v] = d;
+    }
+    if (wts[v]) {
+      float* dw = reinterpret_cast<float*>(static_cast<char*>(w.ptr) + (size_t)v * w_bytes);
+      SMESH_HIP(hipMemcpyAsync(dw, wts[v], cams[v].width * cams[v].height * 4, hipMemcpyHostToDevice, ctx->stream));
+      wts[v] = dw;
+    }
+  }
+  SMESH_HIP(hipStreamSynchronize(ctx->stream));
+  return SMESH_OK;
+}
 
 }  // namespace smesh

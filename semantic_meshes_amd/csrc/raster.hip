@@ -73,7 +73,7 @@ bool smesh_half_takes_strides(int64_t ps0, int64_t ps1);
 int smesh_half_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int probs_dtype);
 // fusion_sampled.hip: (w,h,C) class vectors sampled inside the fusion kernel (include/smesh_sampled.h)
 bool smesh_sampled_native(smesh_aggregator* a, uint64_t F);
-int smesh_sampled_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, const SampledSrc* src);
+int smesh_sampled_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, const SampledSrc& src);
 int smesh_half_widen(smesh_aggregator* a, const void* probs, int probs_dtype, const int64_t s[3], uint64_t W, uint64_t H, const float** out,
                      int slot = 0, size_t slot_bytes = 0, int nslots = 1);
 
@@ -2341,58 +2341,73 @@ constexpr int kLabelsPlaneLevel = 1;
 // Do 16-bit class-vector views of this renderer into this aggregator take k_fuse_tri_h16 (fusion_half.hip)?  Triangle primitives in the
 // caller's face order, Sum / Summax, at most kHalfMaxClasses classes.  Everything else: the image widened on the device, float32 path.
 static bool half_native(smesh_renderer* r, smesh_aggregator* a) { return !r->texels && !r->prim_id && smesh_half_native(a, r->F); }
-// Does the kernel that follows the raster launch of a view in this mode (fuse_rendered's `label_bytes`) read index planes the way
-// k_fuse_tri_labels does?  The tail waves of k_fuse_tri_h16 are that kernel's: they SCAN the plane of every view of the launch for a
-// queued triangle, so its raster launches take kLabelsPlaneLevel as well (no cheaper level is safe: there is no by-mask path).
+// Does the kernel that follows the raster launch of a view of this kind read index planes the way k_fuse_tri_labels does?  The
+// tail waves of k_fuse_tri_h16 are that kernel's: they SCAN the plane of every view of the launch for a queued triangle, so its
+// raster launches take kLabelsPlaneLevel as well (no cheaper level is safe: there is no by-mask path).
 // (k_fuse_tri_sampled's tail waves are k_fuse_tri_h16's: the same level.  A sampled view only gets here where that kernel serves it.)
 static bool sampled_native(smesh_renderer* r, smesh_aggregator* a) { return !r->texels && !r->prim_id && smesh_sampled_native(a, r->F); }
-static bool scans_all_planes(smesh_renderer* r, smesh_aggregator* a, int label_bytes, uint64_t N) {
-  if (sampled_mode(label_bytes)) return sampled_native(r, a);
-  if (half_dtype_of(label_bytes)) return half_native(r, a);
-  return label_bytes && labels_native(r, a, N);
+static bool scans_all_planes(smesh_renderer* r, smesh_aggregator* a, ViewInput::Kind kind, uint64_t N) {
+  switch (kind) {
+    case ViewInput::SAMPLED: return sampled_native(r, a);
+    case ViewInput::HALF: return half_native(r, a);
+    case ViewInput::LABELS: return labels_native(r, a, N);
+    default: return false;
+  }
+}
+
+// One view's records and planes as the fusion kernels take them, `in.image` standing in for the float32 class vectors unless it is them.
+static RenderedView rendered_view(const smesh_renderer::Side& sd, const uint32_t* d_idx, const ViewInput& in, const float* d_w, uint64_t W, uint64_t H,
+                                  bool mid_queue) {
+  RenderedView rv{sd.frags, sd.big_queue, sd.big_count, d_idx, in.probs(), d_w, W, H, in.ps0, in.ps1, mid_queue};
+  if (in.kind != ViewInput::F32) rv.image = in.image;
+  return rv;
 }
 
 // The fusion half of smesh_fuse_view / smesh_aggregator_add_rendered: `d_idx` is the index plane of the render
-// whose per-triangle records sit in r->side[slot].
-// (`label_bytes` 1 / 2: `probs` is no class-vector image but a dense label plane of that many bytes per pixel in DEVICE memory;
-// kHalfMode | dtype: a 16-bit class-vector image in DEVICE memory, class stride 1 -- half_scratch.hpp;
-// kSampledMode | dtype: a (w,h,C) image in DEVICE memory that `smp` describes, which k_fuse_tri_sampled serves -- the caller made sure)
-static int fuse_rendered(smesh_renderer* r, smesh_aggregator* a, int slot, const uint32_t* d_idx, const float* probs,
-                         const float* weights, int memkind, uint64_t W, uint64_t H, int64_t ps0 = 0, int64_t ps1 = 0, int label_bytes = 0,
-                         const SampledSrc* smp = nullptr) {
+// whose per-triangle records sit in r->side[slot].  `in`: the view's image (view_input.hpp); `memkind`: where an F32 image and the
+// weights are -- every other kind is in DEVICE memory.
+static int fuse_rendered(smesh_renderer* r, smesh_aggregator* a, int slot, const uint32_t* d_idx, const ViewInput& in, const float* weights,
+                         int memkind, uint64_t W, uint64_t H) {
   DeviceCtx* ctx = r->ctx;
   const uint64_t N = W * H;
+  const float* probs = in.probs();
   const float* d_probs = probs;
   const float* d_w = weights;
-  if (sampled_mode(label_bytes)) {
-    if (!smp || !sampled_native(r, a)) return fail(SMESH_ERR_INVALID, "sampled view: k_fuse_tri_sampled does not serve this renderer and aggregator");
-    RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H};   // (k_fuse_tri_sampled has no medium-triangle path: mid_queue stays false)
-    rv.probs16 = probs;
-    SMESH_TRY(smesh_sampled_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, smp));
-    note_fuse_sampled(smp->dtype);
-    return SMESH_OK;
-  }
-  if (const int dt16 = half_dtype_of(label_bytes)) {
-    if (half_native(r, a)) {
-      RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H, ps0, ps1, true};
-      rv.probs16 = probs;
-      SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, dt16));
-      note_fuse_half(dt16);
+  int64_t ps0 = in.ps0, ps1 = in.ps1;
+  const smesh_renderer::Side& sd = r->side[slot];
+  switch (in.kind) {
+    case ViewInput::SAMPLED: {
+      if (!sampled_native(r, a)) return fail(SMESH_ERR_INVALID, "sampled view: k_fuse_tri_sampled does not serve this renderer and aggregator");
+      const RenderedView rv = rendered_view(sd, d_idx, in, d_w, W, H, false);   // (k_fuse_tri_sampled has no medium-triangle path: mid_queue stays false)
+      SMESH_TRY(smesh_sampled_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, in.src));
+      note_fuse_sampled(in.src.dtype);
       return SMESH_OK;
     }
-    const int64_t C = (int64_t)smesh_aggregator_classes(a);
-    const int64_t s[3] = {(ps0 || ps1) ? ps0 : (int64_t)H * C, (ps0 || ps1) ? ps1 : C, 1};
-    SMESH_TRY(smesh_half_widen(a, probs, dt16, s, W, H, &d_probs));
-    ps0 = ps1 = 0;
-  } else if (label_bytes) {
-    if (labels_native(r, a, N)) {
-      RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, nullptr, d_w, W, H, 0, 0, true};
-      rv.labels = probs;
-      SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, label_bytes));
-      smesh_note_fuse("k_fuse_tri_labels", "render-records");
-      return SMESH_OK;
+    case ViewInput::HALF: {
+      const int dt16 = in.dtype_or_bytes;
+      if (half_native(r, a)) {
+        const RenderedView rv = rendered_view(sd, d_idx, in, d_w, W, H, true);
+        SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, dt16));
+        note_fuse_half(dt16);
+        return SMESH_OK;
+      }
+      const int64_t C = (int64_t)smesh_aggregator_classes(a);
+      const int64_t s[3] = {(ps0 || ps1) ? ps0 : (int64_t)H * C, (ps0 || ps1) ? ps1 : C, 1};
+      SMESH_TRY(smesh_half_widen(a, in.image, dt16, s, W, H, &d_probs));
+      ps0 = ps1 = 0;
+      break;
     }
-    SMESH_TRY(smesh_labels_expand(a, probs, label_bytes, N, &d_probs));
+    case ViewInput::LABELS: {
+      if (labels_native(r, a, N)) {
+        const RenderedView rv = rendered_view(sd, d_idx, in, d_w, W, H, true);
+        SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, &rv, 1, in.dtype_or_bytes));
+        smesh_note_fuse("k_fuse_tri_labels", "render-records");
+        return SMESH_OK;
+      }
+      SMESH_TRY(smesh_labels_expand(a, in.image, in.dtype_or_bytes, N, &d_probs));
+      break;
+    }
+    case ViewInput::F32: break;
   }
   if (memkind == SMESH_MEM_HOST) {
     const uint32_t C = smesh_aggregator_classes(a);
@@ -2665,9 +2680,9 @@ int smesh_renderer_render(smesh_renderer_t* r, const smesh_camera_t* cam, uint32
 
 // One iteration of the driver loop (colorize_cityscapes_mesh.py:54-67): render + add, indices never leave HBM.
 // Asynchronous for DEVICE probs: they must stay valid until smesh_synchronize().
-static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const float* probs,
-                          const float* weights, int memkind, int label_bytes, const SampledSrc* smp = nullptr) {
-  if (!r || !a || !probs) return fail(SMESH_ERR_INVALID, "NULL argument");
+static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const ViewInput& in, const float* weights,
+                          int memkind) {
+  if (!r || !a || !in.image) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(check_camera(cam));
   DeviceCtx* ctx = r->ctx;
   if (smesh_aggregator_ctx(a) != ctx) return fail(SMESH_ERR_INVALID, "renderer and aggregator live on different devices");
@@ -2693,29 +2708,28 @@ static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smes
   // (the fusion only consumes the index plane -- and the triangle-order kernels not even that, where the view has no queued triangles)
   // (a label view: k_fuse_tri_labels follows the raster launch, or -- labels expanded -- the class-vector kernels as ever)
   // (16-bit class vectors: k_fuse_tri_h16 follows and takes the label kernel's level, see scans_all_planes)
-  const int tri_path = scans_all_planes(r, a, label_bytes, N) ? kLabelsPlaneLevel : plane_optional_level(r, a);
+  const int tri_path = scans_all_planes(r, a, in.kind, N) ? kLabelsPlaneLevel : plane_optional_level(r, a);
   SMESH_TRY(render_into(r, cam, d_idx, /*d_depth=*/nullptr, ctx->stream, slot, tri_path));
-  SMESH_TRY(fuse_rendered(r, a, slot, d_idx, probs, weights, memkind, W, H, 0, 0, label_bytes, smp));
+  SMESH_TRY(fuse_rendered(r, a, slot, d_idx, in, weights, memkind, W, H));
   r->fused_seq++;
   return SMESH_OK;
 }
 
 int smesh_fuse_view(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cam, const float* probs,
                     const float* weights, int memkind) {
-  return fuse_view_impl(r, a, cam, probs, weights, memkind, 0);
+  return fuse_view_impl(r, a, cam, ViewInput::f32(probs), weights, memkind);
 }
 
 // A batch of views: smesh_fuse_view for each of them, in order -- except that, with device-resident class vectors, up to
 // kMaxGroup views share each rasteriser launch, and two consecutive views of a triangle renderer are fused by ONE launch
 // (k_fuse_tri<.., 2>: every 64-row accumulator block makes one round trip for both views; same additions in the same order
 // as two calls).  Asynchronous like smesh_fuse_view.
-// (`label_bytes` != 0: label views -- probs[i] are dense label planes in DEVICE memory, fused by k_fuse_tri_labels; the caller has made
-// sure that labels_native() holds for every view)
-// (kSampledMode | dtype: (w,h,C) images in DEVICE memory that `smp` describes, fused by k_fuse_tri_sampled; the caller has made sure
-// that sampled_native() holds)
-static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n,
-                           const float* const* probs, const float* const* weights, int memkind, int label_bytes,
-                           const SampledSrc* smp = nullptr) {
+// `in`: what every image of the call is (view_input.hpp; its own `image` is not looked at), probs[i]: view i's.  Other than F32: the
+// images are in DEVICE memory and the caller has made sure that the kind's own kernel serves every view (labels_native(),
+// half_native(), sampled_native()).
+static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n, const ViewInput& in,
+                           const void* const* probs, const float* const* weights, int memkind) {
+  const bool own_kernel = in.kind != ViewInput::F32;   // k_fuse_tri_labels / _h16 / _sampled follows every raster launch of this call
   if (!r || !a || (n && (!cams || !probs))) return fail(SMESH_ERR_INVALID, "NULL argument");
   for (uint64_t i = 0; i < n; i++) {
     SMESH_TRY(check_camera(&cams[i]));
@@ -2731,8 +2745,8 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     tri_path = plane_optional_level(r, a);   // (fuse_rendered / the group's fusion take k_fuse_tri*: RasterArgs::idx_optional)
     pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && !r->texels && r->F != 0 && smesh_aggregator_can_fuse_triangles(a, r->F) &&
                smesh_aggregator_can_fuse_pair(a);
-    if (label_bytes) {   // k_fuse_tri_labels follows every raster launch of this call: any class count, up to eight views per launch
-      // (or k_fuse_tri_h16, whose tail waves scan the index planes as that kernel's do: the same level, see scans_all_planes)
+    if (own_kernel) {   // k_fuse_tri_labels: any class count, up to eight views per launch
+      // (or k_fuse_tri_h16 / k_fuse_tri_sampled, whose tail waves scan the index planes as that kernel's do: the same level, see scans_all_planes)
       tri_path = kLabelsPlaneLevel;
       pairable = !pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0;
     }
@@ -2746,7 +2760,7 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     bool grouped = !raster_pairs_off && memkind == SMESH_MEM_DEVICE && r->F != 0 && r->V != 0 && gn >= 2;
     for (int v = 0; v < gn && grouped; v++) grouped = queues_fit_group(cams[i + v].width, cams[i + v].height);
     if ((!pairable && !grouped) || i + 1 >= n) {
-      SMESH_TRY(fuse_view_impl(r, a, &cams[i], probs[i], weights ? weights[i] : nullptr, memkind, label_bytes, smp));
+      SMESH_TRY(fuse_view_impl(r, a, &cams[i], in.at(probs[i]), weights ? weights[i] : nullptr, memkind));
       i += 1;
       continue;
     }
@@ -2816,8 +2830,8 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
       for (int j = 0; j < gn; j++) {
         const smesh_renderer::Side& sd = r->side[base + j];
         const uint64_t k = i + (uint64_t)j;
-        rv[j] = RenderedView{sd.frags, sd.big_queue, sd.big_count, static_cast<const uint32_t*>(r->fused[base + j].ptr), probs[k],
-                             weights ? weights[k] : nullptr, cams[k].width, cams[k].height};
+        rv[j] = rendered_view(sd, static_cast<const uint32_t*>(r->fused[base + j].ptr), in.at(probs[k]), weights ? weights[k] : nullptr, cams[k].width,
+                              cams[k].height, false);
         rv[j].no_big = no_big_possible(r, &cams[k]);
         rv[j].kinds = sd.kinds;
       }
@@ -2826,15 +2840,15 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     }
     for (int j = 0; j < gn && !pairable && !texel_multi; j++) {   // class counts beyond k_fuse_tri, foreign primitive counts
       const uint64_t k = i + (uint64_t)j;
-      SMESH_TRY(fuse_rendered(r, a, base + j, static_cast<const uint32_t*>(r->fused[base + j].ptr), probs[k], weights ? weights[k] : nullptr,
-                              SMESH_MEM_DEVICE, cams[k].width, cams[k].height, 0, 0, label_bytes, smp));
+      SMESH_TRY(fuse_rendered(r, a, base + j, static_cast<const uint32_t*>(r->fused[base + j].ptr), in.at(probs[k]), weights ? weights[k] : nullptr,
+                              SMESH_MEM_DEVICE, cams[k].width, cams[k].height));
     }
     // the fusion launches of a group are back to back: one timed region for all of them (smesh_profile_*: a HIP event pair around a
     // single launch adds the dispatch latency that back-to-back launches hide)
     if (pairable) {
       ProfScope fuse_region(ctx, SMESH_PROF_FUSE_SCATTER);
       static const int label_views_cap = std::max(1, env_int("SMESH_FUSE_VIEWS", 8));
-      const int max_nv = label_bytes ? std::min(8, label_views_cap) : smesh_aggregator_max_fused_views(a);
+      const int max_nv = own_kernel ? std::min(8, label_views_cap) : smesh_aggregator_max_fused_views(a);
       for (int j = 0; j < gn;) {
         // the largest of 8 / 4 / 2 / 1 views that fits what is left of the group and what the kernel takes for this class count
         int nv = 1;
@@ -2843,23 +2857,23 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
         for (int v = 0; v < nv; v++) {
           const smesh_renderer::Side& sd = r->side[base + j + v];
           const uint64_t k = i + (uint64_t)(j + v);
-          rv[v] = RenderedView{sd.frags, sd.big_queue, sd.big_count, static_cast<const uint32_t*>(r->fused[base + j + v].ptr), probs[k],
-                               weights ? weights[k] : nullptr, cams[k].width, cams[k].height, 0, 0, true};
+          rv[v] = rendered_view(sd, static_cast<const uint32_t*>(r->fused[base + j + v].ptr), in.at(probs[k]), weights ? weights[k] : nullptr,
+                                cams[k].width, cams[k].height, true);
           rv[v].no_big = no_big_possible(r, &cams[k]);
           rv[v].fine = box_extent_bound(r->bounds, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
-          if (half_dtype_of(label_bytes) || sampled_mode(label_bytes)) { rv[v].probs16 = probs[k]; rv[v].probs = nullptr; }
-          else if (label_bytes) { rv[v].labels = probs[k]; rv[v].probs = nullptr; }
         }
-        if (sampled_mode(label_bytes)) SMESH_TRY(smesh_sampled_fuse_triangles(a, r->F, r->big_capacity, rv, nv, smp));
-        else if (half_dtype_of(label_bytes)) SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, rv, nv, half_dtype_of(label_bytes)));
-        else if (label_bytes) SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, label_bytes));
-        else SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv));
+        switch (in.kind) {
+          case ViewInput::SAMPLED: SMESH_TRY(smesh_sampled_fuse_triangles(a, r->F, r->big_capacity, rv, nv, in.src)); break;
+          case ViewInput::HALF: SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, rv, nv, in.dtype_or_bytes)); break;
+          case ViewInput::LABELS: SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, in.dtype_or_bytes)); break;
+          case ViewInput::F32: SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv)); break;
+        }
         j += nv;
       }
     }
-    if (pairable && sampled_mode(label_bytes)) note_fuse_sampled(smp->dtype);
-    else if (pairable && half_dtype_of(label_bytes)) note_fuse_half(half_dtype_of(label_bytes));
-    else if (pairable) smesh_note_fuse(label_bytes ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
+    if (pairable && in.kind == ViewInput::SAMPLED) note_fuse_sampled(in.src.dtype);
+    else if (pairable && in.kind == ViewInput::HALF) note_fuse_half(in.dtype_or_bytes);
+    else if (pairable) smesh_note_fuse(in.kind == ViewInput::LABELS ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
     if (grouped && group_pipeline) SMESH_HIP(hipEventRecord(r->ev_bank_consumed[base / kMaxGroup], ctx->stream));
     r->fused_seq += (uint64_t)gn;
     i += (uint64_t)gn;
@@ -2869,7 +2883,7 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
 
 int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_camera_t* cams, uint64_t n,
                      const float* const* probs, const float* const* weights, int memkind) {
-  return fuse_views_impl(r, a, cams, n, probs, weights, memkind, 0);
+  return fuse_views_impl(r, a, cams, n, ViewInput::f32(nullptr), reinterpret_cast<const void* const*>(probs), weights, memkind);
 }
 
 }  // extern "C"
@@ -2877,19 +2891,18 @@ int smesh_fuse_views(smesh_renderer_t* r, smesh_aggregator_t* a, const smesh_cam
 // ---- label views (include/smesh_labels.h; the entry points are fusion_labels.hip's) ---------------------------------------------------
 DeviceCtx* smesh_renderer_ctx(smesh_renderer* r) { return r->ctx; }
 
-// smesh_fuse_views for `n` label views whose dense narrow planes (`label_bytes` = 1 or 2 per pixel) and weights are in DEVICE memory.
+// smesh_fuse_views for `n` label views whose dense narrow planes (`in`: LABELS, 1 or 2 bytes per pixel) and weights are in DEVICE memory.
 // Where k_fuse_tri_labels serves the renderer and the aggregator: the group pipeline and the eight-view grouping of smesh_fuse_views,
 // the planes riding in the views' slots.  Else view by view: labels expanded on the device, smesh_fuse_view's path.
 int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* planes,
-                                     const float* const* weights, int label_bytes) {
+                                     const float* const* weights, const ViewInput& in) {
   bool native = true;
   {
     std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
     for (uint64_t i = 0; i < n; i++) native = native && labels_native(r, a, cams[i].width * cams[i].height);
   }
-  const float* const* p = reinterpret_cast<const float* const*>(planes);
-  if (native) return fuse_views_impl(r, a, cams, n, p, weights, SMESH_MEM_DEVICE, label_bytes);
-  for (uint64_t i = 0; i < n; i++) SMESH_TRY(fuse_view_impl(r, a, &cams[i], p[i], weights ? weights[i] : nullptr, SMESH_MEM_DEVICE, label_bytes));
+  if (native) return fuse_views_impl(r, a, cams, n, in, planes, weights, SMESH_MEM_DEVICE);
+  for (uint64_t i = 0; i < n; i++) SMESH_TRY(fuse_view_impl(r, a, &cams[i], in.at(planes[i]), weights ? weights[i] : nullptr, SMESH_MEM_DEVICE));
   return SMESH_OK;
 }
 
@@ -2899,21 +2912,21 @@ int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, con
 // up to kMaxGroup images widened on the device into as many scratch slots, then smesh_fuse_views' own path for that group -- its
 // multi-view launches and shared rasteriser launches, unchanged.
 int smesh_renderer_fuse_views_half(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
-                                   const float* const* weights, int probs_dtype) {
+                                   const float* const* weights, const ViewInput& in) {
+  const int probs_dtype = in.dtype_or_bytes;
   bool native;
   {
     std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
     native = half_native(r, a);
   }
-  const float* const* p = reinterpret_cast<const float* const*>(probs);
-  if (native) return fuse_views_impl(r, a, cams, n, p, weights, SMESH_MEM_DEVICE, kHalfMode | probs_dtype);
+  if (native) return fuse_views_impl(r, a, cams, n, in, probs, weights, SMESH_MEM_DEVICE);
   DeviceCtx* ctx = r->ctx;
   const uint64_t C = smesh_aggregator_classes(a);
   for (uint64_t i = 0; i < n; i += (uint64_t)kMaxGroup) {
     const int m = (int)std::min<uint64_t>((uint64_t)kMaxGroup, n - i);
     size_t slot_bytes = 256;
     for (int v = 0; v < m; v++) slot_bytes = std::max<size_t>(slot_bytes, (cams[i + v].width * cams[i + v].height * C * 4 + 255) & ~(size_t)255);
-    const float* wide[kMaxGroup];
+    const void* wide[kMaxGroup];
     {
       // (the widening kernels go to the main stream, behind the previous group's fusion launches, which read the same slots)
       std::lock_guard<std::recursive_mutex> lock(ctx->mu);
@@ -2921,20 +2934,23 @@ int smesh_renderer_fuse_views_half(smesh_renderer* r, smesh_aggregator* a, const
       for (int v = 0; v < m; v++) {
         const uint64_t W = cams[i + v].width, H = cams[i + v].height;
         const int64_t s[3] = {(int64_t)(H * C), (int64_t)C, 1};
-        SMESH_TRY(smesh_half_widen(a, probs[i + v], probs_dtype, s, W, H, &wide[v], v, slot_bytes, m));
+        const float* out = nullptr;
+        SMESH_TRY(smesh_half_widen(a, probs[i + v], probs_dtype, s, W, H, &out, v, slot_bytes, m));
+        wide[v] = out;
       }
     }
-    SMESH_TRY(fuse_views_impl(r, a, &cams[i], (uint64_t)m, wide, weights ? &weights[i] : nullptr, SMESH_MEM_DEVICE, 0));
+    SMESH_TRY(fuse_views_impl(r, a, &cams[i], (uint64_t)m, ViewInput::f32(nullptr), wide, weights ? &weights[i] : nullptr, SMESH_MEM_DEVICE));
   }
   return SMESH_OK;
 }
 
-// smesh_aggregator_add_rendered for a 16-bit image in DEVICE memory (x / y element strides ps0 / ps1, class stride 1): *done = 1 if
-// `idx_dev` is the untouched output of one of r's latest smesh_renderer_render_device() calls and the view was fused from that
-// render's records (k_fuse_tri_h16, or -- the image widened -- the triangle / texel kernels of the float32 path); *done = 0: nothing
-// happened.
-int smesh_renderer_add_rendered_half(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* probs, int probs_dtype,
-                                     int64_t ps0, int64_t ps1, const float* weights, uint64_t W, uint64_t H, int* done) {
+// smesh_aggregator_add_rendered for an image other than float32 class vectors, in DEVICE memory (`in`: a label plane, a 16-bit image
+// with x / y element strides in.ps0 / ps1 and class stride 1, or a (w,h,C) image that in.src describes): *done = 1 if `idx_dev` is
+// the untouched output of one of r's latest smesh_renderer_render_device() calls and the view was fused from that render's records --
+// by the kind's own kernel, or (labels expanded, 16-bit image widened) by the triangle / texel kernels of the float32 path; a
+// sampled view only where k_fuse_tri_sampled serves it.  *done = 0: nothing happened.
+int smesh_renderer_add_rendered_input(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const ViewInput& in, const float* weights,
+                                      uint64_t W, uint64_t H, int* done) {
   *done = 0;
   DeviceCtx* ctx = r->ctx;
   if (smesh_aggregator_ctx(a) != ctx || W == 0 || H == 0) return SMESH_OK;
@@ -2945,12 +2961,15 @@ int smesh_renderer_add_rendered_half(smesh_aggregator* a, smesh_renderer* r, con
   int side = -1;
   for (int sd = 0; sd < kRecordSides; sd++)
     if (idx_dev == r->last_idx[sd] && W == r->last_W[sd] && H == r->last_H[sd]) side = sd;
-  if (side < 0 || !((!r->texels && smesh_aggregator_can_fuse_triangles(a, r->F)) || (r->texels && smesh_aggregator_can_fuse_texels(a, r->num_primitives))))
-    return SMESH_OK;
+  const bool served = in.kind == ViewInput::SAMPLED ? sampled_native(r, a)
+                                                    : (!r->texels && smesh_aggregator_can_fuse_triangles(a, r->F)) ||
+                                                          (r->texels && smesh_aggregator_can_fuse_texels(a, r->num_primitives));
+  if (side < 0 || !served) return SMESH_OK;
   SMESH_HIP(hipSetDevice(ctx->device));
+  ViewInput view = in;
   const int64_t C = (int64_t)smesh_aggregator_classes(a);
-  if (ps0 == (int64_t)H * C && ps1 == C) ps0 = ps1 = 0;   // (the dense image)
-  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(probs), weights, SMESH_MEM_DEVICE, W, H, ps0, ps1, kHalfMode | probs_dtype));
+  if (in.kind == ViewInput::HALF && in.ps0 == (int64_t)H * C && in.ps1 == C) view.ps0 = view.ps1 = 0;   // (the dense image)
+  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, view, weights, SMESH_MEM_DEVICE, W, H));
   *done = 1;
   return SMESH_OK;
 }
@@ -2961,34 +2980,12 @@ bool smesh_renderer_sampled_native(smesh_renderer* r, smesh_aggregator* a) {
   return sampled_native(r, a);
 }
 
-// smesh_fuse_views for `n` views whose (w,h,C) images (`src`: dtype, size, strides) and (W,H) weights are in DEVICE memory and which
-// k_fuse_tri_sampled serves (smesh_renderer_sampled_native): the group pipeline and the eight-view grouping of smesh_fuse_views.
+// smesh_fuse_views for `n` views whose (w,h,C) images (`in`: SAMPLED, its src their dtype, size and strides) and (W,H) weights are in
+// DEVICE memory and which k_fuse_tri_sampled serves (smesh_renderer_sampled_native): the group pipeline and the eight-view grouping
+// of smesh_fuse_views.
 int smesh_renderer_fuse_views_sampled(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
-                                      const float* const* weights, const SampledSrc* src) {
-  if (!src) return fail(SMESH_ERR_INVALID, "NULL argument");
-  return fuse_views_impl(r, a, cams, n, reinterpret_cast<const float* const*>(probs), weights, SMESH_MEM_DEVICE, kSampledMode | src->dtype, src);
-}
-
-// smesh_renderer_add_rendered_half for a (w,h,C) image in DEVICE memory: *done = 1 if `idx_dev` is the untouched output of one of r's
-// latest smesh_renderer_render_device() calls and k_fuse_tri_sampled fused the view from that render's records; *done = 0: nothing
-// happened.
-int smesh_renderer_add_rendered_sampled(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* probs, const SampledSrc* src,
-                                        const float* weights, uint64_t W, uint64_t H, int* done) {
-  *done = 0;
-  DeviceCtx* ctx = r->ctx;
-  if (!src || smesh_aggregator_ctx(a) != ctx || W == 0 || H == 0) return SMESH_OK;
-  std::lock_guard<std::mutex> g(r->mu);
-  std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  SMESH_TRY(smesh_aggregator_join_exchange(a));
-  int side = -1;
-  for (int sd = 0; sd < kRecordSides; sd++)
-    if (idx_dev == r->last_idx[sd] && W == r->last_W[sd] && H == r->last_H[sd]) side = sd;
-  if (side < 0 || !sampled_native(r, a)) return SMESH_OK;
-  SMESH_HIP(hipSetDevice(ctx->device));
-  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(probs), weights, SMESH_MEM_DEVICE, W, H, 0, 0, kSampledMode | src->dtype, src));
-  *done = 1;
-  return SMESH_OK;
+                                      const float* const* weights, const ViewInput& in) {
+  return fuse_views_impl(r, a, cams, n, in, probs, weights, SMESH_MEM_DEVICE);
 }
 
 // ---- confusion matrices (include/smesh_eval.h; the entry points are eval.hip's) --------------------------------------------------------
@@ -3030,29 +3027,6 @@ int smesh_renderer_with_index_planes(smesh_renderer* r, const smesh_camera_t* ca
     SMESH_TRY(render_into(r, &cams[v], d_idx, /*d_depth=*/nullptr, ctx->stream, 0, /*idx_optional=*/0));
     SMESH_TRY(use(v, d_idx, cams[v].width, cams[v].height));
   }
-  return SMESH_OK;
-}
-
-// smesh_aggregator_add_rendered for a label plane: *done = 1 if `idx_dev` is the untouched output of one of r's latest
-// smesh_renderer_render_device() calls and the view was fused from that render's records (k_fuse_tri_labels, or -- labels expanded --
-// the triangle / texel kernels of the class-vector path); *done = 0: nothing happened.
-int smesh_renderer_add_rendered_labels(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const void* plane, int label_bytes,
-                                       const float* weights, uint64_t W, uint64_t H, int* done) {
-  *done = 0;
-  DeviceCtx* ctx = r->ctx;
-  if (smesh_aggregator_ctx(a) != ctx || W == 0 || H == 0) return SMESH_OK;
-  std::lock_guard<std::mutex> g(r->mu);
-  std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  SMESH_TRY(smesh_aggregator_join_exchange(a));
-  int side = -1;
-  for (int sd = 0; sd < kRecordSides; sd++)
-    if (idx_dev == r->last_idx[sd] && W == r->last_W[sd] && H == r->last_H[sd]) side = sd;
-  if (side < 0 || !((!r->texels && smesh_aggregator_can_fuse_triangles(a, r->F)) || (r->texels && smesh_aggregator_can_fuse_texels(a, r->num_primitives))))
-    return SMESH_OK;
-  SMESH_HIP(hipSetDevice(ctx->device));
-  SMESH_TRY(fuse_rendered(r, a, side, idx_dev, static_cast<const float*>(plane), weights, SMESH_MEM_DEVICE, W, H, 0, 0, label_bytes));
-  *done = 1;
   return SMESH_OK;
 }
 
@@ -3198,9 +3172,9 @@ int smesh_aggregator_add_rendered(smesh_aggregator_t* a, smesh_renderer_t* r, co
       // reads them where they are; the wide-row and texel kernels get a gathered copy (315 MB more traffic per cfg2-sized view)
       if (strided_dev && !r->texels && probs_strides[2] == 1 && !(reinterpret_cast<uintptr_t>(probs) & 3) &&
           smesh_aggregator_takes_strided_probs(a, probs_strides[0], probs_strides[1], 1))
-        return fuse_rendered(r, a, side, idx_dev, probs, weights, probs_mem, W, H, probs_strides[0], probs_strides[1]);
+        return fuse_rendered(r, a, side, idx_dev, ViewInput::f32(probs, probs_strides[0], probs_strides[1]), weights, probs_mem, W, H);
       if (strided_dev) SMESH_TRY(smesh_aggregator_dense_probs(a, probs, probs_strides, W, H, &probs));
-      return fuse_rendered(r, a, side, idx_dev, probs, weights, probs_mem, W, H);
+      return fuse_rendered(r, a, side, idx_dev, ViewInput::f32(probs), weights, probs_mem, W, H);
     }
   }
   const int64_t is[2] = {(int64_t)H, 1};
@@ -3267,8 +3241,8 @@ int smesh_aggregator_add_matched(smesh_aggregator_t* a, smesh_renderer_t* r,
   for (int sd = 0; sd < kRecordSides; sd++)
     if (r->rec_valid[sd] && r->hash_valid[sd] && r->last_W[sd] == W && r->last_H[sd] == H && h[sd] == h[kRecordSides]) side = sd;
   if (side < 0) return SMESH_OK;
-  SMESH_TRY(fuse_rendered(r, a, side, d_img, probs, weights, probs_mem, W, H, dense_probs ? 0 : probs_strides[0],
-                          dense_probs ? 0 : probs_strides[1]));   // asynchronous for DEVICE images, see smesh_aggregator_add_rendered
+  SMESH_TRY(fuse_rendered(r, a, side, d_img, ViewInput::f32(probs, dense_probs ? 0 : probs_strides[0], dense_probs ? 0 : probs_strides[1]), weights,
+                          probs_mem, W, H));   // asynchronous for DEVICE images, see smesh_aggregator_add_rendered
   *matched = 1;
   return SMESH_OK;
 }

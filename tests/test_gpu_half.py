@@ -194,6 +194,87 @@ def test_a_network_output_seen_as_whc_is_fused_in_place(sm, oracle, dtype, C):
     np.testing.assert_array_equal(bits(got), bits(dense.get_raw()))
 
 
+# ---- 3b. every instance, by the reported slot and view count -------------------------------------------------------------------------
+def _boxes(mesh, cams, oidx):
+    """Per view of the "odd" scene: the triangles SURELY queued (their visible pixels alone span more than 8 in x or y) and the
+    triangles SURELY not (the projected vertices span at most 5 pixels either way: at most six pixel columns, eight with a pixel of
+    padding on both sides), both from the CPU side only -- the oracle's index images and the pinhole projection in float64."""
+    key = ("boxes", len(mesh.faces), len(cams))
+    if key in _cache:
+        return _cache[key]
+    P = len(mesh.faces)
+    v = np.asarray(mesh.vertices, np.float64)
+    tri = np.asarray(mesh.faces)
+    big, small = [], []
+    for cam, oi in zip(cams, oidx):
+        pc = v @ cam.rotation.astype(np.float64).T + cam.translation.astype(np.float64)
+        assert (pc[:, 2] > 0).all()                                # seen from outside: nothing near the camera plane
+        uv = pc[:, :2] / pc[:, 2:3] * cam.focal_lengths + cam.principal_point
+        ext = (uv[tri].max(axis=1) - uv[tri].min(axis=1)).max(axis=1)
+        small.append(ext <= 5.0)
+        x, y = np.nonzero(oi < P)
+        f = oi[x, y]
+        lo = np.full((P, 2), 1 << 30)
+        hi = np.full((P, 2), -1)
+        for axis, coord in enumerate((x, y)):
+            np.minimum.at(lo[:, axis], f, coord)
+            np.maximum.at(hi[:, axis], f, coord)
+        big.append(((hi - lo + 1) > 8).any(axis=1) & (hi[:, 0] >= 0))
+    _cache[key] = (np.array(big), np.array(small))
+    return _cache[key]
+
+
+def _fuse_and_report(sm, oracle, which, C, dtype, kind, n, weighted):
+    """`n` views of a scene through k_fuse_tri_h16, checked as test_native_kernel_against_the_oracle checks them: bit-equal to the oracle
+    and to the float32 path on the widened images where no view queues a triangle, else within helpers.assert_fused_close of the
+    float64-accumulating oracle (a wave sums a queued triangle's pixels in tree order here, the medium and big triangle paths of
+    k_fuse_tri in theirs there).  Returns the reported (slot, views) of the last launch."""
+    from semantic_meshes_amd.device import to_device
+    mesh, cams, r, oidx, queued = scene(sm, oracle, which)
+    P = len(mesh.faces)
+    img, wide = images(C, dtype, n=n, seed=2)
+    weights = None
+    if weighted:
+        rng = np.random.default_rng(99)
+        weights = [rng.uniform(0.1, 2.0, size=(W, H)).astype(np.float32) if k % 2 == 0 else None for k in range(n)]   # view 0 has one
+    d_w = None if weights is None else [None if w is None else to_device(w) for w in weights]
+    agg = sm.fusion.MeshAggregator(P, C, kind)
+    agg.fuse_views(r, cams[:n], device_images(sm, img, dtype), d_w, **kw(dtype))
+    assert sm._lib.last_fuse_kernel() == NATIVE
+    instance = sm._lib.get_option("last_fuse_slot"), sm._lib.get_option("last_fuse_views")
+    got = check_against_oracle(oracle, agg, P, C, kind, 0.5, oidx[:n], wide, sum(queued[:n]), weights)
+    if sum(queued[:n]) == 0:
+        ref = sm.fusion.MeshAggregator(P, C, kind)
+        ref.fuse_views(r, cams[:n], [to_device(w) for w in wide], d_w)
+        assert sm._lib.last_fuse_kernel() == "k_fuse_tri"
+        np.testing.assert_array_equal(bits(got), bits(ref.get_raw()))
+    return instance
+
+
+@pytest.mark.parametrize("C", [1, 8, 9, 16, 17, 24, 25, 32, 33, 40, 41, 48])
+def test_every_slot_edge(sm, oracle, C):
+    """The class counts around every register-slot boundary of k_fuse_tri_h16, where the tail piece of a row load can go wrong
+    (test_gpu_sampled.py::test_every_slot_edge for this kernel).  On "fine", the smallest scene without queued triangles: only there
+    are the sums bit-equal to the float32 path's."""
+    dtype = DTYPES[(C // 8 + C) % 2]                                 # one of the two per class count, both on either side of an edge
+    kind = "summax" if C % 2 else "sum"
+    slot, views = _fuse_and_report(sm, oracle, "fine", C, dtype, kind, 3, False)
+    assert slot == (C + 7) // 8 * 8 and views == 1                   # the last launch of 2 + 1
+
+
+@pytest.mark.parametrize("n,last", [(1, 1), (2, 2), (3, 1), (4, 4), (8, 8)])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_every_view_count(sm, oracle, dtype, n, last):
+    """Every view count of the kernel on the "odd" scene: a last, partial block of rows, triangles that one view of a launch queues and
+    another does not (the tail wave then takes them in every view), and weights images on some views."""
+    assert max(1, int(os.environ.get("SMESH_FUSE_VIEWS", "8"))) >= 8
+    mesh, cams, r, oidx, queued = scene(sm, oracle, "odd")
+    assert len(mesh.faces) % 64 != 0
+    big, small = _boxes(mesh, cams, oidx)
+    assert (big[:8].any(axis=0) & small[:8].any(axis=0)).any() and big[0].any()
+    assert _fuse_and_report(sm, oracle, "odd", 19, dtype, "sum", n, True) == (24, last)
+
+
 # ---- 4. the widening route ----------------------------------------------------------------------------------------------------------
 def _widened_kernel(sm):
     kernel = sm._lib.last_fuse_kernel()
