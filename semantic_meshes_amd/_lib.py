@@ -263,6 +263,17 @@ LABEL_COLORS_SIGNATURES = {
     "smesh_aggregator_add_labels_colors": (c_int, EXT_SIGNATURES["smesh_aggregator_add_labels"][1] + _COLORS_TAIL),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_points.h: the closest face of arbitrary points and the
+# fused rows of those faces, product-only like the tables above (no profile slot; the modes are SMESH_VTX_*)
+POINTS_SIGNATURES = {
+    "smesh_surface_index_create": (c_int, [c_void_p, c_u64, c_void_p, c_u64, c_int, P(c_void_p)]),
+    "smesh_surface_index_destroy": (c_int, [c_void_p]),
+    "smesh_surface_index_stats": (c_int, [c_void_p, P(c_u64), P(c_u32), P(c_u64), P(c_u64)]),
+    "smesh_surface_index_nearest": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_float, c_void_p, c_void_p, c_int]),
+    "smesh_point_gather": (c_int, [c_void_p, c_int, c_u64, c_u32, c_void_p, c_u64, c_int, c_int, c_float, c_void_p, c_void_p, c_int]),
+    "smesh_aggregator_point_annotations": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_int, c_float, c_void_p, c_void_p, c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -390,7 +401,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -105,6 +105,9 @@ bool opt_resize_vector();
 // fuse_sampled: the entry points of smesh_sampled.h sample (w,h,C) class vectors inside k_fuse_tri_sampled where it serves the view
 // (default on; 0 / SMESH_FUSE_SAMPLED=0: every call resamples, then fuses; fusion_sampled.hip).  Same sums either way: a test hook.
 bool opt_fuse_sampled();
+// points_grid: smesh_surface_index_nearest walks the index's grid (default on; 0: the exhaustive scan, one lane per point over all faces;
+// points.hip).  Same results either way: a test hook and the baseline of tools/point_transfer_bench.py.
+bool opt_points_grid();
 // Largest class count the tiled path of probs_labels.hip serves.  Read-only option "probs_labels_tile_max_classes".
 constexpr uint32_t kProbsLabelsTileMaxC = 255;
 

@@ -42,6 +42,9 @@ bool opt_probs_labels_tiles() { return g_probs_labels_tiles.load() != 0; }
 static std::atomic<int> g_resize_vector{1};   // (off: the generic path everywhere -- a test hook, resize.hip)
 bool opt_resize_vector() { return g_resize_vector.load() != 0; }
 
+static std::atomic<int> g_points_grid{1};   // (off: the exhaustive scan -- a test hook, points.hip)
+bool opt_points_grid() { return g_points_grid.load() != 0; }
+
 uint64_t smesh_label_prep_launches();      // label_prep.hip
 uint64_t smesh_label_colors_launches();    // label_colors.hip
 
@@ -367,6 +370,8 @@ int smesh_set_option(const char* name, int64_t value) {
   if (!strcmp(name, "resize_vector")) { g_resize_vector.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // fusion_sampled.hip: 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- same sums
   if (!strcmp(name, "fuse_sampled")) { g_fuse_sampled.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  // points.hip: 0 makes smesh_surface_index_nearest scan all faces for every point -- same faces, same distances
+  if (!strcmp(name, "points_grid")) { g_points_grid.store(value != 0 ? 1 : 0); return SMESH_OK; }
   return fail(SMESH_ERR_INVALID, std::string("unknown option: ") + name);
 }
 int smesh_get_option(const char* name, int64_t* value) {
@@ -384,6 +389,7 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "probs_labels_tiles")) { *value = opt_probs_labels_tiles() ? 1 : 0; return SMESH_OK; }
   if (!strcmp(name, "resize_vector")) { *value = opt_resize_vector() ? 1 : 0; return SMESH_OK; }
   if (!strcmp(name, "fuse_sampled")) { *value = opt_fuse_sampled() ? 1 : 0; return SMESH_OK; }
+  if (!strcmp(name, "points_grid")) { *value = opt_points_grid() ? 1 : 0; return SMESH_OK; }
   // read-only (smesh_label_prep.h): the largest map kept in LDS and this process's launches of k_labels_prepare
   if (!strcmp(name, "labels_prepare_map_lds_max")) { *value = (int64_t)SMESH_LABEL_PREP_MAP_LDS_MAX; return SMESH_OK; }
   if (!strcmp(name, "labels_prepare_launches")) { *value = (int64_t)smesh_label_prep_launches(); return SMESH_OK; }

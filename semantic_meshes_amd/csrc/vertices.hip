@@ -53,62 +53,7 @@ __global__ __launch_bounds__(kBlock) void k_vtx_count(const int32_t* __restrict_
   for (int i = 0; i < n; i++) atomicAdd(&count[v[i]], 1u);
 }
 
-// Exclusive scan of in[n] into out[n] in three launches: kScanTile elements per workgroup (four per thread), the workgroup totals by
-// one workgroup, then the totals added back.
-constexpr int kScanPer = 4;
-constexpr int kScanTile = kBlock * kScanPer;
-
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t* lds, uint32_t* total) {
-  const int t = threadIdx.x;
-  lds[t] = x;
-  __syncthreads();
-  for (int d = 1; d < kBlock; d <<= 1) {
-    const uint32_t y = t >= d ? lds[t - d] : 0u;
-    __syncthreads();
-    lds[t] += y;
-    __syncthreads();
-  }
-  const uint32_t incl = lds[t];
-  *total = lds[kBlock - 1];
-  __syncthreads();
-  return incl - x;
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_tiles(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint64_t n,
-                                                       uint32_t* __restrict__ tile_sums) {
-  __shared__ uint32_t lds[kBlock];
-  const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanPer;
-  uint32_t x[kScanPer], sum = 0;
-  for (int i = 0; i < kScanPer; i++) {
-    x[i] = base + i < n ? in[base + i] : 0u;
-    sum += x[i];
-  }
-  uint32_t total;
-  uint32_t run = block_exclusive_scan(sum, lds, &total);
-  for (int i = 0; i < kScanPer; i++) {
-    if (base + i < n) out[base + i] = run;
-    run += x[i];
-  }
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_sums(uint32_t* __restrict__ sums, uint64_t n) {   // one workgroup, in place
-  __shared__ uint32_t lds[kBlock];
-  uint32_t carry = 0;
-  for (uint64_t base = 0; base < n; base += kBlock) {
-    const uint64_t i = base + threadIdx.x;
-    const uint32_t x = i < n ? sums[i] : 0u;
-    uint32_t total;
-    const uint32_t excl = block_exclusive_scan(x, lds, &total);
-    if (i < n) sums[i] = carry + excl;
-    carry += total;
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_add(uint32_t* __restrict__ out, uint64_t n, const uint32_t* __restrict__ tile_sums) {
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < n) out[i] += tile_sums[i / kScanTile];
-}
+#include "scan.inc.hpp"   // k_scan_tiles, k_scan_sums, k_scan_add
 
 // `cursor` is all zero: the order in which the faces of a vertex arrive is whatever the atomics make it -- the sort below undoes it.
 __global__ __launch_bounds__(kBlock) void k_vtx_fill(const int32_t* __restrict__ faces, uint64_t F, const uint32_t* __restrict__ offsets,
@@ -421,9 +366,7 @@ int build_map(smesh_vertex_map* m, const int32_t* faces) {
     hipLaunchKernelGGL(k_vtx_count, gf, b, 0, st, d_faces, F, V, count, flags);
   }
   // offsets = exclusive scan of count[0 .. V] (count[V] == 0, so offsets[V] is the number of entries)
-  hipLaunchKernelGGL(k_scan_tiles, dim3((uint32_t)ntiles), b, 0, st, count, m->offsets, n, tiles);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), b, 0, st, tiles, ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3((uint32_t)div_up(n, kBlock)), b, 0, st, m->offsets, n, tiles);
+  launch_exclusive_scan(count, m->offsets, n, tiles, st);
   SMESH_HIP(hipGetLastError());
   uint32_t h_flags[4] = {0, 0, 0, 0}, h_nnz = 0;
   SMESH_HIP(hipMemcpyAsync(h_flags, flags, 16, hipMemcpyDeviceToHost, st));

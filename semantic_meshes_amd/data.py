@@ -120,29 +120,76 @@ class Ply(Mesh):
         _write_ply_vertex_colors(path, self.vertices, self.faces, colors, binary)
 
 
+def _read_ply_header(fh, path):
+    """(format, [(element name, count, [properties])]) of the PLY header that `fh` is positioned in front of; a scalar property is
+    (name, numpy type code), a list property (name, "list", count type, item type).  `fh` is left at the first byte of the body."""
+    if fh.readline().strip() != b"ply":
+        raise ValueError("%s is not a PLY file" % path)
+    fmt, elements = None, []
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError("unterminated PLY header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] == "comment" or tok[0] == "obj_info":
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1][2].append((tok[4], "list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+            else:
+                elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
+        elif tok[0] == "end_header":
+            break
+    return fmt, elements
+
+
+def read_ply_vertex_property(path, name):
+    """One scalar property of a PLY file's `vertex` element as a 1-D numpy array in the file's dtype (native byte order) -- ScanNet's
+    ground truth is the `label` property of `_vh_clean_2.labels.ply`, which the reference reads with `plyfile`.  ascii and both binary
+    byte orders; `ValueError` when the file has no such property."""
+    with open(path, "rb") as fh:
+        fmt, elements = _read_ply_header(fh, path)
+        if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+            raise ValueError("%s: unknown PLY format %r" % (path, fmt))
+        end = "<" if fmt == "binary_little_endian" else ">"
+        rows = fh.read().decode("ascii", "replace").split("\n") if fmt == "ascii" else None
+        pos = 0
+        for element, count, props in elements:
+            if element != "vertex":                  # (an element in front of the vertices: step over it)
+                if fmt == "ascii":
+                    pos += count
+                elif all(len(p) == 2 for p in props):
+                    fh.seek(sum(np.dtype(p[1]).itemsize for p in props) * count, 1)
+                else:
+                    _binary_lists(fh, count, props, end)
+                continue
+            names = [p[0] for p in props]
+            if name not in names or len(props[names.index(name)]) != 2:
+                raise ValueError("%s: the vertex element has no scalar property %r (it has %s)" % (path, name, ", ".join(names)))
+            if any(len(p) != 2 for p in props):
+                raise ValueError("%s: list properties in the vertex element are not supported" % path)
+            code = props[names.index(name)][1]
+            if fmt == "ascii":
+                k = names.index(name)
+                column = [r.split()[k] for r in rows[pos:pos + count]]
+                if len(column) != count:
+                    raise ValueError("%s: truncated vertex element" % path)
+                return np.array([float(t) if code[0] == "f" else int(t) for t in column], dtype=np.dtype(code)).reshape(-1)
+            dt = np.dtype([(p[0], end + p[1]) for p in props])
+            blob = fh.read(dt.itemsize * count)
+            if len(blob) != dt.itemsize * count:
+                raise ValueError("%s: truncated vertex element" % path)
+            return np.ascontiguousarray(np.frombuffer(blob, dtype=dt, count=count)[name].astype(np.dtype(code)))
+    raise ValueError("%s has no vertex element" % path)
+
+
 def _read_ply(path):
     with open(path, "rb") as fh:
-        if fh.readline().strip() != b"ply":
-            raise ValueError("%s is not a PLY file" % path)
-        fmt, elements = None, []
-        while True:
-            line = fh.readline()
-            if not line:
-                raise ValueError("unterminated PLY header")
-            tok = line.decode("ascii", "replace").split()
-            if not tok or tok[0] == "comment" or tok[0] == "obj_info":
-                continue
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                elements.append((tok[1], int(tok[2]), []))
-            elif tok[0] == "property":
-                if tok[1] == "list":
-                    elements[-1][2].append((tok[4], "list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
-                else:
-                    elements[-1][2].append((tok[2], _PLY_TYPES[tok[1]]))
-            elif tok[0] == "end_header":
-                break
+        fmt, elements = _read_ply_header(fh, path)
         verts = faces = None
         if fmt == "ascii":
             rows = fh.read().decode("ascii", "replace").split("\n")

@@ -1433,6 +1433,185 @@ class VertexTransfer:
         return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, True)[1]
 
 
+def _same_device(obj, device, what):
+    if isinstance(obj, DeviceArray) and obj.device != device:
+        raise ValueError("%s lives on device %d, not on device %d" % (what, obj.device, device))
+
+
+def _dense_points(points, device, streams):
+    """(pointer, memkind, N, keep-alive) of a dense float32 [N,3] array of query points on the host or the device."""
+    if isinstance(points, np.ndarray) and points.dtype != np.float32:
+        raise ValueError("points must be float32, got %s" % points.dtype)
+    _same_device(points, device, "points")
+    ptr, mem, shape, dt, strides, keep = describe(points, 2, "points", device, streams)
+    if dt != np.float32:
+        raise ValueError("points must be float32, got %s" % dt)
+    if shape[1] != 3:
+        raise ValueError("points must be float32[N,3], got shape %s" % (tuple(shape),))
+    if shape[0] > 1 and tuple(strides) != (3, 1) or strides[1] != 1:
+        if mem != _lib.MEM_HOST:
+            raise ValueError("points must be dense (row-major, no padding)")
+        keep = np.ascontiguousarray(keep)
+        ptr = keep.ctypes.data
+    return ptr, mem, int(shape[0]), keep
+
+
+class SurfaceIndex:
+    """The closest face of arbitrary points, on the device (include/smesh_points.h): a uniform grid over the faces of a mesh, built
+    once on `device`.  `vertices`: float32 [V,3], `faces`: int [F,3].  The closest face of a point is defined to the bit -- the
+    smallest float32 `dist2` of the header's rule over ALL faces, the lowest face among equal values -- and the grid only finds
+    it faster."""
+
+    def __init__(self, vertices, faces, device=0):
+        v, f = np.asarray(vertices), np.asarray(faces)
+        if v.ndim != 2 or v.shape[1] != 3 or v.dtype.kind != "f":
+            raise ValueError("vertices must be a float array [V,3], got %s %s" % (v.dtype, v.shape))
+        if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+            raise ValueError("faces must be an integer array [F,3], got %s %s" % (f.dtype, f.shape))
+        if f.size and (f.min() < 0 or f.max() >= len(v)):      # (the library checks again, on the device)
+            raise ValueError("face indices out of range [0, %d)" % len(v))
+        v, f = np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(f, dtype=np.int32)
+        self.num_faces, self.device = len(f), int(device)
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().smesh_surface_index_create(v.ctypes.data_as(ctypes.c_void_p), len(v), f.ctypes.data_as(ctypes.c_void_p),
+                                                        len(f), self.device, ctypes.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_mesh(cls, mesh, device=0):
+        return cls(mesh.vertices, mesh.faces, device)
+
+    @classmethod
+    def from_renderer(cls, texel_renderer, vertices):
+        """For a texel renderer: its layout's faces, the order `face_annotations()` returns its rows in."""
+        if not hasattr(texel_renderer, "texel_layout"):
+            raise ValueError("from_renderer needs a texel renderer (render.texels)")
+        return cls(vertices, texel_renderer.texel_layout()[0], texel_renderer.device)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            try:
+                _lib.lib().smesh_surface_index_destroy(h)
+            except Exception:
+                pass
+
+    def stats(self):
+        """`dict(faces, dims, entries, large_faces)`: the grid's dimensions, the entries of its cells' face lists, and the faces
+        that every query tests (a box over too many cells, or no area)."""
+        F, entries, large = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        dims = (ctypes.c_uint32 * 3)()
+        _lib.check(_lib.lib().smesh_surface_index_stats(self._h, ctypes.byref(F), dims, ctypes.byref(entries), ctypes.byref(large)))
+        return dict(faces=int(F.value), dims=tuple(int(d) for d in dims), entries=int(entries.value), large_faces=int(large.value))
+
+    def _nearest(self, points, max_distance, on_device):
+        from .device import DeviceBuffer
+        R = float("inf") if max_distance is None else float(max_distance)
+        if not R >= 0:
+            raise ValueError("max_distance must be >= 0 (or None), got %r" % (max_distance,))
+        streams = []
+        ptr, mem, N, keep = _dense_points(points, self.device, streams)
+        if on_device:
+            faces = DeviceBuffer(max(N * 4, 4), self.device).view((N,), np.int32)
+            dist2 = DeviceBuffer(max(N * 4, 4), self.device).view((N,), np.float32)
+            pf, pd, omem = ctypes.c_void_p(faces.ptr), ctypes.c_void_p(dist2.ptr), _lib.MEM_DEVICE
+        else:
+            faces, dist2 = np.empty(N, np.int32), np.empty(N, np.float32)
+            pf, pd, omem = faces.ctypes.data_as(ctypes.c_void_p), dist2.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST
+        _lib.check(_lib.lib().smesh_surface_index_nearest(self._h, ctypes.c_void_p(ptr), N, mem, R, pf, pd, omem))
+        release_to(self.device, streams)
+        return faces, dist2
+
+    def nearest(self, points, max_distance=None):
+        """`(faces int32 [N], dist2 float32 [N])` of float32 [N,3] `points` (numpy, or a dense device array): the closest face and
+        its squared distance; `(-1, inf)` for a point farther than `max_distance` from every face, a point with a non-finite
+        coordinate, and every point of a mesh without faces."""
+        return self._nearest(points, max_distance, False)
+
+    def nearest_device(self, points, max_distance=None):
+        """`nearest()` left in HBM: two `DeviceArray`s."""
+        return self._nearest(points, max_distance, True)
+
+
+class PointTransfer:
+    """Fused results for points that are not the mesh's vertices: the ground truth's vertices on a simplified, COLMAP or texel mesh, a
+    lidar scan, a submission file.  Holds the closest face of every point (`SurfaceIndex.nearest_device`) on the device; a `source` is
+    what it is for `VertexTransfer` -- a MeshAggregator over the index's F faces (its `get()` never leaves the device), a float32
+    [F,C] numpy array or a dense float32 [F,C] device array; for a texel renderer, `renderer.face_annotations(aggregator)`.
+    sums[i] is the row of point i's face (zeros without one); annotations[i] is that row divided by its total, all zero where the
+    total is below `dont_care_threshold` or the point has no face; labels[i] is the row's argmax, -1 where don't care."""
+
+    def __init__(self, index, points, max_distance=None):
+        if not isinstance(index, SurfaceIndex):
+            raise ValueError("PointTransfer needs a SurfaceIndex")
+        self.index, self.device = index, index.device
+        self.faces, self.dist2 = index.nearest_device(points, max_distance)
+        self.num_points = self.faces.shape[0]
+
+    def _run(self, source, mode, threshold, want_rows, want_labels, on_device):
+        from .device import DeviceBuffer
+        N, F = self.num_points, self.index.num_faces
+        if isinstance(source, _MeshAggregator):
+            if source.primitives != F:
+                raise ValueError("the aggregator has %d primitives, the indexed mesh %d faces" % (source.primitives, F))
+            if source.device != self.device:
+                raise ValueError("aggregator and PointTransfer live on different devices")
+            C = source.classes
+        else:
+            streams = []
+            _same_device(source, self.device, "face rows")
+            ptr, mem, C, keep = _dense_rows(source, F, "face rows", self.device, streams)
+        rows = labels = None
+        if on_device:
+            if want_rows:
+                rows = DeviceBuffer(max(N * C * 4, 4), self.device).view((N, C), np.float32)
+            if want_labels:
+                labels = DeviceBuffer(max(N * 4, 4), self.device).view((N,), np.int32)
+            prow, plab, omem = (None if rows is None else ctypes.c_void_p(rows.ptr), None if labels is None else ctypes.c_void_p(labels.ptr),
+                                _lib.MEM_DEVICE)
+        else:
+            if want_rows:
+                rows = result_empty((N, C), np.float32)
+            if want_labels:
+                labels = np.empty(N, np.int32)
+            prow, plab, omem = (None if rows is None else rows.ctypes.data_as(ctypes.c_void_p),
+                                None if labels is None else labels.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST)
+        pf = ctypes.c_void_p(self.faces.ptr)
+        if isinstance(source, _MeshAggregator):
+            # (`_h`: the aggregator's deferred views are handed to the library first, as get() does)
+            _lib.check(_lib.lib().smesh_aggregator_point_annotations(source._h, pf, N, _lib.MEM_DEVICE, mode, float(threshold), prow, plab, omem))
+            source._drain()
+        else:
+            _lib.check(_lib.lib().smesh_point_gather(ctypes.c_void_p(ptr), mem, F, C, pf, N, _lib.MEM_DEVICE, mode, float(threshold),
+                                                    prow, plab, omem))
+            release_to(self.device, streams)
+        return rows, labels
+
+    def sums(self, source):
+        """float32 [N,C]: per point, the row of its closest face."""
+        return self._run(source, _lib.VTX_SUMS, 0.0, True, False, False)[0]
+
+    def annotations(self, source, dont_care_threshold=0.9):
+        """float32 [N,C]: the rows renormalised; all-zero rows where the total is below `dont_care_threshold` or there is no face."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, False)[0]
+
+    def labels(self, source, dont_care_threshold=0.9):
+        """int32 [N]: the class with the largest value (the lowest one among equals), -1 where don't care.  No [N,C] array is made."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, False)[1]
+
+    def sums_device(self, source):
+        """`sums()` left in HBM: a `DeviceArray` in a fresh allocation owned by the returned object."""
+        return self._run(source, _lib.VTX_SUMS, 0.0, True, False, True)[0]
+
+    def annotations_device(self, source, dont_care_threshold=0.9):
+        """`annotations()` left in HBM."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, True)[0]
+
+    def labels_device(self, source, dont_care_threshold=0.9):
+        """`labels()` left in HBM: what `ConfusionMatrix.add` takes beside the points' ground truth."""
+        return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, True)[1]
+
+
 class MeshAggregatorSum(_MeshAggregator):
     pass
 
