@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +52,7 @@ struct DeviceCtx {
   hipEvent_t ev_order = nullptr;        // smesh_stream_wait: marks the producer's stream
   hipEvent_t ev_release = nullptr;      // smesh_stream_release: marks the library's stream
   int num_cus = 256;
+  uint32_t lds_per_cu = 65536;          // bytes of LDS a CU's workgroups share (gfx950: 163 840)
   unsigned profiling = 0;   // bit s set = bracket slot s with HIP events
   unsigned profile_every = 1;   // ... every n-th region of the slot (an event pair costs ~4 us of stream time)
   ProfSlot slots[SMESH_PROF_SLOTS];
@@ -93,6 +95,47 @@ bool opt_group_pipeline();
 // renderer and run without a vertex stage (raster.hip: render_group_into; SMESH_RASTER_MESHLETS=0 / 1).
 constexpr int kRasterMeshletsDefault = 1;
 bool opt_raster_meshlets();
+// pipeline_fit (SMESH_PIPELINE_FIT; default 1): the LDS pad that caps the eight-view fusion launch of the group pipeline is computed from
+// the device's LDS and the instance's own (pipeline_fuse_pad below); 0: the constant 24 576 bytes of rounds 2 - 6, kept selectable so that
+// both can be compared in one process.  Same results either way.
+// pipeline_fuse_waves (SMESH_PIPELINE_FUSE_WAVES; default kPipelineFuseWaves): the fusion waves per CU the computed pad allows at most.
+// pipeline_fuse_pad (SMESH_PIPELINE_FUSE_PAD; default -1: none): a pad in bytes that overrides both.
+constexpr int kPipelineFitDefault = 1;
+constexpr int kPipelineFuseWaves = 5;
+int opt_pipeline_fit();
+int opt_pipeline_fuse_waves();
+int opt_pipeline_fuse_pad();
+
+// What runs on the raster stream beside a pipelined fusion launch: the LDS and registers of a workgroup (four waves, one per SIMD) of
+// the fragment kernel of the renderer at hand.  Zero: not known.
+struct PipelineNeighbour {
+  uint32_t wg_lds = 0, wg_vgprs = 0;
+};
+
+// The dynamic LDS of a one-wave fusion workgroup that lets `want` of them onto a CU and no more: the smallest such pad, which leaves
+// the neighbour the most.  *beside (may be null): how many rasteriser workgroups then fit beside `want` fusion waves, by the LDS that
+// is left and by the registers -- the SIMD with the most fusion waves decides, a workgroup puts a wave on each.  Registers are
+// allocated in eights out of 512 per SIMD lane and a SIMD holds eight waves; LDS is counted in blocks of 1 280 bytes, a multiple of
+// every allocation granule of the CDNA parts.  `static_lds`, `vgprs`: of the fusion instance.  (`want` is held between 2 and 32: half
+// a CU's LDS is more than a launch may ask for.  Lowering `want` until all the workgroups the registers allow also fit the LDS was
+// tried and lost: the fusion launch needs its five waves more than the rasteriser needs a third workgroup, NOTES/pipeline_fit.md.)
+inline uint32_t pipeline_fuse_pad(uint32_t lds_per_cu, uint32_t static_lds, uint32_t vgprs, int want, const PipelineNeighbour& nb,
+                                  int* beside = nullptr) {
+  constexpr uint32_t kBlock = 1280u;
+  auto blocks = [&](uint32_t bytes) { return (bytes + kBlock - 1u) / kBlock * kBlock; };
+  const uint32_t n = (uint32_t)std::min(32, std::max(2, want));
+  // the smallest workgroup, in whole blocks, of which n + 1 no longer fit
+  const uint32_t wg = std::max(blocks(static_lds), (lds_per_cu / (n + 1u)) / kBlock * kBlock + kBlock);
+  if (beside) {
+    const uint32_t alloc_f = std::max(8u, (vgprs + 7u) / 8u * 8u), alloc_r = std::max(8u, (nb.wg_vgprs + 7u) / 8u * 8u);
+    const uint32_t per_simd = (n + 3u) / 4u;
+    const uint32_t left = (uint64_t)wg * n <= lds_per_cu ? lds_per_cu - wg * n : 0u;
+    const uint32_t regs_left = per_simd * alloc_f < 512u ? 512u - per_simd * alloc_f : 0u;
+    const uint32_t by_regs = std::min(regs_left / alloc_r, per_simd < 8u ? 8u - per_simd : 0u);
+    *beside = (int)std::min(by_regs, nb.wg_lds ? left / blocks(nb.wg_lds) : by_regs);
+  }
+  return wg - static_lds;
+}
 // confusion_wave_aggregate: k_confusion adds the population count of the lanes that share a key once (default on; eval.hip).
 bool opt_confusion_wave_aggregate();
 
@@ -208,6 +251,7 @@ struct RenderedView {
   bool no_big = false;          // PROVEN on the host (raster.hip no_big_possible): no triangle of this view has a box over 8 x 8 pixels -- big_queue is empty
   const uint8_t* kinds = nullptr;   // texel renderers: TriFrag::kind of every triangle again, a byte each (RasterArgs::kinds)
   bool fine = false;            // bounded on the host (raster.hip box_extent_bound <= 48 pixels): a finely tessellated mesh seen from outside -- few or no queued triangles
+  PipelineNeighbour beside;     // group pipeline: what the renderer's next group runs beside this view's fusion launch (raster.hip; zeros: unknown)
   const void* image = nullptr;  // what stands in for `probs` in the views of k_fuse_tri_labels, k_fuse_tri_h16 and k_fuse_tri_sampled: the dense label
                                 // plane [W][H], the 16-bit image [W][H][C] (strides: ps0, ps1), the network's (w,h,C) image (view_input.hpp)
 };

@@ -80,6 +80,21 @@ bool opt_raster_meshlets() {
   return v != 0;
 }
 
+// "pipeline_fit", "pipeline_fuse_waves", "pipeline_fuse_pad" (common.hpp): how the group pipeline's two kernels are fitted into a CU.
+// -2: not set by smesh_set_option -- the environment, read once, else the default.
+static std::atomic<int> g_pipeline_fit{-2}, g_pipeline_fuse_waves{-2}, g_pipeline_fuse_pad{-2};
+static int opt_env_once(std::atomic<int>& g, const char* env, int def, int lo, int hi) {
+  int v = g.load();
+  if (v == -2) {
+    v = std::min(hi, std::max(lo, env_int(env, def)));
+    g.store(v);
+  }
+  return v;
+}
+int opt_pipeline_fit() { return opt_env_once(g_pipeline_fit, "SMESH_PIPELINE_FIT", kPipelineFitDefault, 0, 1); }
+int opt_pipeline_fuse_waves() { return opt_env_once(g_pipeline_fuse_waves, "SMESH_PIPELINE_FUSE_WAVES", kPipelineFuseWaves, 2, 32); }
+int opt_pipeline_fuse_pad() { return opt_env_once(g_pipeline_fuse_pad, "SMESH_PIPELINE_FUSE_PAD", -1, -1, 65536 - 16384); }
+
 static std::mutex g_ctx_mu;
 static std::vector<std::unique_ptr<DeviceCtx>> g_ctx;
 
@@ -106,6 +121,7 @@ int get_ctx(int device, DeviceCtx** out) {
     hipDeviceProp_t prop;
     SMESH_HIP(hipGetDeviceProperties(&prop, device));
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    ctx->lds_per_cu = (uint32_t)std::min<size_t>(std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, 65536), 1u << 20);
     // (Round 6 measured the two streams confined to disjoint sets of CUs -- hipExtStreamCreateWithCUMask, 4 or 5 of every 8 CUs for the
     // rasteriser -- so that the group pipeline's two kernels would not share CUs: 15 442 / 15 499 views/s against 15 370 with masks
     // that interleave inside an XCD, 9 000 - 11 000 with masks that give whole XCDs away.  Not kept.)
@@ -346,6 +362,8 @@ void Scratch::release() {
 using namespace smesh;
 
 void smesh_last_fuse_instance(int* slot, int* views);   // fusion.hip: the calling thread's last triangle-order launch
+uint32_t smesh_last_fuse_lds_pad();                     // fusion.hip: dynamic LDS of the calling thread's last eight-view k_fuse_tri launch
+int smesh_last_fuse_beside();                           // fusion.hip: rasteriser workgroups per CU the last computed pad leaves room for
 int smesh_last_fuse_probs_dtype();                      // raster.hip: SMESH_PROBS_* of the class vectors the calling thread's last fusion read
 
 extern "C" {
@@ -361,6 +379,10 @@ int smesh_set_option(const char* name, int64_t value) {
   if (!name) return fail(SMESH_ERR_INVALID, "option name is NULL");
   if (!strcmp(name, "group_pipeline")) { g_group_pipeline.store(value != 0 ? 1 : 0); return SMESH_OK; }
   if (!strcmp(name, "raster_meshlets")) { g_raster_meshlets.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  // how the group pipeline's two kernels share a CU (common.hpp): same results whatever the values
+  if (!strcmp(name, "pipeline_fit")) { g_pipeline_fit.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  if (!strcmp(name, "pipeline_fuse_waves")) { g_pipeline_fuse_waves.store((int)std::min<int64_t>(32, std::max<int64_t>(2, value))); return SMESH_OK; }
+  if (!strcmp(name, "pipeline_fuse_pad")) { g_pipeline_fuse_pad.store((int)std::min<int64_t>(65536 - 16384, std::max<int64_t>(-1, value))); return SMESH_OK; }
   // k_confusion (eval.hip): lanes of a wave that share a key add their population count once (1, the default), or every lane adds 1
   // for itself (0) -- same counts; tools/confusion_bench.py measures both
   if (!strcmp(name, "confusion_wave_aggregate")) { g_confusion_wave_aggregate.store(value != 0 ? 1 : 0); return SMESH_OK; }
@@ -378,6 +400,13 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!name || !value) return fail(SMESH_ERR_INVALID, "NULL argument");
   if (!strcmp(name, "group_pipeline")) { *value = opt_group_pipeline() ? 1 : 0; return SMESH_OK; }
   if (!strcmp(name, "raster_meshlets")) { *value = opt_raster_meshlets() ? 1 : 0; return SMESH_OK; }
+  if (!strcmp(name, "pipeline_fit")) { *value = opt_pipeline_fit(); return SMESH_OK; }
+  if (!strcmp(name, "pipeline_fuse_waves")) { *value = opt_pipeline_fuse_waves(); return SMESH_OK; }
+  if (!strcmp(name, "pipeline_fuse_pad")) { *value = opt_pipeline_fuse_pad(); return SMESH_OK; }
+  // read-only (reporting, like "last_fuse_slot"): the dynamic LDS of the calling thread's last eight-view k_fuse_tri launch, and the
+  // rasteriser workgroups per CU that pad was computed to leave room for
+  if (!strcmp(name, "last_fuse_lds_pad")) { *value = (int64_t)smesh_last_fuse_lds_pad(); return SMESH_OK; }
+  if (!strcmp(name, "last_fuse_beside")) { *value = (int64_t)smesh_last_fuse_beside(); return SMESH_OK; }
   // read-only: up to this class count k_fuse_tri_labels keeps a wave's rows in LDS, beyond it read-modify-writes them in global memory
   if (!strcmp(name, "labels_lds_max_classes")) { *value = (int64_t)kLabelsLdsMaxC; return SMESH_OK; }
   // read-only (smesh_half.h): the largest class count k_fuse_tri_h16 serves; the dtype of the class vectors the last fusion read

@@ -44,6 +44,8 @@ using namespace smesh;
 
 // fusion_pair.hip: k_fuse_tri<CT, KIND, EXACT, 2> for the class-count slot `tri_ct` chosen below
 void smesh_launch_fuse_tri_multi(int kind, int tri_ct, int nviews, dim3 grid, hipStream_t st, const TriFuseArgs& t, const TriViews<8>& tv);
+// fusion_multi8.hip: static LDS and registers of the eight-view instance of that slot
+bool smesh_fuse_tri_8_resources(int kind, int tri_ct, uint32_t* static_lds, uint32_t* vgprs);
 
 namespace {
 
@@ -2474,6 +2476,10 @@ static bool launch_fuse_wide_list(int wide_chunks, uint32_t C, dim3 grid, hipStr
 // k_fuse_tri_any / k_fuse_tri_wide / k_fuse_tri_wide_list, -1 before the first launch; and the `nviews` of that launch.
 static thread_local int g_last_fuse_slot = -1;
 static thread_local int g_last_fuse_views = 0;
+static thread_local uint32_t g_last_fuse_lds_pad = 0u;   // dynamic LDS of the last k_fuse_tri launch of eight views (read-only option "last_fuse_lds_pad")
+static thread_local int g_last_fuse_beside = -1;         // ... and the rasteriser workgroups that pad was computed to leave room for per CU (-1: never computed)
+uint32_t smesh_last_fuse_lds_pad() { return g_last_fuse_lds_pad; }
+int smesh_last_fuse_beside() { return g_last_fuse_beside; }
 void smesh_last_fuse_instance(int* slot, int* views) { *slot = g_last_fuse_slot; *views = g_last_fuse_views; }
 void smesh_set_last_fuse_instance(int slot, int views) { g_last_fuse_slot = slot; g_last_fuse_views = views; }   // (fusion_sampled.hip: register slots, views)
 
@@ -2579,7 +2585,19 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
     // triangles at 1080p 0.102 -> 0.112 ms per view with it.
     bool fine = true;
     for (int v = 0; v < nviews; v++) fine = fine && views[v].fine;
-    t.lds_pad = (fine && opt_group_pipeline() && nparts == 1) ? 24576u : 0u;
+    // The pad is the smallest that caps the launch at pipeline_fuse_waves workgroups per CU, whatever the instance's own LDS and the
+    // device's (common.hpp: pipeline_fuse_pad; until the meshlet rasteriser took LDS of its own the pad was the constant that option
+    // "pipeline_fit" 0 still selects, which left the rasteriser one workgroup per CU where this leaves it two).  Option
+    // "pipeline_fuse_pad" overrides it.
+    t.lds_pad = 0u;
+    if (fine && opt_group_pipeline() && nparts == 1 && nviews == 8 && specialised) {
+      uint32_t static_lds = 0u, vgprs = 0u;
+      const int forced = opt_pipeline_fuse_pad();
+      if (forced >= 0) t.lds_pad = (uint32_t)forced;
+      else if (!opt_pipeline_fit() || !smesh_fuse_tri_8_resources(a->kind, tri_ct, &static_lds, &vgprs)) t.lds_pad = 24576u;
+      else t.lds_pad = pipeline_fuse_pad(ctx->lds_per_cu, static_lds, vgprs, opt_pipeline_fuse_waves(), views[0].beside, &g_last_fuse_beside);
+    }
+    g_last_fuse_lds_pad = t.lds_pad;
   }
   const dim3 grid(t.tri_blocks + big_waves + mid_waves), block(kWave);
   const dim3 tgrid(t.tri_blocks), bgrid(big_waves);                        // any-C paths: big triangles in a second launch

@@ -1923,6 +1923,24 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
 hipError_t alloc_side(smesh_renderer* r, int i);
 thread_local const char* g_last_raster_path = "none";   // smesh_last_raster_path()
 
+// What a grouped render of `r` puts beside a pipelined fusion launch (common.hpp): the registers and LDS of a workgroup of its fragment
+// kernel, from the code object, asked once.
+PipelineNeighbour raster_pipeline_neighbour(const smesh_renderer* r) {
+  static std::once_flag once;
+  static uint32_t ml_vgprs = 96u, ml_lds = 0u, plain_vgprs = 96u, plain_lds = 0u;
+  std::call_once(once, [] {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_raster_frag_group_ml<0>)) == hipSuccess) { ml_vgprs = (uint32_t)std::max(1, fa.numRegs); ml_lds = (uint32_t)fa.sharedSizeBytes; }
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_raster_frag_group<0>)) == hipSuccess) { plain_vgprs = (uint32_t)std::max(1, fa.numRegs); plain_lds = (uint32_t)fa.sharedSizeBytes; }
+    (void)hipGetLastError();
+  });
+  PipelineNeighbour nb;
+  const bool meshlets = r->ml.tris != nullptr && opt_raster_meshlets();
+  nb.wg_vgprs = meshlets ? ml_vgprs : plain_vgprs;
+  nb.wg_lds = meshlets ? ml_lds : plain_lds;
+  return nb;
+}
+
 // Scratch of view slot `i` (smesh_fuse_views rasterises several views per launch).
 // `need_sv`: the launch has a vertex stage (a slot that only ever sees meshlet launches never gets the 24 bytes per vertex).
 hipError_t alloc_scratch(smesh_renderer* r, int i, bool need_sv) {
@@ -2860,6 +2878,7 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
           rv[v] = rendered_view(sd, static_cast<const uint32_t*>(r->fused[base + j + v].ptr), in.at(probs[k]), weights ? weights[k] : nullptr,
                                 cams[k].width, cams[k].height, true);
           rv[v].no_big = no_big_possible(r, &cams[k]);
+          rv[v].beside = raster_pipeline_neighbour(r);
           rv[v].fine = box_extent_bound(r->bounds, &cams[k]) <= 48.0;      // (the bound is ~4 x the largest box: cfg2 13 - 33, boxes under 8 pixels; a 250 000-triangle mesh at 1080p 27 - 66, boxes of ~12)
         }
         switch (in.kind) {
