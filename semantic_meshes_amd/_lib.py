@@ -274,6 +274,24 @@ POINTS_SIGNATURES = {
     "smesh_aggregator_point_annotations": (c_int, [c_void_p, c_void_p, c_u64, c_int, c_int, c_float, c_void_p, c_void_p, c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_depth.h: fusion gated by sensor depth, product-only like
+# the tables above (no profile slot)
+DEPTH_U16, DEPTH_F32 = 0, 1                                         # SMESH_DEPTH_*
+DEPTH_IMG_LABELS_U8, DEPTH_IMG_LABELS_U16 = 3, 4                    # SMESH_DEPTH_IMG_* (class vectors: the SMESH_PROBS_* codes)
+
+
+class DepthGatePOD(ctypes.Structure):
+    """smesh_depth_gate_t (include/smesh_depth.h)."""
+    _fields_ = [("scale", c_float), ("abs_tol", c_float), ("rel_tol", c_float), ("max_depth", c_float), ("missing_keep", ctypes.c_int32)]
+
+
+DEPTH_SIGNATURES = {
+    "smesh_depth_weights": (c_int, [c_void_p, c_u64, c_u64, c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64,
+                                    P(DepthGatePOD), c_void_p, c_void_p, c_void_p, c_int]),
+    "smesh_fuse_views_depth": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, P(c_void_p), c_int, P(c_void_p),
+                                       P(c_void_p), c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(DepthGatePOD), c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -401,7 +419,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -11,6 +11,7 @@
 
 #include "common.hpp"
 #include "labels_scratch.hpp"
+#include "nearest_rule.hpp"
 #include "../../include/smesh_label_prep.h"
 
 #include <atomic>
@@ -36,13 +37,7 @@ struct PrepArgs {
   uint32_t map_lds;           // the map is copied into LDS as narrowed codes
 };
 
-// The rule, per axis.  n, N <= 65536: (2X + 1) n < 2^34 -- a 32-bit division where the product fits, which is every image below
-// 32768 pixels a side, else a 64-bit one.
-__device__ __forceinline__ uint32_t src_index(uint32_t X, uint32_t n, uint32_t N) {
-  const uint64_t num = (uint64_t)(2u * X + 1u) * n;
-  if ((num >> 32) == 0) return (uint32_t)num / (2u * N);
-  return (uint32_t)(num / (2ull * N));
-}
+// (the rule, per axis: src_index, nearest_rule.hpp)
 
 template <typename T>
 __device__ __forceinline__ bool in_range(T v, uint32_t limit) {

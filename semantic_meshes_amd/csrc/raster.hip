@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "meshlets.hpp"
 #include "half_scratch.hpp"
+#include "depth_gate.hpp"
 #include "../../include/smesh_meshlets.h"
 
 #include <algorithm>
@@ -1467,6 +1468,15 @@ __global__ __launch_bounds__(256) void k_tile_resolve_group(RasterGroup g) {
   });
 }
 
+// k_tile_resolve_group for views whose DEPTH planes are read as well (smesh_renderer_fuse_views_gated): every plane of every view is
+// written -- the index plane, and the depth plane behind it in the view's slot of 8 W H bytes.
+__global__ __launch_bounds__(256) void k_tile_resolve_group_depth(RasterGroup g) {
+  uint32_t v = 0;
+  while (v + 1 < g.n && blockIdx.x >= g.tile_end[v]) v++;   // block-uniform, n <= kMaxGroup
+  float* depth = reinterpret_cast<float*>(g.idx[v] + (uint64_t)g.view[v].W * g.view[v].H);
+  tile_resolve_block(g.view[v], g.idx[v], depth, blockIdx.x - (v ? g.tile_end[v - 1] : 0u), [] { return true; });
+}
+
 // Split the key image into the two output planes and re-arm the keys for the next render.
 __global__ void k_resolve(unsigned long long* __restrict__ keys, uint32_t* __restrict__ idx, float* __restrict__ depth,
                           uint32_t W, uint32_t H) {
@@ -1610,6 +1620,7 @@ struct smesh_renderer {
   unsigned long long* d_hash = nullptr;
   hipEvent_t hash_ev[kRecordSides] = {};   // recorded on the main stream behind the kernel that writes d_hash[s]
   Scratch match_stage;             // device copy of a host index image that is being looked up
+  DepthScratch gate;               // smesh_renderer_fuse_views_gated: weights planes, staged sensor images and counts of a group
   int last_render_side = 0;        // the side render_into() filled last (smesh_renderer_render_stats)
   bool raster_pending = false;     // work queued on the raster stream since the last synchronisation
   bool main_pending = false;       // renderer state (keys, scratch) used on the main stream since then
@@ -1991,9 +2002,9 @@ int prepare_group_slots(smesh_renderer* r, const smesh_camera_t* cams, int n, hi
 // `side_base`: where the records and index planes go (side[side_base + v], fused[side_base + v]) when that is not the view slots'
 // own set (held views: the rasteriser scratch of slots base .. base + n - 1 is free again after the launches, the records stay).
 int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipStream_t st, int base = 0, int side_base = -1,
-                      int idx_optional = 0) {
+                      int idx_optional = 0, bool with_depth = false) {
   if (side_base < 0) side_base = base;
-  if (!plane_optional_allowed(r)) idx_optional = 0;
+  if (!plane_optional_allowed(r) || with_depth) idx_optional = 0;
   DeviceCtx* ctx = r->ctx;
   ProjectGroup pg;
   RasterGroup rg;
@@ -2095,7 +2106,8 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   for (int v = 0; v < n; v++) huge_needed = huge_needed || !no_huge_possible(r, &cams[v]);
   if (huge_needed) hipLaunchKernelGGL(k_raster_huge_group, dim3(std::min<uint32_t>(tiles, 4u * (uint32_t)ctx->num_cus)), dim3(256), 0, st, rg);
   SMESH_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_tile_resolve_group, dim3(tiles), dim3(256), 0, st, rg);
+  if (with_depth) hipLaunchKernelGGL(k_tile_resolve_group_depth, dim3(tiles), dim3(256), 0, st, rg);   // (the depth planes: behind the index planes, in the slots)
+  else hipLaunchKernelGGL(k_tile_resolve_group, dim3(tiles), dim3(256), 0, st, rg);
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }
@@ -2597,6 +2609,7 @@ int smesh_renderer_destroy(smesh_renderer_t* r) {
   for (auto& im : r->images) { (void)dev_free(im.idx); (void)dev_free(im.depth); }
   r->own_idx.release();
   r->match_stage.release();
+  r->gate.release();
   if (r->d_hash) (void)dev_free(r->d_hash);
   for (int sd = 0; sd < kRecordSides; sd++)
     if (r->hash_ev[sd]) (void)hipEventDestroy(r->hash_ev[sd]);
@@ -3005,6 +3018,114 @@ bool smesh_renderer_sampled_native(smesh_renderer* r, smesh_aggregator* a) {
 int smesh_renderer_fuse_views_sampled(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* probs,
                                       const float* const* weights, const ViewInput& in) {
   return fuse_views_impl(r, a, cams, n, in, probs, weights, SMESH_MEM_DEVICE);
+}
+
+// ---- views gated by sensor depth (include/smesh_depth.h; the entry points are depth_weights.hip's) -------------------------------------
+// Per group of up to kMaxGroup views: the views rasterised into slots 0 .. m - 1 on the MAIN stream -- index plane, depth plane behind
+// it in the slot's 8 W H bytes, per-triangle records in side v; all planes written (idx_optional 0) --, by the grouped launches with
+// the depth-writing tile resolve where smesh_fuse_views would group them, else one view at a time as in that branch of
+// fuse_views_impl; `gate` called once for the group's weights planes; then the group fused from its slots: by the multi-view launches
+// of fuse_views_impl where it would take them (the same conditions, the same launches), else view by view through fuse_rendered.
+// fuse_views_impl and the group pipeline are not involved: nothing runs on the raster stream.  Locks and stream hand-over as
+// smesh_renderer_with_index_planes.
+int smesh_renderer_fuse_views_gated(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const ViewInput& in,
+                                    const void* const* images, const float* const* weights, const GateFn& gate) {
+  if (!r || !a || (n && (!cams || !images))) return fail(SMESH_ERR_INVALID, "NULL argument");
+  if (in.kind != ViewInput::F32 && in.kind != ViewInput::HALF && in.kind != ViewInput::LABELS) return fail(SMESH_ERR_INVALID, "bad image kind");
+  for (uint64_t i = 0; i < n; i++) {
+    SMESH_TRY(check_camera(&cams[i]));
+    if (!images[i]) return fail(SMESH_ERR_INVALID, "NULL image");
+  }
+  DeviceCtx* ctx = r->ctx;
+  if (smesh_aggregator_ctx(a) != ctx) return fail(SMESH_ERR_INVALID, "renderer and aggregator live on different devices");
+  static const bool pairs_off = env_int("SMESH_FUSE_PAIRS", 1) == 0;
+  for (uint64_t i = 0; i < n; i += (uint64_t)kMaxGroup) {
+    const int m = (int)std::min<uint64_t>((uint64_t)kMaxGroup, n - i);
+    std::lock_guard<std::mutex> g(r->mu);
+    std::lock_guard<std::mutex> g2(smesh_aggregator_mutex(a));
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    SMESH_HIP(hipSetDevice(ctx->device));
+    SMESH_TRY(smesh_aggregator_join_exchange(a));   // (rows still being exchanged on the exchange stream: smesh_allreduce_rows)
+    SMESH_TRY(main_after_raster(r));   // (a pipelined smesh_fuse_views call may still be rasterising into the view slots)
+    r->main_pending = true;            // the next pipelined group must wait for what this call does to the slots on the main stream
+    // does fuse_views_impl fuse such a group by the multi-view launches of the image kind's kernel?  (its `pairable`)
+    bool family = !pairs_off && r->F != 0;
+    switch (in.kind) {
+      case ViewInput::LABELS:
+        for (int v = 0; v < m; v++) family = family && labels_native(r, a, cams[i + v].width * cams[i + v].height);
+        break;
+      case ViewInput::HALF: family = family && half_native(r, a); break;
+      default: family = family && !r->texels && smesh_aggregator_can_fuse_triangles(a, r->F) && smesh_aggregator_can_fuse_pair(a); break;
+    }
+    size_t wbytes = 0;
+    for (int v = 0; v < m; v++) wbytes += round256(cams[i + v].width * cams[i + v].height * 4);
+    SMESH_TRY(r->gate.w.reserve(wbytes));
+    GatedView gv[kMaxGroup];
+    size_t woff = 0;
+    // two views and more share their rasteriser launches where smesh_fuse_views would group them (render_group_into, slots 0 .. m - 1,
+    // its tile resolve writing the depth planes too); else view by view
+    bool grouped = m >= 2 && r->F != 0 && r->V != 0;
+    for (int v = 0; v < m && grouped; v++) grouped = queues_fit_group(cams[i + v].width, cams[i + v].height);
+    if (grouped) SMESH_TRY(render_group_into(r, &cams[i], m, ctx->stream, 0, -1, /*idx_optional=*/0, /*with_depth=*/true));
+    for (int v = 0; v < m; v++) {
+      const smesh_camera_t* cam = &cams[i + (uint64_t)v];
+      const uint64_t N = cam->width * cam->height;
+      if (grouped) {
+        gv[v] = GatedView{reinterpret_cast<float*>(static_cast<uint32_t*>(r->fused[v].ptr) + N), weights ? weights[i + (uint64_t)v] : nullptr,
+                          reinterpret_cast<float*>(static_cast<char*>(r->gate.w.ptr) + woff), cam->width, cam->height};
+        woff += round256(N * 4);
+        continue;
+      }
+      if (v) SMESH_HIP(alloc_side(r, v));
+      if (r->fused[v].bytes < N * 8) {
+        // growing a slot frees the old buffer: nothing may still be reading it
+        SMESH_HIP(hipStreamSynchronize(ctx->raster_stream));
+        SMESH_HIP(hipStreamSynchronize(ctx->stream));
+        SMESH_TRY(r->fused[v].reserve(N * 8));
+      }
+      if (v < kRecordSides) { r->last_idx[v] = nullptr; r->rec_valid[v] = false; }   // the records of a render_device() on this side are being overwritten
+      uint32_t* d_idx = static_cast<uint32_t*>(r->fused[v].ptr);
+      float* d_depth = reinterpret_cast<float*>(d_idx + N);
+      SMESH_TRY(render_into(r, cam, d_idx, d_depth, ctx->stream, v, /*idx_optional=*/0));
+      gv[v] = GatedView{d_depth, weights ? weights[i + (uint64_t)v] : nullptr, reinterpret_cast<float*>(static_cast<char*>(r->gate.w.ptr) + woff), cam->width, cam->height};
+      woff += round256(N * 4);
+    }
+    SMESH_TRY(gate(ctx, r->gate, i, m, gv));
+    if (!family) {
+      for (int j = 0; j < m; j++) {
+        const uint64_t k = i + (uint64_t)j;
+        SMESH_TRY(fuse_rendered(r, a, j, static_cast<const uint32_t*>(r->fused[j].ptr), in.at(images[k]), gv[j].w_out, SMESH_MEM_DEVICE, cams[k].width,
+                                cams[k].height));
+      }
+    } else {
+      // (fuse_views_impl's loop over a group: the largest of 8 / 4 / 2 / 1 views per launch; nothing runs beside these launches, so
+      // they carry no LDS pad -- RenderedView::fine and ::beside stay unset)
+      ProfScope fuse_region(ctx, SMESH_PROF_FUSE_SCATTER);
+      static const int label_views_cap = std::max(1, env_int("SMESH_FUSE_VIEWS", 8));
+      const int max_nv = in.kind != ViewInput::F32 ? std::min(8, label_views_cap) : smesh_aggregator_max_fused_views(a);
+      for (int j = 0; j < m;) {
+        int nv = 1;
+        while (nv * 2 <= std::min(max_nv, m - j)) nv *= 2;
+        RenderedView rv[kMaxGroup];
+        for (int v = 0; v < nv; v++) {
+          const uint64_t k = i + (uint64_t)(j + v);
+          rv[v] = rendered_view(r->side[j + v], static_cast<const uint32_t*>(r->fused[j + v].ptr), in.at(images[k]), gv[j + v].w_out, cams[k].width,
+                                cams[k].height, true);
+          rv[v].no_big = no_big_possible(r, &cams[k]);
+        }
+        switch (in.kind) {
+          case ViewInput::HALF: SMESH_TRY(smesh_half_fuse_triangles(a, r->F, r->big_capacity, rv, nv, in.dtype_or_bytes)); break;
+          case ViewInput::LABELS: SMESH_TRY(smesh_labels_fuse_triangles(a, r->F, r->big_capacity, rv, nv, in.dtype_or_bytes)); break;
+          default: SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, rv, nv)); break;
+        }
+        j += nv;
+      }
+      if (in.kind == ViewInput::HALF) note_fuse_half(in.dtype_or_bytes);
+      else smesh_note_fuse(in.kind == ViewInput::LABELS ? "k_fuse_tri_labels" : smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
+    }
+    r->fused_seq += (uint64_t)m;
+  }
+  return SMESH_OK;
 }
 
 // ---- confusion matrices (include/smesh_eval.h; the entry points are eval.hip's) --------------------------------------------------------

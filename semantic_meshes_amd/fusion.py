@@ -249,6 +249,140 @@ def narrow_probs(array, dtype, device=0):
     return out
 
 
+class DepthGate:
+    """The gate of the depth-consistency weights (include/smesh_depth.h, where the rule is stated to the bit): a pixel keeps its
+    weight when |rendered depth - sensor depth| <= abs_tol + rel_tol * sensor depth, in float32, the sensor depth being
+    raw * `scale`.  `abs_tol` has no default: the caller states it.  `scale` None: 0.001 for integer sensor images (ScanNet's
+    millimetres), 1.0 for float ones.  `max_depth`: rendered depths beyond it get weight 0 (None: no limit).  `missing`: what a
+    pixel without a measurement (raw 0; a float sample that is not a positive finite number) gets -- "keep" its weight (no
+    evidence against it, the ungated behaviour) or "drop" it."""
+
+    def __init__(self, abs_tol, rel_tol=0.0, scale=None, max_depth=None, missing="keep"):
+        def number(v, name, allow_inf=False):
+            try:
+                f = float(np.float32(v))
+            except (TypeError, ValueError):
+                raise ValueError("DepthGate: %s must be a number, got %r" % (name, v))
+            if f != f or f < 0.0 or (not allow_inf and f == float("inf")):
+                raise ValueError("DepthGate: %s must be a finite number >= 0, got %r" % (name, v))
+            return f
+        self.abs_tol = number(abs_tol, "abs_tol")
+        self.rel_tol = number(rel_tol, "rel_tol")
+        self.scale = None if scale is None else number(scale, "scale")
+        if max_depth is None:
+            self.max_depth = None
+        else:
+            try:
+                self.max_depth = float(np.float32(max_depth))
+            except (TypeError, ValueError):
+                raise ValueError("DepthGate: max_depth must be a number or None, got %r" % (max_depth,))
+            if self.max_depth != self.max_depth:
+                raise ValueError("DepthGate: max_depth must not be NaN")
+        if missing not in ("keep", "drop"):
+            raise ValueError('DepthGate: missing must be "keep" or "drop", got %r' % (missing,))
+        self.missing = missing
+
+    def scale_for(self, dtype):
+        """The scale applied to a sensor image of `dtype`."""
+        if self.scale is not None:
+            return self.scale
+        return 0.001 if np.dtype(dtype).kind in "iu" else 1.0
+
+    def _pod(self, dtype):
+        return _lib.DepthGatePOD(self.scale_for(dtype), self.abs_tol, self.rel_tol,
+                                 float("inf") if self.max_depth is None else self.max_depth, 1 if self.missing == "keep" else 0)
+
+    def __repr__(self):
+        return "DepthGate(abs_tol=%r, rel_tol=%r, scale=%r, max_depth=%r, missing=%r)" % (self.abs_tol, self.rel_tol, self.scale, self.max_depth, self.missing)
+
+
+_DEPTH_CODES = {"uint16": _lib.DEPTH_U16, "float32": _lib.DEPTH_F32}
+
+
+def _describe_sensor(sensor, device, streams, what="sensor depth image"):
+    """(pointer, memkind, (w, h), dtype code, element strides, keep-alive, numpy dtype) of a sensor depth image: (w,h) uint16 or
+    float32, host numpy or device array, any non-negative strides -- a decoded (h,w) image goes over as its transposed view."""
+    sp, smem, sshape, sdt, sstr, keep = describe(sensor, 2, what, device, streams)
+    if sdt.name not in _DEPTH_CODES:
+        raise ValueError("%s dtype must be uint16 or float32, got %s" % (what, sdt))
+    if not (sshape[0] and sshape[1]):
+        raise ValueError("an empty %s %s cannot be sampled" % (what, tuple(sshape)))
+    return sp, smem, (int(sshape[0]), int(sshape[1])), _DEPTH_CODES[sdt.name], tuple(sstr), keep, sdt
+
+
+def _dense_plane(image, W, H, device, what, streams):
+    """`image` as a dense float32 (W,H) plane in device memory (a host array is copied there): (pointer, keep-alive)."""
+    from .device import to_device
+    ptr, mem, shape, dt, strides, keep = describe(image, 2, what, device, streams)
+    if mem == _lib.MEM_HOST:
+        if not isinstance(keep, np.ndarray) or dt.kind != "f":
+            raise ValueError("%s must be a float32 array, got %s" % (what, dt))
+        keep = to_device(np.ascontiguousarray(keep, dtype=np.float32), device)
+        ptr, shape, dt, strides = keep.ptr, keep.shape, keep.dtype, keep.strides
+    if tuple(shape) != (W, H) or dt != np.float32 or tuple(strides) != (H, 1):
+        raise ValueError("%s must be contiguous float32 (W,H) = %s, got %s %s" % (what, (W, H), dt, tuple(shape)))
+    return ptr, keep
+
+
+def depth_weights_device(depth, sensor_depth, gate, weights_image=None, device=0, return_counts=False):
+    """The depth-consistency weights of ONE view on the device (`smesh_depth_weights`, include/smesh_depth.h): `depth` the float32
+    (W,H) depth plane of `renderer.render(camera)` (or a host copy of one), `sensor_depth` the sensor's (w,h) uint16 / float32 image
+    (host numpy or device array, any non-negative strides; sampled nearest with half-pixel centres where its size differs),
+    `gate` a `DepthGate`, `weights_image` an optional float32 (W,H) image that is multiplied in.  Returns a float32 (W,H)
+    `DeviceArray` -- what `add(idx, probs, w)` takes as its weights image; with `return_counts=True` also the uint64
+    [visible, far, missing, inconsistent] counts, which makes the call wait."""
+    from .device import DeviceBuffer
+    if not isinstance(gate, DepthGate):
+        raise ValueError("depth_gate must be a fusion.DepthGate, got %r" % (gate,))
+    if isinstance(depth, DeviceArray):
+        device = depth.device
+    device = int(device)
+    shape = tuple(getattr(depth, "shape", None) or np.shape(depth))
+    if len(shape) != 2:
+        raise ValueError("depth plane must have rank 2, got shape %s" % (shape,))
+    W, H = int(shape[0]), int(shape[1])
+    streams = []
+    sp, smem, (w, h), scode, sstr, skeep, sdt = _describe_sensor(sensor_depth, device, streams)
+    dp, dkeep = _dense_plane(depth, W, H, device, "depth plane", streams)
+    wp, wkeep = (None, None) if weights_image is None else _dense_plane(weights_image, W, H, device, "weights image", streams)
+    out = DeviceBuffer(max(W * H * 4, 4), device).view((W, H), np.float32)
+    counts = np.zeros(4, np.uint64) if return_counts else None
+    pod = gate._pod(sdt)
+    _lib.check(_lib.lib().smesh_depth_weights(ctypes.c_void_p(dp), W, H, ctypes.c_void_p(sp), scode, _c64(sstr), smem, w, h, ctypes.byref(pod),
+                                              None if wp is None else ctypes.c_void_p(wp), ctypes.c_void_p(out.ptr),
+                                              None if counts is None else counts.ctypes.data_as(ctypes.c_void_p), device))
+    release_to(device, streams)
+    if any(k is not None and not isinstance(k, (DeviceArray, np.ndarray)) for k in (skeep, dkeep, wkeep)):
+        _lib.synchronize(device)      # (a foreign input may be freed by its owner as soon as we return)
+    out._gate_inputs = (dkeep, wkeep, skeep)      # (this library's own arrays are freed behind its streams)
+    return (out, counts) if return_counts else out
+
+
+def depth_weights(depth, sensor_depth, gate, weights_image=None, device=0, return_counts=False):
+    """`depth_weights_device` copied to the host: a numpy array (and the counts)."""
+    r = depth_weights_device(depth, sensor_depth, gate, weights_image, device, return_counts)
+    return (r[0].numpy(), r[1]) if return_counts else r.numpy()
+
+
+def _gate_keywords(sensor_depths, depth_gate, depth_stats, n, sample_in_kernel, what):
+    """The `sensor_depth(s)=`, `depth_gate=` and `depth_stats=` keywords of a fuse call of `n` views, checked: None for a call
+    without them, else the list of sensor images."""
+    if sensor_depths is None and depth_gate is None:
+        if depth_stats:
+            raise ValueError("%s: depth_stats=True needs sensor depths and a depth_gate" % what)
+        return None
+    if sensor_depths is None or depth_gate is None:
+        raise ValueError("%s: sensor depths and depth_gate go together, one was given without the other" % what)
+    if not isinstance(depth_gate, DepthGate):
+        raise ValueError("%s: depth_gate must be a fusion.DepthGate, got %r" % (what, depth_gate))
+    if sample_in_kernel:
+        raise ValueError("%s: sample_in_kernel=True cannot be combined with a depth gate" % what)
+    sensors = list(sensor_depths)
+    if len(sensors) != n:
+        raise ValueError("%s needs one sensor depth image per camera: %d for %d cameras" % (what, len(sensors), n))
+    return sensors
+
+
 GROUP_VIEWS = 8                                                     # views per deferred group (= the library's views per launch)
 DEFER_VIEWS = os.environ.get("SMESH_DEFER_VIEWS", "1") != "0"       # default of MeshAggregator.defer
 
@@ -508,6 +642,111 @@ class _MeshAggregator:
         release_to(self.device, streams)
         self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if pmem == _lib.MEM_DEVICE else None,
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
+
+    # ---- views gated by sensor depth (include/smesh_depth.h) ---------------------------------------------------------------------
+    def _gated_probs(self, image, W, H, mode, probs_dtype, streams, what):
+        """A class-vector image of a gated call as the library takes it: resampled where `resize=` asks for it, copied to the device
+        where it is a host array -- (pointer, SMESH_PROBS_* code, keep-alive) of a dense (W,H,C) device image."""
+        from .device import to_device
+        image = self._resampled(image, (W, H), mode, probs_dtype)
+        pp, pmem, pshape, pdt, pstr, k1 = describe(image, 3, what, self.device, streams)
+        code = probs_code(pdt, k1, probs_dtype, what)
+        if tuple(pshape) != (W, H, self.classes) or code is None:
+            raise ValueError("%s must be float32, float16 or bfloat16 (W,H,C) = %s" % (what, (W, H, self.classes)))
+        if pmem == _lib.MEM_HOST:
+            if not isinstance(k1, np.ndarray):
+                raise ValueError("%s: a host image of a gated fuse call must be a numpy array" % what)
+            dev = to_device(np.ascontiguousarray(k1), self.device)
+            dev.bfloat16 = code == _lib.PROBS_BF16
+            return dev.ptr, code, dev
+        if pstr != (H * self.classes, self.classes, 1):
+            raise ValueError("a gated fuse call needs contiguous (W,H,C) probs images on the device")
+        return pp, code, k1
+
+    def _gated_labels(self, image, W, H, resize, m, streams, what):
+        """A label image of a gated call as the library takes it: (pointer, SMESH_DEPTH_IMG_LABELS_* code, keep-alive) of a dense
+        (W,H) uint8 / uint16 device plane -- this library's own dense plane as it is, anything else through `prepare_labels_device`
+        (sampled, mapped, narrowed)."""
+        if (m is None and type(image) is DeviceArray and image.device == self.device and image.shape == (W, H) and image.strides == (H, 1)
+                and (image.dtype == np.uint16 or (image.dtype == np.uint8 and self.classes <= 255))):
+            plane = image
+        else:
+            table = m if isinstance(m, ColorTable) else None
+            plane = prepare_labels_device(image, self.classes, (W, H), resize, None if table is not None else m, self.device, table)
+        return plane.ptr, (_lib.DEPTH_IMG_LABELS_U8 if plane.dtype == np.uint8 else _lib.DEPTH_IMG_LABELS_U16), plane
+
+    def _fuse_views_gated(self, renderer, cameras, prepare, weights_images, sensors, gate, depth_stats, what):
+        """The gated form of fuse_views / fuse_views_labels: the batch is worked through in chunks of eight views -- the views of a
+        fusion launch; `prepare(i, streams)` gives view i's dense device image as (pointer, image kind, keep-alive), host weights are
+        copied to the device, and a chunk whose sensor images share size, dtype, strides and memory (and whose images share their kind)
+        is ONE `smesh_fuse_views_depth` call; a mixed chunk goes view by view.  Returns the uint64 [n, 4] counts with `depth_stats`."""
+        n = len(cameras)
+        counts = np.zeros((n, 4), np.uint64) if depth_stats else None
+        sensor_streams = []
+        # (every sensor image is checked before anything is copied or fused)
+        sdesc = [_describe_sensor(sensors[i], self.device, sensor_streams, "sensor depth image %d" % i) for i in range(n)]
+        rh = renderer._h
+        for lo in range(0, n, GROUP_VIEWS):
+            hi = min(lo + GROUP_VIEWS, n)
+            streams, views = [], []
+            for i in range(lo, hi):
+                W, H = cameras[i].resolution
+                d_img = prepare(i, streams)
+                d_s = sdesc[i]
+                wk = (None, None)
+                if weights_images is not None and weights_images[i] is not None:
+                    wk = _dense_plane(weights_images[i], W, H, self.device, "weights image %d" % i, streams)
+                views.append((d_img, d_s, wk))
+            runs, start = [], 0
+            for j in range(1, len(views) + 1):
+                if j == len(views) or views[j][0][1] != views[start][0][1] or views[j][1][1:5] != views[start][1][1:5]:
+                    runs.append((start, j))
+                    start = j
+            if len(runs) > 1:      # a mixed chunk: view by view
+                runs = [(j, j + 1) for j in range(len(views))]
+            for a, b in runs:
+                k = b - a
+                first_img, first_s = views[a][0], views[a][1]
+                pods = (_lib.CameraPOD * k)(*[cameras[lo + j]._pod for j in range(a, b)])
+                iptr = (ctypes.c_void_p * k)(*[views[j][0][0] for j in range(a, b)])
+                sptr = (ctypes.c_void_p * k)(*[views[j][1][0] for j in range(a, b)])
+                wptr = None
+                if any(views[j][2][0] is not None for j in range(a, b)):
+                    wptr = (ctypes.c_void_p * k)(*[views[j][2][0] for j in range(a, b)])
+                pod = gate._pod(first_s[6])
+                cptr = None if counts is None else ctypes.c_void_p(counts.ctypes.data + (lo + a) * 32)
+                _lib.check(_lib.lib().smesh_fuse_views_depth(rh, self._h, pods, k, iptr, first_img[1], wptr, sptr, first_s[3], _c64(first_s[4]),
+                                                             first_s[1], first_s[2][0], first_s[2][1], ctypes.byref(pod), cptr))
+            release_to(self.device, streams)
+            self._hold([v[0][2] for v in views] + [v[1][5] for v in views if v[1][1] == _lib.MEM_DEVICE] + [v[2][1] for v in views])
+        release_to(self.device, sensor_streams)
+        return counts
+
+    def _fuse_views_probs_gated(self, renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, gate, depth_stats, what):
+        from .resize import resize_mode
+        mode = resize_mode(resize)
+        cameras, probs_images = list(cameras), list(probs_images)
+        wts = None if weights_images is None else list(weights_images)
+        if len(probs_images) != len(cameras) or (wts is not None and len(wts) != len(cameras)):
+            raise ValueError("%s needs one probs image (and one weights image or None) per camera" % what)
+
+        def prepare(i, streams):
+            W, H = cameras[i].resolution
+            return self._gated_probs(probs_images[i], W, H, mode, probs_dtype, streams, "probs image %d" % i)
+        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what)
+
+    def _fuse_views_labels_gated(self, renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors, gate, depth_stats, what):
+        label_resize_mode(resize)
+        cameras, label_images = list(cameras), list(label_images)
+        wts = None if weights_images is None else list(weights_images)
+        if len(label_images) != len(cameras) or (wts is not None and len(wts) != len(cameras)):
+            raise ValueError("%s needs one label image (and one weights image or None) per camera" % what)
+        m = _palette_or_map(palette, label_map, label_images, self.classes, self.device) if cameras else None
+
+        def prepare(i, streams):
+            W, H = cameras[i].resolution
+            return self._gated_labels(label_images[i], W, H, resize, m, streams, "label image %d" % i)
+        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what)
 
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
@@ -792,9 +1031,15 @@ class _MeshAggregator:
         self._hold([k0 if imem == _lib.MEM_DEVICE else None, k1 if lmem == _lib.MEM_DEVICE else None,
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
 
-    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None, palette=None):
+    def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None, palette=None,
+                         sensor_depth=None, depth_gate=None, depth_stats=False):
         """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`,
-        `label_map` and `palette`)."""
+        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate` and `depth_stats`)."""
+        sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, False, "fuse_view_labels")
+        if sensors is not None:
+            stats = self._fuse_views_labels_gated(renderer, [camera], [label_image], None if weights_image is None else [weights_image],
+                                                  resize, label_map, palette, sensors, depth_gate, depth_stats, "fuse_view_labels")
+            return None if stats is None else stats[0]
         mode, m = label_resize_mode(resize), _palette_or_map(palette, label_map, [label_image], self.classes, self.device)
         W, H = camera.resolution
         if m is not None or (mode is not None and self._shape_of(label_image) != (W, H)):
@@ -861,14 +1106,21 @@ class _MeshAggregator:
         if first[1] == _lib.MEM_DEVICE:
             self._hold([d[5] for d, _ in desc] + [dw[1] for _, dw in desc])
 
-    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None, palette=None):
+    def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None, palette=None,
+                          sensor_depths=None, depth_gate=None, depth_stats=False):
         """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
         views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
         and memory go to the library as one batch; a mixed list is fused view by view.  `resize="nearest"` / `label_map` (see
         add_labels): the fast form for masks at the network's resolution or in the dataset's ids -- images that also share their
         size are prepared and fused by the library in batches of eight.  `palette` (see add_labels): colour images; a `ColorRemap`
         is first updated with all the call's images, in their order -- their distinct colours are found on the device, eight images
-        per synchronisation -- and must then hold no more colours than the aggregator has classes."""
+        per synchronisation -- and must then hold no more colours than the aggregator has classes.
+        `sensor_depths=`, `depth_gate=`, `depth_stats=`: see fuse_views -- the masks are prepared in chunks of eight, then gated."""
+        cameras = list(cameras)
+        sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), False, "fuse_views_labels")
+        if sensors is not None:
+            return self._fuse_views_labels_gated(renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors,
+                                                 depth_gate, depth_stats, "fuse_views_labels")
         mode, m = label_resize_mode(resize), check_label_map(label_map)
         cameras, label_images = list(cameras), list(label_images)
         n = len(cameras)
@@ -1090,12 +1342,19 @@ class _MeshAggregator:
         """`ModelAggregator::renderer()` (Mesh.h:124-129): snapshot of the fused annotations for image gathers."""
         return ModelRenderer(self)
 
-    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False):
+    def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False,
+                  sensor_depth=None, depth_gate=None, depth_stats=False):
         """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
         float32, float16 or bfloat16 (see add()); with `resize="bilinear"` any (w,h,C) image add() takes, resampled to the camera's
         resolution on the device first -- or, with `sample_in_kernel=True`, sampled inside the fusion kernel (see add(); one library
-        call per view, after the views already deferred)."""
+        call per view, after the views already deferred).  `sensor_depth=`, `depth_gate=`, `depth_stats=`: the view is gated by its
+        sensor depth (see fuse_views); the views already deferred are handed over first, then this view is a call of its own."""
         from .resize import resize_mode
+        sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, sample_in_kernel, "fuse_view")
+        if sensors is not None:
+            stats = self._fuse_views_probs_gated(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
+                                                 probs_dtype, resize, sensors, depth_gate, depth_stats, "fuse_view")
+            return None if stats is None else stats[0]
         smode = self._sampling_mode(resize, sample_in_kernel, "fuse_view")
         if smode is not None:
             return self._fuse_views_sampled(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
@@ -1169,7 +1428,8 @@ class _MeshAggregator:
         return (pods, n, pptr, (None if weights_images is None else wptr), (mem if mem is not None else _lib.MEM_HOST), keep, streams,
                 _lib.PROBS_F32 if code is None else code)
 
-    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False):
+    def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False,
+                   sensor_depths=None, depth_gate=None, depth_stats=False):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
         accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
@@ -1178,8 +1438,19 @@ class _MeshAggregator:
         chunks of eight views -- the views of a fusion launch -- so at most eight resampled images are alive at once.  Same views in
         the same order: the same sums.  `sample_in_kernel=True` (with `resize="bilinear"`): the small images go to the library as
         they are, as one batch; the fusion kernel samples them for the visible pixels (include/smesh_sampled.h) -- the same sums,
-        no (W,H,C) image anywhere.  This is the fast form of the keyword."""
+        no (W,H,C) image anywhere.  This is the fast form of the keyword.
+        `sensor_depths=` (one (w,h) uint16 / float32 sensor depth image per camera, host or device, a decoded (h,w) image as its
+        transposed view) together with `depth_gate=` (a `DepthGate`): every pixel's contribution is gated by the consistency of the
+        rendered depth with the sensor's (include/smesh_depth.h) -- the weights are computed on the device between the rasteriser
+        and the fusion launch, eight views per launch, multiplied into `weights_images` where given.  The batch is worked through
+        in chunks of eight views; host images are copied to the device per chunk.  `depth_stats=True` returns the uint64 [n, 4]
+        counts [visible, far, missing, inconsistent] per view and waits for them.  Not with `sample_in_kernel=True`."""
         from .resize import image_size, resize_mode
+        cameras = list(cameras)
+        sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), sample_in_kernel, "fuse_views")
+        if sensors is not None:
+            return self._fuse_views_probs_gated(renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, depth_gate,
+                                                depth_stats, "fuse_views")
         mode = resize_mode(resize)
         smode = self._sampling_mode(resize, sample_in_kernel, "fuse_views")
         if smode is not None:
