@@ -292,6 +292,21 @@ DEPTH_SIGNATURES = {
                                        P(c_void_p), c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(DepthGatePOD), c_void_p]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_face_graph.h: the faces across every face's edges and the
+# propagation of fused rows over them, product-only like the tables above (no profile slot; the output modes are SMESH_VTX_*)
+FG_SMOOTH, FG_FILL = 0, 1                                           # SMESH_FG_*
+FG_MAX_POWER = 16                                                   # SMESH_FG_MAX_POWER
+_FG_TAIL = [c_void_p, c_int, c_int, c_u32, c_float, c_float, c_int, c_float, c_void_p, c_void_p, P(c_u64), c_int]
+FACE_GRAPH_SIGNATURES = {
+    "smesh_face_graph_create": (c_int, [c_void_p, c_u64, c_u64, c_int, P(c_void_p)]),
+    "smesh_face_graph_destroy": (c_int, [c_void_p]),
+    "smesh_face_graph_size": (c_int, [c_void_p, P(c_u64), P(c_u64), P(c_u64)]),
+    "smesh_face_graph_adjacency": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "smesh_face_graph_propagate": (c_int, [c_void_p, c_void_p, c_int, c_u32] + _FG_TAIL),
+    "smesh_aggregator_face_propagate": (c_int, [c_void_p, c_void_p] + _FG_TAIL),
+    "smesh_face_graph_normal_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_u32, c_int, c_void_p, c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -419,7 +434,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -305,6 +305,13 @@ int smesh_renderer_texel_tables(const smesh_renderer* r, smesh::DeviceCtx** ctx,
 // (vertices.hip: k_vertex_gather, one row per item); `out_labels`: int32[n] in `out_memkind`.  Context locked, device current.
 int smesh_rows_labels(smesh::DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, float dont_care_threshold, int32_t* out_labels,
                       int out_memkind);
+// What the face graph (face_graph.hip) needs from vertices.hip.  smesh_rows_finish: every row of a dense float32 [n, C] device array
+// treated as a vertex with that one row is (mode, threshold; rows and/or labels, in `out_memkind`) -- smesh_rows_labels with rows.
+// smesh_vertex_map_tables: the device CSR of a vertex map (uint32 offsets[V + 1], list[nnz]).  Context locked, device current.
+struct smesh_vertex_map;
+int smesh_rows_finish(smesh::DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, int mode, float dont_care_threshold,
+                      float* out_rows, int32_t* out_labels, int out_memkind);
+int smesh_vertex_map_tables(const smesh_vertex_map* m, smesh::DeviceCtx** ctx, const uint32_t** offsets, const uint32_t** list);
 // What the confusion matrices (eval.hip) need from a renderer: `n` views (at most eight) rasterised on the context's main stream with
 // FULLY WRITTEN index planes, and `use(view, idx, W, H)` called for each with the renderer and its context locked -- what `use`
 // queues on the main stream reads the plane before anything overwrites it.  `P` must be the renderer's primitive count.

@@ -401,6 +401,28 @@ int smesh_rows_labels(DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t 
   return gather_device_rows(ctx, g, nullptr, out_labels, out_memkind);
 }
 
+// What face_graph.hip needs: the same gather with rows and/or labels out, and the device CSR of a map.
+int smesh_rows_finish(DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, int mode, float dont_care_threshold, float* out_rows,
+                      int32_t* out_labels, int out_memkind) {
+  SMESH_TRY(check_gather_args(C, mode, out_rows, out_labels, SMESH_MEM_DEVICE, out_memkind));
+  if (n >= 0xFFFFFFFFull) return fail(SMESH_ERR_INVALID, "rows: the row count must stay below 2^32");
+  GatherArgs g = {};
+  g.rows = d_rows;
+  g.n = n;
+  g.C = C;
+  g.mode = mode;
+  g.threshold = dont_care_threshold;
+  return gather_device_rows(ctx, g, out_rows, out_labels, out_memkind);
+}
+
+int smesh_vertex_map_tables(const smesh_vertex_map* m, DeviceCtx** ctx, const uint32_t** offsets, const uint32_t** list) {
+  if (!m) return fail(SMESH_ERR_INVALID, "NULL vertex map");
+  *ctx = m->ctx;
+  *offsets = m->offsets;
+  *list = m->list;
+  return SMESH_OK;
+}
+
 extern "C" {
 
 int smesh_vertex_map_create(const int32_t* faces, uint64_t F, uint64_t V, int device, smesh_vertex_map_t** out) {

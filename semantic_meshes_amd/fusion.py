@@ -1883,6 +1883,219 @@ class PointTransfer:
         return self._run(source, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, True)[1]
 
 
+class FaceGraph:
+    """Fused rows propagated along the surface, on the device (include/smesh_face_graph.h): for every face the faces across its
+    edges, built once on `device`, and T averaging iterations over them.  The reference has no such step.
+
+    `faces`: int[F,3], `num_vertices`: V.  A `source` is what it is for `VertexTransfer`: a MeshAggregator over the F faces (its
+    `get()` never leaves the device), a float32 [F,C] numpy array, or a dense float32 [F,C] device array.  In every iteration a face
+    takes the mean m of its INFORMED neighbours (those whose row total is > 0; weighted by `weights`, one float32 per entry of
+    `adjacency()`, e.g. `normal_weights()`).  `smooth*`: x <- (1 - alpha) x0 + alpha m.  `fill*`: a face whose own total reaches
+    `observed_threshold` keeps its row, every other face takes m, so the front advances one ring of faces per iteration.  The
+    result is finished as `VertexTransfer` finishes a vertex row: `*_sums` the rows as they are, the plain form divided by their
+    total (all zero below `dont_care_threshold`), `*_labels` their argmax (-1 where don't care); `*_device` leaves it in HBM.
+    `return_unreached=True`: `(result, number of faces whose final total is not > 0)`."""
+
+    def __init__(self, faces, num_vertices, device=0):
+        f = np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+            raise ValueError("faces must be an integer array [F,3], got %s %s" % (f.dtype, f.shape))
+        self.num_vertices, self.num_faces, self.device = int(num_vertices), len(f), int(device)
+        if self.num_vertices < 0:
+            raise ValueError("num_vertices must be >= 0")
+        if f.size and (f.min() < 0 or f.max() >= self.num_vertices):      # (the library checks again, on the device)
+            raise ValueError("face indices out of range [0, %d)" % self.num_vertices)
+        self._faces = np.ascontiguousarray(f, dtype=np.int32)              # (normal_weights reads them again)
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().smesh_face_graph_create(self._faces.ctypes.data_as(ctypes.c_void_p), self.num_faces, self.num_vertices,
+                                                     self.device, ctypes.byref(h)))
+        self._h = h
+        nnz = ctypes.c_uint64()
+        _lib.check(_lib.lib().smesh_face_graph_size(self._h, None, None, ctypes.byref(nnz)))
+        self.num_entries = int(nnz.value)
+
+    @classmethod
+    def from_mesh(cls, mesh, device=0):
+        return cls(mesh.faces, len(mesh.vertices), device)
+
+    @classmethod
+    def from_renderer(cls, texel_renderer, num_vertices):
+        """For a texel renderer: its layout's faces, the order `face_annotations()` returns its rows in."""
+        if not hasattr(texel_renderer, "texel_layout"):
+            raise ValueError("from_renderer needs a texel renderer (render.texels)")
+        return cls(texel_renderer.texel_layout()[0], num_vertices, texel_renderer.device)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            try:
+                _lib.lib().smesh_face_graph_destroy(h)
+            except Exception:
+                pass
+
+    def adjacency(self):
+        """The graph as `(offsets uint64[F+1], neighbours uint32[nnz])`: the faces across the edges of face f, edge slot after edge
+        slot and ascending within a slot, are `neighbours[offsets[f]:offsets[f+1]]`."""
+        offsets, nbr = np.empty(self.num_faces + 1, np.uint64), np.empty(self.num_entries, np.uint32)
+        _lib.check(_lib.lib().smesh_face_graph_adjacency(self._h, offsets.ctypes.data_as(ctypes.c_void_p), nbr.ctypes.data_as(ctypes.c_void_p)))
+        return offsets, nbr
+
+    # ---- normal-agreement weights ------------------------------------------------------------------------------------------------
+    def _normal_weights(self, vertices, power, two_sided, on_device):
+        if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 1 <= int(power) <= _lib.FG_MAX_POWER:
+            raise ValueError("power must be an int in 1 .. %d, got %r" % (_lib.FG_MAX_POWER, power))
+        streams = []
+        ptr, mem, N, keep = _dense_points(vertices, self.device, streams)
+        if N != self.num_vertices:
+            raise ValueError("vertices must be float32[%d,3], got %d rows" % (self.num_vertices, N))
+        n = self.num_entries
+        if on_device:
+            from .device import DeviceBuffer
+            out = DeviceBuffer(max(n * 4, 4), self.device).view((n,), np.float32)
+            pout, omem = ctypes.c_void_p(out.ptr), _lib.MEM_DEVICE
+        else:
+            out = np.empty(n, np.float32)
+            pout, omem = out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST
+        _lib.check(_lib.lib().smesh_face_graph_normal_weights(self._h, self._faces.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), mem,
+                                                             int(power), 1 if two_sided else 0, pout, omem))
+        release_to(self.device, streams)
+        return out
+
+    def normal_weights(self, vertices, power=4, two_sided=True):
+        """One float32 weight per entry of `adjacency()`, a `DeviceArray`: the cosine between the two faces' normals (its absolute
+        value with `two_sided`), clamped to [0, 1] and raised to `power` -- 1 across a flat edge, 0 across a right angle or next to
+        a face without area.  `vertices`: float32 [V,3], numpy or a dense device array."""
+        return self._normal_weights(vertices, power, two_sided, True)
+
+    def normal_weights_host(self, vertices, power=4, two_sided=True):
+        """`normal_weights()` as a numpy array."""
+        return self._normal_weights(vertices, power, two_sided, False)
+
+    # ---- propagation -------------------------------------------------------------------------------------------------------------
+    def _run(self, source, fg_mode, iterations, alpha, observed_threshold, weights, out_mode, threshold, want_rows, want_labels, on_device,
+             return_unreached):
+        from .device import DeviceBuffer
+        F = self.num_faces
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or iterations < 0 or iterations > 0xFFFFFFFF:
+            raise ValueError("iterations must be a non-negative int, got %r" % (iterations,))
+        if not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError("alpha must lie in [0, 1], got %r" % (alpha,))
+        streams = []
+        pw, wmem, wkeep = None, _lib.MEM_HOST, None
+        if weights is not None:
+            if isinstance(weights, np.ndarray) and weights.dtype != np.float32:
+                raise ValueError("weights must be float32, got %s" % weights.dtype)
+            _same_device(weights, self.device, "weights")
+            wptr, wmem, wshape, wdt, wstrides, wkeep = describe(weights, 1, "weights", self.device, streams)
+            if wdt != np.float32:
+                raise ValueError("weights must be float32, got %s" % wdt)
+            if wshape[0] != self.num_entries:
+                raise ValueError("weights must have one element per entry of the graph (%d), got %d" % (self.num_entries, wshape[0]))
+            if wshape[0] > 1 and wstrides[0] != 1:
+                if wmem != _lib.MEM_HOST:
+                    raise ValueError("weights must be dense")
+                wkeep = np.ascontiguousarray(wkeep)
+                wptr = wkeep.ctypes.data
+            pw = ctypes.c_void_p(wptr)
+        if isinstance(source, _MeshAggregator):
+            if source.primitives != F:
+                raise ValueError("the aggregator has %d primitives, the mesh %d faces" % (source.primitives, F))
+            if source.device != self.device:
+                raise ValueError("aggregator and FaceGraph live on different devices")
+            C = source.classes
+        else:
+            _same_device(source, self.device, "face rows")
+            ptr, mem, C, keep = _dense_rows(source, F, "face rows", self.device, streams)
+        rows = labels = None
+        if on_device:
+            if want_rows:
+                rows = DeviceBuffer(max(F * C * 4, 4), self.device).view((F, C), np.float32)
+            if want_labels:
+                labels = DeviceBuffer(max(F * 4, 4), self.device).view((F,), np.int32)
+            prow, plab, omem = (None if rows is None else ctypes.c_void_p(rows.ptr), None if labels is None else ctypes.c_void_p(labels.ptr),
+                                _lib.MEM_DEVICE)
+        else:
+            if want_rows:
+                rows = result_empty((F, C), np.float32)
+            if want_labels:
+                labels = np.empty(F, np.int32)
+            prow, plab, omem = (None if rows is None else rows.ctypes.data_as(ctypes.c_void_p),
+                                None if labels is None else labels.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST)
+        unreached = ctypes.c_uint64(0)
+        tail = (pw, wmem, fg_mode, int(iterations), float(alpha), float(observed_threshold), out_mode, float(threshold), prow, plab,
+                ctypes.byref(unreached) if return_unreached else None, omem)
+        if isinstance(source, _MeshAggregator):
+            # (`_h`: the aggregator's deferred views are handed to the library first, as get() does)
+            _lib.check(_lib.lib().smesh_aggregator_face_propagate(source._h, self._h, *tail))
+            source._drain()
+        else:
+            _lib.check(_lib.lib().smesh_face_graph_propagate(self._h, ctypes.c_void_p(ptr), mem, C, *tail))
+        release_to(self.device, streams)
+        result = rows if want_rows else labels
+        return (result, int(unreached.value)) if return_unreached else result
+
+    def _smooth(self, source, iterations, alpha, weights, out_mode, threshold, want_labels, on_device, return_unreached):
+        return self._run(source, _lib.FG_SMOOTH, iterations, alpha, 0.0, weights, out_mode, threshold, not want_labels, want_labels,
+                         on_device, return_unreached)
+
+    def _fill(self, source, iterations, observed_threshold, weights, out_mode, threshold, want_labels, on_device, return_unreached):
+        return self._run(source, _lib.FG_FILL, iterations, 0.0, observed_threshold, weights, out_mode, threshold, not want_labels,
+                         want_labels, on_device, return_unreached)
+
+    def smooth(self, source, iterations=10, alpha=0.5, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """float32 [F,C]: the smoothed rows renormalised; all-zero rows where their total is below `dont_care_threshold`."""
+        return self._smooth(source, iterations, alpha, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, False, return_unreached)
+
+    def smooth_sums(self, source, iterations=10, alpha=0.5, weights=None, return_unreached=False):
+        """float32 [F,C]: the smoothed rows as they are."""
+        return self._smooth(source, iterations, alpha, weights, _lib.VTX_SUMS, 0.0, False, False, return_unreached)
+
+    def smooth_labels(self, source, iterations=10, alpha=0.5, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """int32 [F]: the class with the largest smoothed value (the lowest one among equals), -1 where don't care."""
+        return self._smooth(source, iterations, alpha, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, return_unreached)
+
+    def smooth_device(self, source, iterations=10, alpha=0.5, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """`smooth()` left in HBM: a `DeviceArray` in a fresh allocation owned by the returned object."""
+        return self._smooth(source, iterations, alpha, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, return_unreached)
+
+    def smooth_sums_device(self, source, iterations=10, alpha=0.5, weights=None, return_unreached=False):
+        """`smooth_sums()` left in HBM."""
+        return self._smooth(source, iterations, alpha, weights, _lib.VTX_SUMS, 0.0, False, True, return_unreached)
+
+    def smooth_labels_device(self, source, iterations=10, alpha=0.5, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """`smooth_labels()` left in HBM: a label table for `LabelRenderer`, `ConfusionMatrix.add_views` and `PointTransfer`."""
+        return self._smooth(source, iterations, alpha, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, True, return_unreached)
+
+    def fill(self, source, iterations=32, observed_threshold=0.9, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """float32 [F,C]: observed faces as they were, the others filled from them, renormalised; all-zero rows where the total is
+        below `dont_care_threshold` (a face the front has not reached)."""
+        return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, False,
+                          return_unreached)
+
+    def fill_sums(self, source, iterations=32, observed_threshold=0.9, weights=None, return_unreached=False):
+        """float32 [F,C]: the filled rows as they are."""
+        return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_SUMS, 0.0, False, False, return_unreached)
+
+    def fill_labels(self, source, iterations=32, observed_threshold=0.9, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """int32 [F]: the class with the largest filled value (the lowest one among equals), -1 where don't care."""
+        return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False,
+                          return_unreached)
+
+    def fill_device(self, source, iterations=32, observed_threshold=0.9, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """`fill()` left in HBM."""
+        return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True,
+                          return_unreached)
+
+    def fill_sums_device(self, source, iterations=32, observed_threshold=0.9, weights=None, return_unreached=False):
+        """`fill_sums()` left in HBM."""
+        return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_SUMS, 0.0, False, True, return_unreached)
+
+    def fill_labels_device(self, source, iterations=32, observed_threshold=0.9, weights=None, dont_care_threshold=0.9, return_unreached=False):
+        """`fill_labels()` left in HBM."""
+        return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, True,
+                          return_unreached)
+
+
 class MeshAggregatorSum(_MeshAggregator):
     pass
 
