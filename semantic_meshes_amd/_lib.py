@@ -307,6 +307,19 @@ FACE_GRAPH_SIGNATURES = {
     "smesh_face_graph_normal_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_u32, c_int, c_void_p, c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_face_segments.h: the connected components of a labelled
+# mesh over the face graph and the removal of the small ones, product-only like the tables above (no profile slot)
+FACE_SEGMENTS_SIGNATURES = {
+    "smesh_face_segments_create": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, P(c_void_p)]),
+    "smesh_aggregator_face_segments": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_float, P(c_void_p)]),
+    "smesh_face_segments_destroy": (c_int, [c_void_p]),
+    "smesh_face_segments_size": (c_int, [c_void_p, P(c_u64), P(c_u64), P(c_u64)]),
+    "smesh_face_segments_get": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "smesh_face_segments_despeckle_labels": (c_int, [c_void_p, c_u32, c_void_p, c_int, P(c_u64), P(c_u64)]),
+    "smesh_face_segments_despeckle_rows": (c_int, [c_void_p, c_u32, c_void_p, c_int, c_u32, c_void_p, c_int]),
+    "smesh_aggregator_face_segments_despeckle": (c_int, [c_void_p, c_void_p, c_u32, c_void_p, c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -434,7 +447,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -312,6 +312,11 @@ struct smesh_vertex_map;
 int smesh_rows_finish(smesh::DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, int mode, float dont_care_threshold,
                       float* out_rows, int32_t* out_labels, int out_memkind);
 int smesh_vertex_map_tables(const smesh_vertex_map* m, smesh::DeviceCtx** ctx, const uint32_t** offsets, const uint32_t** list);
+// What the segments (face_segments.hip) need from face_graph.hip: the device CSR of a face graph (uint32 offsets[F + 1],
+// neighbours[nnz]) and the context it lives in.
+struct smesh_face_graph;
+int smesh_face_graph_tables(const smesh_face_graph* graph, smesh::DeviceCtx** ctx, const uint32_t** offsets, const uint32_t** neighbours,
+                            uint64_t* F, uint64_t* nnz);
 // What the confusion matrices (eval.hip) need from a renderer: `n` views (at most eight) rasterised on the context's main stream with
 // FULLY WRITTEN index planes, and `use(view, idx, W, H)` called for each with the renderer and its context locked -- what `use`
 // queues on the main stream reads the plane before anything overwrites it.  `P` must be the renderer's primitive count.

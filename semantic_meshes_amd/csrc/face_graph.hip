@@ -495,6 +495,17 @@ int propagate_device_rows(const smesh_face_graph* gr, DeviceCtx* ctx, const floa
 
 }  // namespace
 
+int smesh_face_graph_tables(const smesh_face_graph* gr, DeviceCtx** ctx, const uint32_t** offsets, const uint32_t** neighbours, uint64_t* F,
+                            uint64_t* nnz) {
+  if (!gr) return fail(SMESH_ERR_INVALID, "NULL face graph");
+  *ctx = gr->ctx;
+  *offsets = gr->offsets;
+  *neighbours = gr->neighbours;
+  *F = gr->F;
+  *nnz = gr->nnz;
+  return SMESH_OK;
+}
+
 extern "C" {
 
 int smesh_face_graph_create(const int32_t* faces, uint64_t F, uint64_t V, int device, smesh_face_graph_t** out) {

@@ -1971,6 +1971,25 @@ class FaceGraph:
         """`normal_weights()` as a numpy array."""
         return self._normal_weights(vertices, power, two_sided, False)
 
+    def _entry_weights(self, weights, streams):
+        """(pointer or None, memkind, keep-alive) of per-entry weights: float32, `num_entries` elements, dense, on this device."""
+        if weights is None:
+            return None, _lib.MEM_HOST, None
+        if isinstance(weights, np.ndarray) and weights.dtype != np.float32:
+            raise ValueError("weights must be float32, got %s" % weights.dtype)
+        _same_device(weights, self.device, "weights")
+        wptr, wmem, wshape, wdt, wstrides, wkeep = describe(weights, 1, "weights", self.device, streams)
+        if wdt != np.float32:
+            raise ValueError("weights must be float32, got %s" % wdt)
+        if wshape[0] != self.num_entries:
+            raise ValueError("weights must have one element per entry of the graph (%d), got %d" % (self.num_entries, wshape[0]))
+        if wshape[0] > 1 and wstrides[0] != 1:
+            if wmem != _lib.MEM_HOST:
+                raise ValueError("weights must be dense")
+            wkeep = np.ascontiguousarray(wkeep)
+            wptr = wkeep.ctypes.data
+        return ctypes.c_void_p(wptr), wmem, wkeep
+
     # ---- propagation -------------------------------------------------------------------------------------------------------------
     def _run(self, source, fg_mode, iterations, alpha, observed_threshold, weights, out_mode, threshold, want_rows, want_labels, on_device,
              return_unreached):
@@ -1981,22 +2000,7 @@ class FaceGraph:
         if not 0.0 <= float(alpha) <= 1.0:
             raise ValueError("alpha must lie in [0, 1], got %r" % (alpha,))
         streams = []
-        pw, wmem, wkeep = None, _lib.MEM_HOST, None
-        if weights is not None:
-            if isinstance(weights, np.ndarray) and weights.dtype != np.float32:
-                raise ValueError("weights must be float32, got %s" % weights.dtype)
-            _same_device(weights, self.device, "weights")
-            wptr, wmem, wshape, wdt, wstrides, wkeep = describe(weights, 1, "weights", self.device, streams)
-            if wdt != np.float32:
-                raise ValueError("weights must be float32, got %s" % wdt)
-            if wshape[0] != self.num_entries:
-                raise ValueError("weights must have one element per entry of the graph (%d), got %d" % (self.num_entries, wshape[0]))
-            if wshape[0] > 1 and wstrides[0] != 1:
-                if wmem != _lib.MEM_HOST:
-                    raise ValueError("weights must be dense")
-                wkeep = np.ascontiguousarray(wkeep)
-                wptr = wkeep.ctypes.data
-            pw = ctypes.c_void_p(wptr)
+        pw, wmem, wkeep = self._entry_weights(weights, streams)
         if isinstance(source, _MeshAggregator):
             if source.primitives != F:
                 raise ValueError("the aggregator has %d primitives, the mesh %d faces" % (source.primitives, F))
@@ -2094,6 +2098,176 @@ class FaceGraph:
         """`fill_labels()` left in HBM."""
         return self._fill(source, iterations, observed_threshold, weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, True,
                           return_unreached)
+
+    # ---- segments ----------------------------------------------------------------------------------------------------------------
+    def segments(self, source, weights=None, min_weight=None, dont_care_threshold=0.9):
+        """The connected components of equal labels over the graph, a `FaceSegments` (include/smesh_face_segments.h).
+
+        `source`: labels as a 1-D integer array [F] (numpy, or an int32 device array such as `labels_device()` returns; a negative
+        label is "don't care" and belongs to no segment), or what every other method takes -- an aggregator or float32 [F,C] rows,
+        whose labels are their argmax, -1 below `dont_care_threshold`.  With `weights` (one float32 per entry of `adjacency()`) an
+        entry links its two faces only where its weight is >= `min_weight`, which then has to be given: there is no default.  One
+        passing entry in either face's list links the two."""
+        if (weights is None) != (min_weight is None):
+            raise ValueError("min_weight is required with weights and only with weights")
+        if min_weight is not None and (isinstance(min_weight, bool) or not isinstance(min_weight, (int, float, np.integer, np.floating))):
+            raise ValueError("min_weight must be a number, got %r" % (min_weight,))
+        F = self.num_faces
+        streams = []
+        pw, wmem, wkeep = self._entry_weights(weights, streams)
+        mw = 0.0 if min_weight is None else float(min_weight)
+        h = ctypes.c_void_p()
+        if isinstance(source, _MeshAggregator):
+            if source.primitives != F:
+                raise ValueError("the aggregator has %d primitives, the mesh %d faces" % (source.primitives, F))
+            if source.device != self.device:
+                raise ValueError("aggregator and FaceGraph live on different devices")
+            # (`_h`: the aggregator's deferred views are handed to the library first, as get() does)
+            _lib.check(_lib.lib().smesh_aggregator_face_segments(source._h, self._h, float(dont_care_threshold), pw, wmem, mw, ctypes.byref(h)))
+            source._drain()
+        else:
+            shape = source.shape if hasattr(source, "shape") else np.shape(source)
+            if len(shape) == 2:      # rows: their labels by the finishing step (T = 0), left on the device
+                source = self.smooth_labels_device(source, 0, dont_care_threshold=dont_care_threshold)
+            if isinstance(source, np.ndarray) or not hasattr(source, "shape"):
+                a = np.asarray(source)
+                if a.ndim != 1 or a.dtype.kind not in "iu" or len(a) != F:
+                    raise ValueError("labels must be an integer array [%d], got %s %s" % (F, a.dtype, a.shape))
+                if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+                    raise ValueError("labels must fit int32")
+                source = np.ascontiguousarray(a, dtype=np.int32)
+            _same_device(source, self.device, "labels")
+            ptr, mem, lshape, ldt, lstrides, keep = describe(source, 1, "labels", self.device, streams)
+            if ldt != np.int32 or lshape[0] != F:
+                raise ValueError("labels must be int32[%d], got %s %s" % (F, ldt, tuple(lshape)))
+            if lshape[0] > 1 and lstrides[0] != 1:
+                raise ValueError("labels must be dense")
+            _lib.check(_lib.lib().smesh_face_segments_create(self._h, ctypes.c_void_p(ptr), mem, pw, wmem, mw, ctypes.byref(h)))
+        release_to(self.device, streams)
+        return FaceSegments(h, self.device)
+
+
+def _min_faces(min_faces):
+    if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)) or min_faces < 0 or min_faces > 0xFFFFFFFF:
+        raise ValueError("min_faces must be a non-negative int, got %r" % (min_faces,))
+    return int(min_faces)
+
+
+class FaceSegments:
+    """The segments of a labelled mesh, on the device (include/smesh_face_segments.h); made by `FaceGraph.segments()`.
+
+    A segment is a connected component of faces with one label (>= 0) under the graph's links; segments are numbered 0 .. count-1
+    in the order of their lowest face.  `ids()`: int32 [F], the segment of every face, -1 for an unlabelled one.  Per segment:
+    `first_faces()` uint32, `labels()` int32, `sizes()` uint32 (faces).  The `*_device()` forms leave a `DeviceArray` in HBM.
+    `despeckle_*(min_faces)`: a face is kept when its segment has at least `min_faces` faces; `despeckle_labels*` gives the labels
+    with every other face at -1 (a label table like any other, for `LabelRenderer`, `ConfusionMatrix.add*`, `PointTransfer`);
+    `despeckle_sums*` gives the rows of `source` with the rows of removed faces zeroed, a source for `FaceGraph.fill_*`, which
+    lets the surroundings grow back in.  Everything is an integer result: two calls agree in every bit."""
+
+    def __init__(self, handle, device):
+        self._h, self.device = handle, int(device)
+        F, S, n = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(_lib.lib().smesh_face_segments_size(self._h, ctypes.byref(F), ctypes.byref(S), ctypes.byref(n)))
+        self.num_faces, self.count, self.num_labelled = int(F.value), int(S.value), int(n.value)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and h.value:
+            try:
+                _lib.lib().smesh_face_segments_destroy(h)
+            except Exception:
+                pass
+
+    def _out(self, shape, dtype, on_device):
+        """(array, pointer, memkind) of a fresh result."""
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        if on_device:
+            from .device import DeviceBuffer
+            out = DeviceBuffer(max(n, 4), self.device).view(shape, dtype)
+            return out, ctypes.c_void_p(out.ptr), _lib.MEM_DEVICE
+        out = result_empty(shape, dtype) if len(shape) == 2 else np.empty(shape, dtype)
+        return out, out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST
+
+    def _get(self, which, on_device):
+        shape, dtype = [((self.num_faces,), np.int32), ((self.count,), np.uint32), ((self.count,), np.int32), ((self.count,), np.uint32)][which]
+        out, ptr, mem = self._out(shape, dtype, on_device)
+        args = [None] * 4
+        args[which] = ptr
+        _lib.check(_lib.lib().smesh_face_segments_get(self._h, *args, mem))
+        return out
+
+    def ids(self):
+        """int32 [F]: the segment of every face, -1 for an unlabelled face."""
+        return self._get(0, False)
+
+    def first_faces(self):
+        """uint32 [count]: the lowest face of every segment (ascending)."""
+        return self._get(1, False)
+
+    def labels(self):
+        """int32 [count]: the label of every segment."""
+        return self._get(2, False)
+
+    def sizes(self):
+        """uint32 [count]: the number of faces of every segment."""
+        return self._get(3, False)
+
+    def ids_device(self):
+        return self._get(0, True)
+
+    def first_faces_device(self):
+        return self._get(1, True)
+
+    def labels_device(self):
+        return self._get(2, True)
+
+    def sizes_device(self):
+        return self._get(3, True)
+
+    def _despeckle_labels(self, min_faces, return_removed, on_device):
+        min_faces = _min_faces(min_faces)
+        out, ptr, mem = self._out((self.num_faces,), np.int32, on_device)
+        faces, segs = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(_lib.lib().smesh_face_segments_despeckle_labels(self._h, min_faces, ptr, mem, ctypes.byref(faces) if return_removed else None,
+                                                                  ctypes.byref(segs) if return_removed else None))
+        return (out, int(faces.value), int(segs.value)) if return_removed else out
+
+    def despeckle_labels(self, min_faces, return_removed=False):
+        """int32 [F]: the label of every kept face, -1 elsewhere.  `return_removed=True`: `(labels, removed faces, removed segments)`."""
+        return self._despeckle_labels(min_faces, return_removed, False)
+
+    def despeckle_labels_device(self, min_faces, return_removed=False):
+        """`despeckle_labels()` left in HBM."""
+        return self._despeckle_labels(min_faces, return_removed, True)
+
+    def _despeckle_sums(self, source, min_faces, on_device):
+        min_faces = _min_faces(min_faces)
+        F = self.num_faces
+        if isinstance(source, _MeshAggregator):
+            if source.primitives != F:
+                raise ValueError("the aggregator has %d primitives, the segments %d faces" % (source.primitives, F))
+            if source.device != self.device:
+                raise ValueError("aggregator and FaceSegments live on different devices")
+            out, ptr, mem = self._out((F, source.classes), np.float32, on_device)
+            _lib.check(_lib.lib().smesh_aggregator_face_segments_despeckle(source._h, self._h, min_faces, ptr, mem))
+            source._drain()
+            return out
+        streams = []
+        _same_device(source, self.device, "face rows")
+        rptr, rmem, C, keep = _dense_rows(source, F, "face rows", self.device, streams)
+        out, ptr, mem = self._out((F, C), np.float32, on_device)
+        _lib.check(_lib.lib().smesh_face_segments_despeckle_rows(self._h, min_faces, ctypes.c_void_p(rptr), rmem, C, ptr, mem))
+        release_to(self.device, streams)
+        return out
+
+    def despeckle_sums(self, source, min_faces):
+        """float32 [F,C]: the rows of `source` (an aggregator over the F faces, or float32 [F,C] rows) with every class of a removed
+        face at 0; the rows of kept and of unlabelled faces pass through bit for bit."""
+        return self._despeckle_sums(source, min_faces, False)
+
+    def despeckle_sums_device(self, source, min_faces):
+        """`despeckle_sums()` left in HBM: a `source` for `FaceGraph.fill_*`."""
+        return self._despeckle_sums(source, min_faces, True)
 
 
 class MeshAggregatorSum(_MeshAggregator):
