@@ -114,6 +114,9 @@ def oracle_rows(oracle, kind, raw):
 
 
 CLASS_COUNTS = [1, 3, 6, 12, 19, 40, 64, 65, 150, 256, 300, 600]      # (600: beyond the rows whose sums stay in registers)
+# the wave-wide instances that hold 6, 7 and 8 chunks of 64 classes per lane (k_vertex_gather<64, 6 .. 8>: 321 .. 512 classes), and
+# the last count that stays in registers
+WIDE_CLASS_COUNTS = [321, 385, 449, 512]
 
 
 # ---- 1. adjacency ---------------------------------------------------------------------------------------------------------------
@@ -136,7 +139,7 @@ def test_adjacency_equals_the_numpy_csr(sm):
 
 
 # ---- 2. sums, bit for bit -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", CLASS_COUNTS)
+@pytest.mark.parametrize("C", CLASS_COUNTS + WIDE_CLASS_COUNTS)
 def test_sums_are_bit_equal(sm, oracle, C):
     from semantic_meshes_amd.device import to_device
     rng = np.random.default_rng(100 + C)
