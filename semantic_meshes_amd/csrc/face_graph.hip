@@ -5,7 +5,7 @@
 // The reference has no such step.  Graph, propagation and weights are defined to the bit in the header: every face (graph) and
 // every (face, class) element (propagation) is owned by ONE lane that adds in list order, so there are no float atomics, and the
 // launch boundary is the only synchronisation between two iterations.
-#include "common.hpp"
+#include "mesh_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -330,31 +330,6 @@ __global__ __launch_bounds__(kBlock) void k_fg_weights(const uint32_t* __restric
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-// Device blocks of one call, given back when it returns.
-struct TempBlocks {
-  std::vector<void*> blocks;
-  int alloc(void** out, size_t bytes) {
-    SMESH_HIP(dev_malloc(out, std::max<size_t>(bytes, 16)));
-    blocks.push_back(*out);
-    return SMESH_OK;
-  }
-  ~TempBlocks() { for (void* p : blocks) (void)dev_free(p); }
-};
-
-// `src` (`bytes` in `memkind`) on the device: itself, or a staged copy that lives as long as `tmp`.
-template <typename T>
-int on_device(DeviceCtx* ctx, TempBlocks& tmp, const T* src, size_t bytes, int memkind, const T** out) {
-  *out = src;
-  if (memkind == SMESH_MEM_DEVICE || bytes == 0) return SMESH_OK;
-  void* staged = nullptr;
-  SMESH_TRY(tmp.alloc(&staged, bytes));
-  SMESH_HIP(hipMemcpyAsync(staged, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  *out = static_cast<const T*>(staged);
-  return SMESH_OK;
-}
-
-bool memkind_ok(int m) { return m == SMESH_MEM_HOST || m == SMESH_MEM_DEVICE; }
-
 int build_graph(smesh_face_graph* gr, const int32_t* faces) {
   DeviceCtx* ctx = gr->ctx;
   hipStream_t st = ctx->stream;
@@ -374,10 +349,10 @@ int build_graph(smesh_face_graph* gr, const int32_t* faces) {
   int32_t* d_faces = nullptr;
   uint32_t *count = nullptr, *tiles = nullptr;
   unsigned long long* total = nullptr;
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&d_faces), F * 12));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&count), n * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&tiles), div_up(n, kScanTile) * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&total), 16));
+  SMESH_TRY(tmp.alloc(&d_faces, F * 12));
+  SMESH_TRY(tmp.alloc(&count, n * 4));
+  SMESH_TRY(tmp.alloc(&tiles, div_up(n, kScanTile) * 4));
+  SMESH_TRY(tmp.alloc(&total, 16));
   SMESH_HIP(dev_malloc(reinterpret_cast<void**>(&gr->offsets), std::max<uint64_t>(n * 4, 16)));
   SMESH_HIP(hipMemsetAsync(count, 0, n * 4, st));
   SMESH_HIP(hipMemsetAsync(total, 0, 16, st));
@@ -451,10 +426,10 @@ int propagate_device_rows(const smesh_face_graph* gr, DeviceCtx* ctx, const floa
     a.observed = p.observed;
     // x0's totals and two ping-pong pairs (rows, totals); a call of one iteration needs one pair
     float *tot0 = nullptr, *rows[2] = {nullptr, nullptr}, *tots[2] = {nullptr, nullptr};
-    SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&tot0), F * 4));
+    SMESH_TRY(tmp.alloc(&tot0, F * 4));
     for (uint32_t i = 0; i < std::min<uint32_t>(p.iterations, 2); i++) {
-      SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&rows[i]), (size_t)F * C * 4));
-      SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&tots[i]), F * 4));
+      SMESH_TRY(tmp.alloc(&rows[i], (size_t)F * C * 4));
+      SMESH_TRY(tmp.alloc(&tots[i], F * 4));
     }
     a.mode = kModeTotals;      // tot_0: the kernel's own total step on x0
     a.totn = tot0;
@@ -479,7 +454,7 @@ int propagate_device_rows(const smesh_face_graph* gr, DeviceCtx* ctx, const floa
     *p.out_unreached = 0;
     if (F) {
       unsigned long long* d_count = nullptr;
-      SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&d_count), 16));
+      SMESH_TRY(tmp.alloc(&d_count, 16));
       SMESH_HIP(hipMemsetAsync(d_count, 0, 16, st));
       hipLaunchKernelGGL(k_face_unreached, gf, b, 0, st, (const float*)tot_final, F, d_count);
       SMESH_HIP(hipGetLastError());
@@ -533,12 +508,9 @@ int smesh_face_graph_create(const int32_t* faces, uint64_t F, uint64_t V, int de
 int smesh_face_graph_destroy(smesh_face_graph_t* gr) {
   if (!gr) return SMESH_OK;
   std::lock_guard<std::recursive_mutex> lock(gr->ctx->mu);
-  int current = -1;
-  (void)hipGetDevice(&current);
-  (void)hipSetDevice(gr->ctx->device);
+  DeviceScope scope(gr->ctx->device);
   if (gr->offsets) (void)dev_free(gr->offsets);
   if (gr->neighbours) (void)dev_free(gr->neighbours);
-  if (current >= 0 && current != gr->ctx->device) (void)hipSetDevice(current);   // (the caller's current device is what it was)
   delete gr;
   return SMESH_OK;
 }
@@ -553,15 +525,7 @@ int smesh_face_graph_size(const smesh_face_graph_t* gr, uint64_t* F, uint64_t* V
 
 int smesh_face_graph_adjacency(const smesh_face_graph_t* gr, uint64_t* offsets, uint32_t* neighbours) {
   if (!gr || !offsets || (gr->nnz && !neighbours)) return fail(SMESH_ERR_INVALID, "NULL argument");
-  DeviceCtx* ctx = gr->ctx;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  SMESH_HIP(hipSetDevice(ctx->device));
-  std::vector<uint32_t> narrow(gr->F + 1);
-  SMESH_HIP(hipMemcpyAsync(narrow.data(), gr->offsets, (gr->F + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (gr->nnz) SMESH_HIP(hipMemcpyAsync(neighbours, gr->neighbours, gr->nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SMESH_HIP(hipStreamSynchronize(ctx->stream));
-  for (uint64_t f = 0; f <= gr->F; f++) offsets[f] = narrow[f];
-  return SMESH_OK;
+  return csr_to_host(gr->ctx, gr->offsets, gr->F, gr->neighbours, gr->nnz, offsets, neighbours);
 }
 
 int smesh_face_graph_propagate(const smesh_face_graph_t* gr, const float* face_rows, int rows_memkind, uint32_t C, const float* weights,
@@ -591,10 +555,7 @@ int smesh_aggregator_face_propagate(smesh_aggregator_t* ag, const smesh_face_gra
                       out_rows, out_labels, out_unreached, out_memkind};
   SMESH_TRY(check_prop_call(p));
   return smesh_aggregator_with_final_rows(ag, [&](DeviceCtx* ctx, const float* d_rows, uint64_t P, uint32_t C) -> int {
-    if (ctx != gr->ctx) return fail(SMESH_ERR_INVALID, "face propagate: aggregator and face graph live on different devices");
-    if (P != gr->F)
-      return fail(SMESH_ERR_INVALID, "face propagate: the aggregator has " + std::to_string(P) + " primitives, the face graph " +
-                                         std::to_string(gr->F) + " faces");
+    SMESH_TRY(check_rows_owner("face propagate", "face graph", ctx, gr->ctx, P, gr->F));
     return propagate_device_rows(gr, ctx, d_rows, C, p);
   });
 }
@@ -615,21 +576,21 @@ int smesh_face_graph_normal_weights(const smesh_face_graph_t* gr, const int32_t*
   const float* d_vertices = nullptr;
   float4* nl = nullptr;
   uint32_t* bad = nullptr;
-  float* d_w = out_weights;
+  Out<float> w;
   SMESH_TRY(on_device(ctx, tmp, faces, gr->F * 12, SMESH_MEM_HOST, &d_faces));
   SMESH_TRY(on_device(ctx, tmp, vertices, gr->V * 12, vertices_memkind, &d_vertices));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&nl), gr->F * 16));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&bad), 16));
-  if (out_memkind == SMESH_MEM_HOST) SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&d_w), gr->nnz * 4));
+  SMESH_TRY(tmp.alloc(&nl, gr->F * 16));
+  SMESH_TRY(tmp.alloc(&bad, 16));
+  SMESH_TRY(w.init(tmp, out_weights, gr->nnz * 4, out_memkind));
   SMESH_HIP(hipMemsetAsync(bad, 0, 16, st));
   const dim3 gf((uint32_t)div_up(gr->F, kBlock)), b(kBlock);
   hipLaunchKernelGGL(k_fg_normals, gf, b, 0, st, d_faces, gr->F, gr->V, d_vertices, nl, bad);
   hipLaunchKernelGGL(k_fg_weights, gf, b, 0, st, (const uint32_t*)gr->offsets, (const uint32_t*)gr->neighbours, gr->F, (const float4*)nl,
-                     power, two_sided, d_w);
+                     power, two_sided, w.dev);
   SMESH_HIP(hipGetLastError());
   uint32_t h_bad = 0;
   SMESH_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
-  if (out_memkind == SMESH_MEM_HOST) SMESH_HIP(hipMemcpyAsync(out_weights, d_w, gr->nnz * 4, hipMemcpyDeviceToHost, st));
+  SMESH_TRY(w.copy_back(st));
   SMESH_HIP(hipStreamSynchronize(st));
   if (h_bad) return fail(SMESH_ERR_INVALID, "normal weights: a face index lies outside [0, " + std::to_string(gr->V) + ")");
   return SMESH_OK;

@@ -14,7 +14,7 @@
 //      lane's progress: every loop below ends because an unsigned value that the lane itself holds strictly decreased (stated at each).
 //   4. The launch sequence is fixed: init, hook, flatten, flag + scan, number, count.  Nothing depends on the labels or on the mesh's
 //      diameter; there is no "until nothing changed".
-#include "common.hpp"
+#include "mesh_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -249,33 +249,6 @@ __global__ __launch_bounds__(kBlock) void k_seg_despeckle_rows(const T* __restri
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-// Device blocks of one call, given back when it returns.
-struct TempBlocks {
-  std::vector<void*> blocks;
-  int alloc(void** out, size_t bytes) {
-    SMESH_HIP(dev_malloc(out, std::max<size_t>(bytes, 16)));
-    blocks.push_back(*out);
-    return SMESH_OK;
-  }
-  ~TempBlocks() { for (void* p : blocks) (void)dev_free(p); }
-};
-
-// `src` (`bytes` in `memkind`) on the device: itself, or a staged copy that lives as long as `tmp`.
-template <typename T>
-int on_device(DeviceCtx* ctx, TempBlocks& tmp, const T* src, size_t bytes, int memkind, const T** out) {
-  *out = src;
-  if (memkind == SMESH_MEM_DEVICE || bytes == 0) return SMESH_OK;
-  void* staged = nullptr;
-  SMESH_TRY(tmp.alloc(&staged, bytes));
-  SMESH_HIP(hipMemcpyAsync(staged, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  *out = static_cast<const T*>(staged);
-  return SMESH_OK;
-}
-
-bool memkind_ok(int m) { return m == SMESH_MEM_HOST || m == SMESH_MEM_DEVICE; }
-
-hipMemcpyKind copy_out(int memkind) { return memkind == SMESH_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice; }
-
 dim3 grid_for(uint64_t n) { return dim3((uint32_t)div_up(n, kBlock)); }
 
 void free_segments(smesh_face_segments* sg) {
@@ -297,12 +270,12 @@ int build_segments(smesh_face_segments* sg, const uint32_t* offsets, const uint3
   TempBlocks tmp;
   uint32_t *parent = nullptr, *root = nullptr, *flag = nullptr, *number = nullptr, *tiles = nullptr;
   unsigned long long* labelled = nullptr;
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&parent), F * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&root), F * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&flag), n * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&number), n * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&tiles), div_up(n, kScanTile) * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&labelled), 16));
+  SMESH_TRY(tmp.alloc(&parent, F * 4));
+  SMESH_TRY(tmp.alloc(&root, F * 4));
+  SMESH_TRY(tmp.alloc(&flag, n * 4));
+  SMESH_TRY(tmp.alloc(&number, n * 4));
+  SMESH_TRY(tmp.alloc(&tiles, div_up(n, kScanTile) * 4));
+  SMESH_TRY(tmp.alloc(&labelled, 16));
   SMESH_HIP(hipMemsetAsync(labelled, 0, 16, st));
   const dim3 gf = grid_for(F), b(kBlock);
   hipLaunchKernelGGL(k_seg_init, gf, b, 0, st, offsets, nbr, (const int32_t*)sg->labels, d_w, min_weight, F, parent);
@@ -373,8 +346,9 @@ int despeckle_device_rows(const smesh_face_segments* sg, DeviceCtx* ctx, uint32_
   if (elems == 0) return SMESH_OK;
   if (div_up(elems, kBlock) > 0x7FFFFFFFull) return fail(SMESH_ERR_INVALID, "face segments: F * C must stay below 2^39");
   TempBlocks tmp;
-  float* d_out = out_rows;
-  if (out_memkind == SMESH_MEM_HOST) SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&d_out), elems * 4));
+  Out<float> out;
+  SMESH_TRY(out.init(tmp, out_rows, elems * 4, out_memkind));
+  float* const d_out = out.dev;
   const bool wide = C % 4 == 0 && (reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_out)) % 16 == 0;
   if (wide)
     hipLaunchKernelGGL(k_seg_despeckle_rows<float4>, grid_for(elems / 4), dim3(kBlock), 0, st, reinterpret_cast<const float4*>(d_rows),
@@ -383,7 +357,7 @@ int despeckle_device_rows(const smesh_face_segments* sg, DeviceCtx* ctx, uint32_
     hipLaunchKernelGGL(k_seg_despeckle_rows<float>, grid_for(elems), dim3(kBlock), 0, st, d_rows, (const int32_t*)sg->ids,
                        (const uint32_t*)sg->size, min_faces, elems, C, d_out);
   SMESH_HIP(hipGetLastError());
-  if (out_memkind == SMESH_MEM_HOST) SMESH_HIP(hipMemcpyAsync(out_rows, d_out, elems * 4, hipMemcpyDeviceToHost, st));
+  SMESH_TRY(out.copy_back(st));
   SMESH_HIP(hipStreamSynchronize(st));
   return SMESH_OK;
 }
@@ -416,10 +390,7 @@ int smesh_aggregator_face_segments(smesh_aggregator_t* ag, const smesh_face_grap
   SMESH_TRY(check_create_args(graph, weights, weights_memkind, out, &gctx, &offsets, &nbr, &F, &nnz));
   if (!ag) return fail(SMESH_ERR_INVALID, "NULL argument");
   return smesh_aggregator_with_final_rows(ag, [&](DeviceCtx* ctx, const float* d_rows, uint64_t P, uint32_t C) -> int {
-    if (ctx != gctx) return fail(SMESH_ERR_INVALID, "face segments: aggregator and face graph live on different devices");
-    if (P != F)
-      return fail(SMESH_ERR_INVALID, "face segments: the aggregator has " + std::to_string(P) + " primitives, the face graph " +
-                                         std::to_string(F) + " faces");
+    SMESH_TRY(check_rows_owner("face segments", "face graph", ctx, gctx, P, F));
     return create_segments(ctx, offsets, nbr, F, nnz, weights, weights_memkind, min_weight, out, [&](int32_t* d_labels) -> int {
       if (F == 0) return SMESH_OK;
       // the labels of the finishing step (vertices.hip), written straight into the handle's copy
@@ -431,12 +402,8 @@ int smesh_aggregator_face_segments(smesh_aggregator_t* ag, const smesh_face_grap
 int smesh_face_segments_destroy(smesh_face_segments_t* sg) {
   if (!sg) return SMESH_OK;
   std::lock_guard<std::recursive_mutex> lock(sg->ctx->mu);
-  int current = -1;
-  (void)hipGetDevice(&current);
-  (void)hipSetDevice(sg->ctx->device);
-  const int device = sg->ctx->device;
+  DeviceScope scope(sg->ctx->device);
   free_segments(sg);
-  if (current >= 0 && current != device) (void)hipSetDevice(current);   // (the caller's current device is what it was)
   return SMESH_OK;
 }
 
@@ -454,11 +421,10 @@ int smesh_face_segments_get(const smesh_face_segments_t* sg, int32_t* ids, uint3
   DeviceCtx* ctx = sg->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   SMESH_HIP(hipSetDevice(ctx->device));
-  const hipMemcpyKind kind = copy_out(out_memkind);
-  if (ids && sg->F) SMESH_HIP(hipMemcpyAsync(ids, sg->ids, sg->F * 4, kind, ctx->stream));
-  if (first_face && sg->S) SMESH_HIP(hipMemcpyAsync(first_face, sg->first_face, sg->S * 4, kind, ctx->stream));
-  if (label && sg->S) SMESH_HIP(hipMemcpyAsync(label, sg->seg_label, sg->S * 4, kind, ctx->stream));
-  if (size && sg->S) SMESH_HIP(hipMemcpyAsync(size, sg->size, sg->S * 4, kind, ctx->stream));
+  SMESH_TRY(copy_out<int32_t>(ids, sg->ids, sg->F * 4, out_memkind, ctx->stream));
+  SMESH_TRY(copy_out<uint32_t>(first_face, sg->first_face, sg->S * 4, out_memkind, ctx->stream));
+  SMESH_TRY(copy_out<int32_t>(label, sg->seg_label, sg->S * 4, out_memkind, ctx->stream));
+  SMESH_TRY(copy_out<uint32_t>(size, sg->size, sg->S * 4, out_memkind, ctx->stream));
   SMESH_HIP(hipStreamSynchronize(ctx->stream));
   return SMESH_OK;
 }
@@ -476,19 +442,19 @@ int smesh_face_segments_despeckle_labels(const smesh_face_segments_t* sg, uint32
   if (sg->F == 0) return SMESH_OK;
   hipStream_t st = ctx->stream;
   TempBlocks tmp;
-  int32_t* d_out = out_labels;
+  Out<int32_t> out;
   unsigned long long* removed = nullptr;      // [0] faces, [1] segments
-  if (out_memkind == SMESH_MEM_HOST) SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&d_out), sg->F * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&removed), 16));
+  SMESH_TRY(out.init(tmp, out_labels, sg->F * 4, out_memkind));
+  SMESH_TRY(tmp.alloc(&removed, 16));
   SMESH_HIP(hipMemsetAsync(removed, 0, 16, st));
   hipLaunchKernelGGL(k_seg_despeckle_labels, count_grid(sg->F), dim3(kBlock), 0, st, (const int32_t*)sg->labels, (const int32_t*)sg->ids,
-                     (const uint32_t*)sg->size, min_faces, sg->F, d_out, removed);
+                     (const uint32_t*)sg->size, min_faces, sg->F, out.dev, removed);
   if (removed_segments && sg->S)
     hipLaunchKernelGGL(k_seg_small, count_grid(sg->S), dim3(kBlock), 0, st, (const uint32_t*)sg->size, min_faces, sg->S, removed + 1);
   SMESH_HIP(hipGetLastError());
   unsigned long long h_removed[2] = {0, 0};
   SMESH_HIP(hipMemcpyAsync(h_removed, removed, 16, hipMemcpyDeviceToHost, st));
-  if (out_memkind == SMESH_MEM_HOST) SMESH_HIP(hipMemcpyAsync(out_labels, d_out, sg->F * 4, hipMemcpyDeviceToHost, st));
+  SMESH_TRY(out.copy_back(st));
   SMESH_HIP(hipStreamSynchronize(st));
   if (removed_faces) *removed_faces = h_removed[0];
   if (removed_segments) *removed_segments = h_removed[1];
@@ -516,10 +482,7 @@ int smesh_aggregator_face_segments_despeckle(smesh_aggregator_t* ag, const smesh
   if (!memkind_ok(out_memkind)) return fail(SMESH_ERR_INVALID, "face segments: bad memory kind");
   if (sg->F && !out_rows) return fail(SMESH_ERR_INVALID, "face segments: NULL out_rows");
   return smesh_aggregator_with_final_rows(ag, [&](DeviceCtx* ctx, const float* d_rows, uint64_t P, uint32_t C) -> int {
-    if (ctx != sg->ctx) return fail(SMESH_ERR_INVALID, "face segments: aggregator and segments live on different devices");
-    if (P != sg->F)
-      return fail(SMESH_ERR_INVALID, "face segments: the aggregator has " + std::to_string(P) + " primitives, the segments " +
-                                         std::to_string(sg->F) + " faces");
+    SMESH_TRY(check_rows_owner("face segments", "segments", ctx, sg->ctx, P, sg->F));
     return despeckle_device_rows(sg, ctx, min_faces, d_rows, C, out_rows, out_memkind);
   });
 }

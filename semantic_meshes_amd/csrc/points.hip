@@ -7,7 +7,7 @@
 // The closest face is defined to the bit (smesh_points.h) as the result of the exhaustive scan: faces are compared by (dist2, f), so
 // neither the order in which the grid walk meets them nor meeting one twice can change the result.  What the walk has to get right is
 // WHEN TO STOP: k_pts_nearest_grid, "the bound".
-#include "common.hpp"
+#include "mesh_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -418,40 +418,9 @@ void launch_point_gather(const PointGatherArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((k_point_gather<G>), dim3((uint32_t)div_up(a.N * G, kBlock)), dim3(kBlock), 0, st, a);
 }
 
-// Device blocks of one call, given back when it returns.
-struct TempBlocks {
-  std::vector<void*> blocks;
-  template <typename T>
-  int alloc(T** out, size_t bytes) {
-    void* p = nullptr;
-    SMESH_HIP(dev_malloc(&p, std::max<size_t>(bytes, 16)));
-    blocks.push_back(p);
-    *out = static_cast<T*>(p);
-    return SMESH_OK;
-  }
-  ~TempBlocks() { for (void* p : blocks) (void)dev_free(p); }
-};
-
-// `src` ([bytes] in `memkind`) on the device: itself, or a staged copy that lives as long as `tmp`.
-template <typename T>
-int on_device(DeviceCtx* ctx, TempBlocks& tmp, const T* src, size_t bytes, int memkind, const T** out) {
-  *out = src;
-  if (memkind == SMESH_MEM_DEVICE || bytes == 0) return SMESH_OK;
-  T* staged = nullptr;
-  SMESH_TRY(tmp.alloc(&staged, bytes));
-  SMESH_HIP(hipMemcpyAsync(staged, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  *out = staged;
-  return SMESH_OK;
-}
-
-bool memkind_ok(int m) { return m == SMESH_MEM_HOST || m == SMESH_MEM_DEVICE; }
-
-int check_gather_args(uint32_t C, uint64_t N, const void* faces, int faces_memkind, int mode, const void* out_rows, const void* out_labels,
-                      int out_memkind) {
-  if (C == 0) return fail(SMESH_ERR_INVALID, "point gather: the class count must be positive");
-  if (mode != SMESH_VTX_SUMS && mode != SMESH_VTX_ANNOTATIONS) return fail(SMESH_ERR_INVALID, "point gather: mode must be SMESH_VTX_SUMS or SMESH_VTX_ANNOTATIONS");
-  if (!out_rows && !out_labels) return fail(SMESH_ERR_INVALID, "point gather: at least one of out_rows and out_labels is required");
-  if (!memkind_ok(faces_memkind) || !memkind_ok(out_memkind)) return fail(SMESH_ERR_INVALID, "point gather: bad memory kind");
+int check_point_gather_args(uint32_t C, uint64_t N, const void* faces, int faces_memkind, int mode, const void* out_rows,
+                            const void* out_labels, int out_memkind) {
+  SMESH_TRY(check_gather_args("point gather", C, mode, out_rows, out_labels, faces_memkind, out_memkind));
   if (N && !faces) return fail(SMESH_ERR_INVALID, "point gather: NULL faces");
   if (N >= 0xFFFFFFFFull) return fail(SMESH_ERR_INVALID, "point gather: N must stay below 2^32");
   return SMESH_OK;
@@ -470,16 +439,15 @@ int gather_device_rows(DeviceCtx* ctx, const float* d_rows, uint64_t F, uint32_t
   a.C = C;
   a.mode = mode;
   a.threshold = threshold;
-  a.out_rows = out_rows;
-  a.out_labels = out_labels;
   SMESH_TRY(on_device(ctx, tmp, faces, N * 4, faces_memkind, &a.faces));
   SMESH_TRY(tmp.alloc(&a.bad, 16));
   SMESH_HIP(hipMemsetAsync(a.bad, 0, 16, st));
-  const size_t row_bytes = (size_t)N * C * 4, label_bytes = (size_t)N * 4;
-  if (out_memkind == SMESH_MEM_HOST) {
-    if (out_rows) SMESH_TRY(tmp.alloc(&a.out_rows, row_bytes));
-    if (out_labels) SMESH_TRY(tmp.alloc(&a.out_labels, label_bytes));
-  }
+  Out<float> rows;
+  Out<int32_t> labels;
+  SMESH_TRY(rows.init(tmp, out_rows, (size_t)N * C * 4, out_memkind));
+  SMESH_TRY(labels.init(tmp, out_labels, (size_t)N * 4, out_memkind));
+  a.out_rows = rows.dev;
+  a.out_labels = labels.dev;
   if (C <= 1) launch_point_gather<1>(a, st);
   else if (C <= 2) launch_point_gather<2>(a, st);
   else if (C <= 4) launch_point_gather<4>(a, st);
@@ -490,10 +458,8 @@ int gather_device_rows(DeviceCtx* ctx, const float* d_rows, uint64_t F, uint32_t
   SMESH_HIP(hipGetLastError());
   uint32_t h_bad = 0;
   SMESH_HIP(hipMemcpyAsync(&h_bad, a.bad, 4, hipMemcpyDeviceToHost, st));
-  if (out_memkind == SMESH_MEM_HOST) {
-    if (out_rows) SMESH_HIP(hipMemcpyAsync(out_rows, a.out_rows, row_bytes, hipMemcpyDeviceToHost, st));
-    if (out_labels) SMESH_HIP(hipMemcpyAsync(out_labels, a.out_labels, label_bytes, hipMemcpyDeviceToHost, st));
-  }
+  SMESH_TRY(rows.copy_back(st));
+  SMESH_TRY(labels.copy_back(st));
   SMESH_HIP(hipStreamSynchronize(st));
   if (h_bad) return fail(SMESH_ERR_INVALID, "point gather: a face index is not below " + std::to_string(F));
   return SMESH_OK;
@@ -643,12 +609,9 @@ int smesh_surface_index_create(const float* vertices, uint64_t V, const int32_t*
 int smesh_surface_index_destroy(smesh_surface_index_t* s) {
   if (!s) return SMESH_OK;
   std::lock_guard<std::recursive_mutex> lock(s->ctx->mu);
-  int current = -1;
-  (void)hipGetDevice(&current);
-  (void)hipSetDevice(s->ctx->device);
+  DeviceScope scope(s->ctx->device);
   for (void* p : {(void*)s->tris, (void*)s->edges, (void*)s->cell_start, (void*)s->cell_list, (void*)s->large})
     if (p) (void)dev_free(p);
-  if (current >= 0 && current != s->ctx->device) (void)hipSetDevice(current);   // (the caller's current device is what it was)
   delete s;
   return SMESH_OK;
 }
@@ -678,12 +641,10 @@ int smesh_surface_index_nearest(const smesh_surface_index_t* s, const float* poi
   TempBlocks tmp;
   const float* d_points = nullptr;
   SMESH_TRY(on_device(ctx, tmp, points, N * 12, points_memkind, &d_points));
-  int32_t* d_face = out_face;
-  float* d_dist2 = out_dist2;
-  if (out_memkind == SMESH_MEM_HOST) {
-    SMESH_TRY(tmp.alloc(&d_face, N * 4));
-    if (out_dist2) SMESH_TRY(tmp.alloc(&d_dist2, N * 4));
-  }
+  Out<int32_t> face;
+  Out<float> dist2;      // (out_dist2 may be null: the kernels then leave it out)
+  SMESH_TRY(face.init(tmp, out_face, N * 4, out_memkind));
+  SMESH_TRY(dist2.init(tmp, out_dist2, N * 4, out_memkind));
   const float r2 = max_distance * max_distance;
   const dim3 b(kBlock), gn((uint32_t)div_up(N, kBlock));
   if (opt_points_grid()) {
@@ -699,22 +660,20 @@ int smesh_surface_index_nearest(const smesh_surface_index_t* s, const float* poi
     launch_exclusive_scan(count, start, n, tiles, st);
     SMESH_HIP(hipMemsetAsync(count, 0, n * 4, st));      // now the fill cursors
     hipLaunchKernelGGL(k_pts_perm, gn, b, 0, st, cell, N, start, count, perm);
-    hipLaunchKernelGGL(k_pts_nearest_grid, gn, b, 0, st, d_points, perm, N, s->grid, r2, d_face, d_dist2);
+    hipLaunchKernelGGL(k_pts_nearest_grid, gn, b, 0, st, d_points, perm, N, s->grid, r2, face.dev, dist2.dev);
   } else {
-    hipLaunchKernelGGL(k_pts_nearest_all, gn, b, 0, st, d_points, N, s->tris, s->F, r2, d_face, d_dist2);
+    hipLaunchKernelGGL(k_pts_nearest_all, gn, b, 0, st, d_points, N, s->tris, s->F, r2, face.dev, dist2.dev);
   }
   SMESH_HIP(hipGetLastError());
-  if (out_memkind == SMESH_MEM_HOST) {
-    SMESH_HIP(hipMemcpyAsync(out_face, d_face, N * 4, hipMemcpyDeviceToHost, st));
-    if (out_dist2) SMESH_HIP(hipMemcpyAsync(out_dist2, d_dist2, N * 4, hipMemcpyDeviceToHost, st));
-  }
+  SMESH_TRY(face.copy_back(st));
+  SMESH_TRY(dist2.copy_back(st));
   SMESH_HIP(hipStreamSynchronize(st));
   return SMESH_OK;
 }
 
 int smesh_point_gather(const float* face_rows, int rows_memkind, uint64_t F, uint32_t C, const int32_t* faces, uint64_t N, int faces_memkind,
                        int mode, float dont_care_threshold, float* out_rows, int32_t* out_labels, int out_memkind) {
-  SMESH_TRY(check_gather_args(C, N, faces, faces_memkind, mode, out_rows, out_labels, out_memkind));
+  SMESH_TRY(check_point_gather_args(C, N, faces, faces_memkind, mode, out_rows, out_labels, out_memkind));
   if (!memkind_ok(rows_memkind)) return fail(SMESH_ERR_INVALID, "point gather: bad memory kind");
   if (F && !face_rows) return fail(SMESH_ERR_INVALID, "point gather: NULL face rows");
   int device = 0;
@@ -740,7 +699,7 @@ int smesh_point_gather(const float* face_rows, int rows_memkind, uint64_t F, uin
 int smesh_aggregator_point_annotations(smesh_aggregator_t* a, const int32_t* faces, uint64_t N, int faces_memkind, int mode,
                                        float dont_care_threshold, float* out_rows, int32_t* out_labels, int out_memkind) {
   if (!a) return fail(SMESH_ERR_INVALID, "NULL argument");
-  SMESH_TRY(check_gather_args(1, N, faces, faces_memkind, mode, out_rows, out_labels, out_memkind));
+  SMESH_TRY(check_point_gather_args(1, N, faces, faces_memkind, mode, out_rows, out_labels, out_memkind));
   return smesh_aggregator_with_final_rows(a, [&](DeviceCtx* ctx, const float* d_rows, uint64_t P, uint32_t C) -> int {
     return gather_device_rows(ctx, d_rows, P, C, faces, N, faces_memkind, mode, dont_care_threshold, out_rows, out_labels, out_memkind);
   });

@@ -6,7 +6,7 @@
 //
 // The sums are defined to the bit (smesh_vertices.h): ONE lane owns one (vertex, class) sum and adds the vertex's face rows in
 // ascending face order, so no float atomics anywhere and the result does not depend on how the lists were filled (they are sorted).
-#include "common.hpp"
+#include "mesh_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -281,53 +281,19 @@ int launch_gather(DeviceCtx* ctx, const GatherArgs& a) {
   return SMESH_OK;
 }
 
-// Device blocks of one call, given back when it returns.
-struct TempBlocks {
-  std::vector<void*> blocks;
-  int alloc(void** out, size_t bytes) {
-    SMESH_HIP(dev_malloc(out, std::max<size_t>(bytes, 16)));
-    blocks.push_back(*out);
-    return SMESH_OK;
-  }
-  ~TempBlocks() { for (void* p : blocks) (void)dev_free(p); }
-};
-
-int check_gather_args(uint32_t C, int mode, const void* out_rows, const void* out_labels, int rows_memkind, int out_memkind) {
-  if (C == 0) return fail(SMESH_ERR_INVALID, "vertex gather: the class count must be positive");
-  if (mode != SMESH_VTX_SUMS && mode != SMESH_VTX_ANNOTATIONS) return fail(SMESH_ERR_INVALID, "vertex gather: mode must be SMESH_VTX_SUMS or SMESH_VTX_ANNOTATIONS");
-  if (!out_rows && !out_labels) return fail(SMESH_ERR_INVALID, "vertex gather: at least one of out_rows and out_labels is required");
-  for (int m : {rows_memkind, out_memkind})
-    if (m != SMESH_MEM_HOST && m != SMESH_MEM_DEVICE) return fail(SMESH_ERR_INVALID, "vertex gather: bad memory kind");
-  return SMESH_OK;
-}
-
 // The gather over rows that are on the device already; the outputs go where the caller wants them.  Context locked, device current.
 int gather_device_rows(DeviceCtx* ctx, GatherArgs a, float* out_rows, int32_t* out_labels, int out_memkind) {
   TempBlocks tmp;
-  const size_t row_bytes = (size_t)a.n * a.C * 4, label_bytes = (size_t)a.n * 4;
-  a.out_rows = out_rows;
-  a.out_labels = out_labels;
-  if (out_memkind == SMESH_MEM_HOST) {
-    if (out_rows) SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&a.out_rows), row_bytes));
-    if (out_labels) SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&a.out_labels), label_bytes));
-  }
+  Out<float> rows;
+  Out<int32_t> labels;
+  SMESH_TRY(rows.init(tmp, out_rows, (size_t)a.n * a.C * 4, out_memkind));
+  SMESH_TRY(labels.init(tmp, out_labels, (size_t)a.n * 4, out_memkind));
+  a.out_rows = rows.dev;
+  a.out_labels = labels.dev;
   SMESH_TRY(launch_gather(ctx, a));
-  if (out_memkind == SMESH_MEM_HOST && a.n) {
-    if (out_rows) SMESH_HIP(hipMemcpyAsync(out_rows, a.out_rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_labels) SMESH_HIP(hipMemcpyAsync(out_labels, a.out_labels, label_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  }
+  SMESH_TRY(rows.copy_back(ctx->stream));
+  SMESH_TRY(labels.copy_back(ctx->stream));
   SMESH_HIP(hipStreamSynchronize(ctx->stream));
-  return SMESH_OK;
-}
-
-// `rows` ([n_rows, C] in `memkind`) on the device: itself, or a staged copy that lives as long as `tmp`.
-int rows_on_device(DeviceCtx* ctx, TempBlocks& tmp, const float* rows, uint64_t n_rows, uint32_t C, int memkind, const float** d_rows) {
-  *d_rows = rows;
-  if (memkind == SMESH_MEM_DEVICE || n_rows == 0) return SMESH_OK;
-  void* staged = nullptr;
-  SMESH_TRY(tmp.alloc(&staged, (size_t)n_rows * C * 4));
-  SMESH_HIP(hipMemcpyAsync(staged, rows, (size_t)n_rows * C * 4, hipMemcpyHostToDevice, ctx->stream));
-  *d_rows = static_cast<const float*>(staged);
   return SMESH_OK;
 }
 
@@ -351,11 +317,11 @@ int build_map(smesh_vertex_map* m, const int32_t* faces) {
   int32_t* d_faces = nullptr;
   uint32_t *count = nullptr, *tiles = nullptr, *flags = nullptr, *queue = nullptr;   // flags: [0] bad index seen, [1] queue length
   const uint64_t ntiles = div_up(n, kScanTile), queue_cap = 3 * F / (kShortList + 1) + 1;
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&d_faces), F * 12));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&count), n * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&tiles), ntiles * 4));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&flags), 16));
-  SMESH_TRY(tmp.alloc(reinterpret_cast<void**>(&queue), queue_cap * 4));
+  SMESH_TRY(tmp.alloc(&d_faces, F * 12));
+  SMESH_TRY(tmp.alloc(&count, n * 4));
+  SMESH_TRY(tmp.alloc(&tiles, ntiles * 4));
+  SMESH_TRY(tmp.alloc(&flags, 16));
+  SMESH_TRY(tmp.alloc(&queue, queue_cap * 4));
   SMESH_HIP(dev_malloc(reinterpret_cast<void**>(&m->offsets), std::max<uint64_t>(n * 4, 16)));
   SMESH_HIP(dev_malloc(reinterpret_cast<void**>(&m->list), std::max<uint64_t>(3 * F * 4, 16)));
   SMESH_HIP(hipMemsetAsync(count, 0, n * 4, st));
@@ -390,7 +356,7 @@ int build_map(smesh_vertex_map* m, const int32_t* faces) {
 // What eval.hip (smesh_aggregator_labels) needs: the label of every row of a dense float32 [n, C] array on the device -- a vertex
 // that owns exactly one row: 0 + x == x, so the row total and the label are those of the row itself.  Context locked, device current.
 int smesh_rows_labels(DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, float dont_care_threshold, int32_t* out_labels, int out_memkind) {
-  SMESH_TRY(check_gather_args(C, SMESH_VTX_ANNOTATIONS, nullptr, out_labels, SMESH_MEM_DEVICE, out_memkind));
+  SMESH_TRY(check_gather_args("vertex gather", C, SMESH_VTX_ANNOTATIONS, nullptr, out_labels, SMESH_MEM_DEVICE, out_memkind));
   if (n >= 0xFFFFFFFFull) return fail(SMESH_ERR_INVALID, "labels: the row count must stay below 2^32");
   GatherArgs g = {};
   g.rows = d_rows;
@@ -404,7 +370,7 @@ int smesh_rows_labels(DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t 
 // What face_graph.hip needs: the same gather with rows and/or labels out, and the device CSR of a map.
 int smesh_rows_finish(DeviceCtx* ctx, const float* d_rows, uint64_t n, uint32_t C, int mode, float dont_care_threshold, float* out_rows,
                       int32_t* out_labels, int out_memkind) {
-  SMESH_TRY(check_gather_args(C, mode, out_rows, out_labels, SMESH_MEM_DEVICE, out_memkind));
+  SMESH_TRY(check_gather_args("vertex gather", C, mode, out_rows, out_labels, SMESH_MEM_DEVICE, out_memkind));
   if (n >= 0xFFFFFFFFull) return fail(SMESH_ERR_INVALID, "rows: the row count must stay below 2^32");
   GatherArgs g = {};
   g.rows = d_rows;
@@ -450,12 +416,9 @@ int smesh_vertex_map_create(const int32_t* faces, uint64_t F, uint64_t V, int de
 int smesh_vertex_map_destroy(smesh_vertex_map_t* m) {
   if (!m) return SMESH_OK;
   std::lock_guard<std::recursive_mutex> lock(m->ctx->mu);
-  int current = -1;
-  (void)hipGetDevice(&current);
-  (void)hipSetDevice(m->ctx->device);
+  DeviceScope scope(m->ctx->device);
   if (m->offsets) (void)dev_free(m->offsets);
   if (m->list) (void)dev_free(m->list);
-  if (current >= 0 && current != m->ctx->device) (void)hipSetDevice(current);   // (the caller's current device is what it was)
   delete m;
   return SMESH_OK;
 }
@@ -470,40 +433,29 @@ int smesh_vertex_map_size(const smesh_vertex_map_t* m, uint64_t* F, uint64_t* V,
 
 int smesh_vertex_map_adjacency(const smesh_vertex_map_t* m, uint64_t* offsets, uint32_t* faces) {
   if (!m || !offsets || (m->nnz && !faces)) return fail(SMESH_ERR_INVALID, "NULL argument");
-  DeviceCtx* ctx = m->ctx;
-  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-  SMESH_HIP(hipSetDevice(ctx->device));
-  std::vector<uint32_t> narrow(m->V + 1);
-  SMESH_HIP(hipMemcpyAsync(narrow.data(), m->offsets, (m->V + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-  if (m->nnz) SMESH_HIP(hipMemcpyAsync(faces, m->list, m->nnz * 4, hipMemcpyDeviceToHost, ctx->stream));
-  SMESH_HIP(hipStreamSynchronize(ctx->stream));
-  for (uint64_t v = 0; v <= m->V; v++) offsets[v] = narrow[v];
-  return SMESH_OK;
+  return csr_to_host(m->ctx, m->offsets, m->V, m->list, m->nnz, offsets, faces);
 }
 
 int smesh_vertex_map_gather(const smesh_vertex_map_t* m, const float* face_rows, int rows_memkind, uint32_t C, int mode,
                             float dont_care_threshold, float* out_rows, int32_t* out_labels, int out_memkind) {
   if (!m) return fail(SMESH_ERR_INVALID, "NULL vertex map");
-  SMESH_TRY(check_gather_args(C, mode, out_rows, out_labels, rows_memkind, out_memkind));
+  SMESH_TRY(check_gather_args("vertex gather", C, mode, out_rows, out_labels, rows_memkind, out_memkind));
   if (m->F && !face_rows) return fail(SMESH_ERR_INVALID, "vertex gather: NULL face rows");
   DeviceCtx* ctx = m->ctx;
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   SMESH_HIP(hipSetDevice(ctx->device));
   TempBlocks tmp;
   const float* d_rows = nullptr;
-  SMESH_TRY(rows_on_device(ctx, tmp, face_rows, m->F, C, rows_memkind, &d_rows));
+  SMESH_TRY(on_device(ctx, tmp, face_rows, (size_t)m->F * C * 4, rows_memkind, &d_rows));
   return gather_device_rows(ctx, map_args(m, d_rows, C, mode, dont_care_threshold), out_rows, out_labels, out_memkind);
 }
 
 int smesh_aggregator_vertex_annotations(smesh_aggregator_t* a, const smesh_vertex_map_t* m, int mode, float dont_care_threshold,
                                         float* out_rows, int32_t* out_labels, int out_memkind) {
   if (!a || !m) return fail(SMESH_ERR_INVALID, "NULL argument");
-  SMESH_TRY(check_gather_args(1, mode, out_rows, out_labels, SMESH_MEM_DEVICE, out_memkind));
+  SMESH_TRY(check_gather_args("vertex gather", 1, mode, out_rows, out_labels, SMESH_MEM_DEVICE, out_memkind));
   return smesh_aggregator_with_final_rows(a, [&](DeviceCtx* ctx, const float* d_rows, uint64_t P, uint32_t C) -> int {
-    if (ctx != m->ctx) return fail(SMESH_ERR_INVALID, "vertex annotations: aggregator and vertex map live on different devices");
-    if (P != m->F)
-      return fail(SMESH_ERR_INVALID, "vertex annotations: the aggregator has " + std::to_string(P) + " primitives, the vertex map " +
-                                         std::to_string(m->F) + " faces");
+    SMESH_TRY(check_rows_owner("vertex annotations", "vertex map", ctx, m->ctx, P, m->F));
     return gather_device_rows(ctx, map_args(m, d_rows, C, mode, dont_care_threshold), out_rows, out_labels, out_memkind);
   });
 }
@@ -511,7 +463,7 @@ int smesh_aggregator_vertex_annotations(smesh_aggregator_t* a, const smesh_verte
 int smesh_renderer_texel_face_rows(smesh_renderer_t* r, const float* texel_rows, int rows_memkind, uint32_t C, int mode,
                                    float dont_care_threshold, float* out_face_rows, int out_memkind) {
   if (!r) return fail(SMESH_ERR_INVALID, "NULL renderer");
-  SMESH_TRY(check_gather_args(C, mode, out_face_rows, nullptr, rows_memkind, out_memkind));
+  SMESH_TRY(check_gather_args("vertex gather", C, mode, out_face_rows, nullptr, rows_memkind, out_memkind));
   DeviceCtx* ctx = nullptr;
   uint64_t F = 0, P = 0;
   GatherArgs g = {};
@@ -520,7 +472,7 @@ int smesh_renderer_texel_face_rows(smesh_renderer_t* r, const float* texel_rows,
   std::lock_guard<std::recursive_mutex> lock(ctx->mu);
   SMESH_HIP(hipSetDevice(ctx->device));
   TempBlocks tmp;
-  SMESH_TRY(rows_on_device(ctx, tmp, texel_rows, P, C, rows_memkind, &g.rows));
+  SMESH_TRY(on_device(ctx, tmp, texel_rows, (size_t)P * C * 4, rows_memkind, &g.rows));
   g.n = F;
   g.C = C;
   g.mode = mode;

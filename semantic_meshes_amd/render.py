@@ -213,8 +213,9 @@ class _Renderer:
 
     # ---- texel annotations back on the mesh (include/smesh_vertices.h); texel renderers only -------------------------------------
     def _face_rows(self, source, threshold, normalize, on_device):
-        from .fusion import _MeshAggregator, _dense_rows
-        from .device import DeviceBuffer, release_to, result_empty
+        from .fusion import _MeshAggregator
+        from .mesh_results import _dense_rows, _out
+        from .device import release_to
         if not getattr(self, "is_texel", False):     # (defined for every renderer so that a triangle renderer is refused, not unknown)
             raise ValueError("face_annotations needs a texel renderer (render.texels): the primitives of this one are its faces")
         P, F = self.getPrimitivesNum(), self._num_faces
@@ -228,12 +229,7 @@ class _Renderer:
             ptr, mem, C = keep.ptr, _lib.MEM_DEVICE, source.classes
         else:
             ptr, mem, C, keep = _dense_rows(source, P, "texel rows", self.device, streams)
-        if on_device:
-            out = DeviceBuffer(max(F * C * 4, 4), self.device).view((F, C), np.float32)
-            pout, omem = ctypes.c_void_p(out.ptr), _lib.MEM_DEVICE
-        else:
-            out = result_empty((F, C), np.float32)
-            pout, omem = out.ctypes.data_as(ctypes.c_void_p), _lib.MEM_HOST
+        out, pout, omem = _out((F, C), np.float32, self.device, on_device)
         _lib.check(_lib.lib().smesh_renderer_texel_face_rows(self._h, ctypes.c_void_p(ptr), mem, C,
                                                             _lib.VTX_ANNOTATIONS if normalize else _lib.VTX_SUMS, float(threshold), pout, omem))
         release_to(self.device, streams)
