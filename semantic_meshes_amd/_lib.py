@@ -292,6 +292,22 @@ DEPTH_SIGNATURES = {
                                        P(c_void_p), c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(DepthGatePOD), c_void_p]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_view_weights.h: fusion weighted by viewing geometry,
+# product-only like the tables above (no profile slot; image kinds and sensor arguments are those of smesh_depth.h)
+VW_MAX_POWER = 16                                                   # SMESH_VW_MAX_POWER
+
+
+class ViewWeightsPOD(ctypes.Structure):
+    """smesh_view_weights_spec_t (include/smesh_view_weights.h)."""
+    _fields_ = [("power", ctypes.c_int32), ("min_cos", c_float), ("two_sided", ctypes.c_int32), ("max_depth", c_float), ("falloff_depth", c_float)]
+
+
+VIEW_WEIGHTS_SIGNATURES = {
+    "smesh_view_weights": (c_int, [c_void_p, P(CameraPOD), c_void_p, c_void_p, c_u64, c_u64, P(ViewWeightsPOD), c_void_p, c_void_p, c_void_p]),
+    "smesh_fuse_views_view_weights": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, P(c_void_p), c_int, P(c_void_p), P(ViewWeightsPOD),
+                                              P(c_void_p), c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(DepthGatePOD), c_void_p, c_void_p]),
+}
+
 # name -> (restype, argtypes); one entry per symbol declared in include/smesh_face_graph.h: the faces across every face's edges and the
 # propagation of fused rows over them, product-only like the tables above (no profile slot; the output modes are SMESH_VTX_*)
 FG_SMOOTH, FG_FILL = 0, 1                                           # SMESH_FG_*
@@ -447,7 +463,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

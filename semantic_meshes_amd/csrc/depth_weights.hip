@@ -216,9 +216,38 @@ int gate_group(DeviceCtx* ctx, DepthScratch& scratch, const GatedView* views, co
 
 }  // namespace
 
-// (context.cpp: the read-only option "depth_weights_launches")
+// (context.cpp: the read-only option "depth_weights_launches"; view_weights.hip: a depth gate behind the view weights -- depth_gate.hpp)
 namespace smesh {
 uint64_t smesh_depth_weights_launches() { return g_launches.load(); }
+
+int depth_gate_check(int dtype, const int64_t* strides, int memkind, uint64_t w, uint64_t h, const smesh_depth_gate_t* gate) {
+  return depth_check(dtype, strides, memkind, w, h, gate);
+}
+
+int depth_gate_group(DeviceCtx* ctx, DepthScratch& scratch, const GatedView* views, const DepthGateCall& call, uint64_t first, int m,
+                     uint64_t* counts_host) {
+  return gate_group(ctx, scratch, views, call.sensors + first, call.memkind, m, sensor_desc(call.dtype, call.strides, call.w, call.h), call.gate,
+                    counts_host);
+}
+
+int depth_image_input(smesh_aggregator* aggregator, int image_kind, ViewInput* in) {
+  const uint32_t C = smesh_aggregator_classes(aggregator);
+  switch (image_kind) {
+    case SMESH_DEPTH_IMG_F32: *in = ViewInput::f32(nullptr); break;
+    case SMESH_DEPTH_IMG_F16: *in = ViewInput::half(nullptr, SMESH_PROBS_F16); break;
+    case SMESH_DEPTH_IMG_BF16: *in = ViewInput::half(nullptr, SMESH_PROBS_BF16); break;
+    case SMESH_DEPTH_IMG_LABELS_U8:
+      if (C > 255u) return fail(SMESH_ERR_INVALID, "a uint8 label plane holds at most 255 classes");
+      *in = ViewInput::labels(nullptr, 1);
+      break;
+    case SMESH_DEPTH_IMG_LABELS_U16:
+      if (C > 65535u) return fail(SMESH_ERR_INVALID, "label images need an aggregator of at most 65535 classes");
+      *in = ViewInput::labels(nullptr, 2);
+      break;
+    default: return fail(SMESH_ERR_INVALID, "bad image kind");
+  }
+  return SMESH_OK;
+}
 }  // namespace smesh
 
 extern "C" int smesh_depth_weights(const float* depth, uint64_t W, uint64_t H, const void* sensor, int sensor_dtype, const int64_t sensor_strides[2],
@@ -249,21 +278,7 @@ extern "C" int smesh_fuse_views_depth(smesh_renderer_t* renderer, smesh_aggregat
   if (!renderer || !aggregator || (n && (!cameras || !images || !sensors))) return fail(SMESH_ERR_INVALID, "NULL argument");
   SMESH_TRY(depth_check(sensor_dtype, sensor_strides, sensor_memkind, w, h, gate));
   ViewInput in;
-  const uint32_t C = smesh_aggregator_classes(aggregator);
-  switch (image_kind) {
-    case SMESH_DEPTH_IMG_F32: in = ViewInput::f32(nullptr); break;
-    case SMESH_DEPTH_IMG_F16: in = ViewInput::half(nullptr, SMESH_PROBS_F16); break;
-    case SMESH_DEPTH_IMG_BF16: in = ViewInput::half(nullptr, SMESH_PROBS_BF16); break;
-    case SMESH_DEPTH_IMG_LABELS_U8:
-      if (C > 255u) return fail(SMESH_ERR_INVALID, "a uint8 label plane holds at most 255 classes");
-      in = ViewInput::labels(nullptr, 1);
-      break;
-    case SMESH_DEPTH_IMG_LABELS_U16:
-      if (C > 65535u) return fail(SMESH_ERR_INVALID, "label images need an aggregator of at most 65535 classes");
-      in = ViewInput::labels(nullptr, 2);
-      break;
-    default: return fail(SMESH_ERR_INVALID, "bad image kind");
-  }
+  SMESH_TRY(depth_image_input(aggregator, image_kind, &in));
   for (uint64_t i = 0; i < n; i++)
     if (!sensors[i]) return fail(SMESH_ERR_INVALID, "NULL sensor depth image");
   if (counts) for (uint64_t i = 0; i < n * kCounts; i++) counts[i] = 0;

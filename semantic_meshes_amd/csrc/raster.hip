@@ -1621,6 +1621,7 @@ struct smesh_renderer {
   hipEvent_t hash_ev[kRecordSides] = {};   // recorded on the main stream behind the kernel that writes d_hash[s]
   Scratch match_stage;             // device copy of a host index image that is being looked up
   DepthScratch gate;               // smesh_renderer_fuse_views_gated: weights planes, staged sensor images and counts of a group
+  float* normals = nullptr;        // [F][4] face normals by primitive id, built at first use (view_weights.hip, smesh_renderer_mesh)
   int last_render_side = 0;        // the side render_into() filled last (smesh_renderer_render_stats)
   bool raster_pending = false;     // work queued on the raster stream since the last synchronisation
   bool main_pending = false;       // renderer state (keys, scratch) used on the main stream since then
@@ -2598,7 +2599,7 @@ int smesh_renderer_destroy(smesh_renderer_t* r) {
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->raster_stream);
   (void)hipStreamSynchronize(r->ctx->stream);
-  for (void* p : {(void*)r->prim_id, (void*)r->verts, (void*)r->faces, (void*)r->tex_res, (void*)r->tex_first, (void*)r->ml.first, (void*)r->ml.ids, (void*)r->ml.tris, (void*)r->ml.pos})
+  for (void* p : {(void*)r->prim_id, (void*)r->verts, (void*)r->faces, (void*)r->tex_res, (void*)r->tex_first, (void*)r->ml.first, (void*)r->ml.ids, (void*)r->ml.tris, (void*)r->ml.pos, (void*)r->normals})
     if (p) (void)dev_free(p);
   for (auto& sd : r->side)
     for (void* p : {(void*)sd.big_queue, (void*)sd.big_count, (void*)sd.frags, (void*)sd.kinds})
@@ -3072,7 +3073,8 @@ int smesh_renderer_fuse_views_gated(smesh_renderer* r, smesh_aggregator* a, cons
       const uint64_t N = cam->width * cam->height;
       if (grouped) {
         gv[v] = GatedView{reinterpret_cast<float*>(static_cast<uint32_t*>(r->fused[v].ptr) + N), weights ? weights[i + (uint64_t)v] : nullptr,
-                          reinterpret_cast<float*>(static_cast<char*>(r->gate.w.ptr) + woff), cam->width, cam->height};
+                          reinterpret_cast<float*>(static_cast<char*>(r->gate.w.ptr) + woff), cam->width, cam->height,
+                          static_cast<const uint32_t*>(r->fused[v].ptr), cam};
         woff += round256(N * 4);
         continue;
       }
@@ -3087,7 +3089,7 @@ int smesh_renderer_fuse_views_gated(smesh_renderer* r, smesh_aggregator* a, cons
       uint32_t* d_idx = static_cast<uint32_t*>(r->fused[v].ptr);
       float* d_depth = reinterpret_cast<float*>(d_idx + N);
       SMESH_TRY(render_into(r, cam, d_idx, d_depth, ctx->stream, v, /*idx_optional=*/0));
-      gv[v] = GatedView{d_depth, weights ? weights[i + (uint64_t)v] : nullptr, reinterpret_cast<float*>(static_cast<char*>(r->gate.w.ptr) + woff), cam->width, cam->height};
+      gv[v] = GatedView{d_depth, weights ? weights[i + (uint64_t)v] : nullptr, reinterpret_cast<float*>(static_cast<char*>(r->gate.w.ptr) + woff), cam->width, cam->height, d_idx, cam};
       woff += round256(N * 4);
     }
     SMESH_TRY(gate(ctx, r->gate, i, m, gv));
@@ -3125,6 +3127,13 @@ int smesh_renderer_fuse_views_gated(smesh_renderer* r, smesh_aggregator* a, cons
     }
     r->fused_seq += (uint64_t)m;
   }
+  return SMESH_OK;
+}
+
+// (view_weights.hip; declared in depth_gate.hpp)
+int smesh_renderer_mesh(smesh_renderer* r, RendererMesh* out) {
+  if (!r || !out) return fail(SMESH_ERR_INVALID, "NULL renderer");
+  *out = RendererMesh{r->ctx, r->V, r->F, r->verts, r->faces, r->prim_id, r->texels, &r->normals, &r->mu};
   return SMESH_OK;
 }
 

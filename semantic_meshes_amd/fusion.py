@@ -310,17 +310,19 @@ def _describe_sensor(sensor, device, streams, what="sensor depth image"):
     return sp, smem, (int(sshape[0]), int(sshape[1])), _DEPTH_CODES[sdt.name], tuple(sstr), keep, sdt
 
 
-def _dense_plane(image, W, H, device, what, streams):
-    """`image` as a dense float32 (W,H) plane in device memory (a host array is copied there): (pointer, keep-alive)."""
+def _dense_plane(image, W, H, device, what, streams, dtype=np.float32):
+    """`image` as a dense (W,H) plane of `dtype` (float32; uint32 for an index plane) in device memory (a host array is copied
+    there): (pointer, keep-alive)."""
     from .device import to_device
+    dtype = np.dtype(dtype)
     ptr, mem, shape, dt, strides, keep = describe(image, 2, what, device, streams)
     if mem == _lib.MEM_HOST:
-        if not isinstance(keep, np.ndarray) or dt.kind != "f":
-            raise ValueError("%s must be a float32 array, got %s" % (what, dt))
-        keep = to_device(np.ascontiguousarray(keep, dtype=np.float32), device)
+        if not isinstance(keep, np.ndarray) or (dt.kind != "f" if dtype.kind == "f" else dt != dtype):
+            raise ValueError("%s must be a %s array, got %s" % (what, dtype, dt))
+        keep = to_device(np.ascontiguousarray(keep, dtype=dtype), device)
         ptr, shape, dt, strides = keep.ptr, keep.shape, keep.dtype, keep.strides
-    if tuple(shape) != (W, H) or dt != np.float32 or tuple(strides) != (H, 1):
-        raise ValueError("%s must be contiguous float32 (W,H) = %s, got %s %s" % (what, (W, H), dt, tuple(shape)))
+    if tuple(shape) != (W, H) or dt != dtype or tuple(strides) != (H, 1):
+        raise ValueError("%s must be contiguous %s (W,H) = %s, got %s %s" % (what, dtype, (W, H), dt, tuple(shape)))
     return ptr, keep
 
 
@@ -381,6 +383,109 @@ def _gate_keywords(sensor_depths, depth_gate, depth_stats, n, sample_in_kernel, 
     if len(sensors) != n:
         raise ValueError("%s needs one sensor depth image per camera: %d for %d cameras" % (what, len(sensors), n))
     return sensors
+
+
+class ViewWeights:
+    """The spec of the viewing-geometry weights (include/smesh_view_weights.h, where the rule is stated to the bit): a pixel's weight
+    is cos^`power` of the angle between its ray and the normal of the face it shows (an integer power, 0 .. 16), times
+    1 / (1 + (depth / `falloff_depth`)^2) where a falloff is given.  `min_cos`: pixels seen at a smaller cosine get weight 0.
+    `two_sided=False`: faces that look away from the camera get weight 0.  `max_depth`: rendered depths beyond it get weight 0
+    (None: no limit).  Triangle renderers only."""
+
+    def __init__(self, power=1, min_cos=0.0, two_sided=True, max_depth=None, falloff_depth=None):
+        if isinstance(power, bool) or not isinstance(power, (int, np.integer)) or not 0 <= int(power) <= _lib.VW_MAX_POWER:
+            raise ValueError("ViewWeights: power must be an integer in [0, %d], got %r" % (_lib.VW_MAX_POWER, power))
+        self.power = int(power)
+
+        def number(v, name):
+            try:
+                f = float(np.float32(v))
+            except (TypeError, ValueError):
+                raise ValueError("ViewWeights: %s must be a number, got %r" % (name, v))
+            if f != f:
+                raise ValueError("ViewWeights: %s must not be NaN" % name)
+            return f
+        self.min_cos = number(min_cos, "min_cos")
+        if not 0.0 <= self.min_cos <= 1.0:
+            raise ValueError("ViewWeights: min_cos must be in [0, 1], got %r" % (min_cos,))
+        if not isinstance(two_sided, (bool, np.bool_)):
+            raise ValueError("ViewWeights: two_sided must be True or False, got %r" % (two_sided,))
+        self.two_sided = bool(two_sided)
+        self.max_depth = None if max_depth is None else number(max_depth, "max_depth")
+        self.falloff_depth = None if falloff_depth is None else number(falloff_depth, "falloff_depth")
+        if self.falloff_depth is not None and not self.falloff_depth > 0.0:
+            raise ValueError("ViewWeights: falloff_depth must be > 0 or None, got %r" % (falloff_depth,))
+
+    def _pod(self):
+        inf = float("inf")
+        return _lib.ViewWeightsPOD(self.power, self.min_cos, 1 if self.two_sided else 0, inf if self.max_depth is None else self.max_depth,
+                                   inf if self.falloff_depth is None else self.falloff_depth)
+
+    def __repr__(self):
+        return "ViewWeights(power=%r, min_cos=%r, two_sided=%r, max_depth=%r, falloff_depth=%r)" % (
+            self.power, self.min_cos, self.two_sided, self.max_depth, self.falloff_depth)
+
+
+def _triangle_renderer(renderer, what):
+    if getattr(renderer, "is_texel", False):
+        raise ValueError("%s: view weights need a triangle renderer -- the index plane of a texel renderer holds texel ids, and a "
+                         "texel -> face lookup is not built" % what)
+
+
+def view_weights_device(renderer, camera, primitive_indices, depth, spec, weights_image=None, return_counts=False):
+    """The viewing-geometry weights of ONE view on the device (`smesh_view_weights`, include/smesh_view_weights.h):
+    `primitive_indices`, `depth` the uint32 and float32 (W,H) planes of `renderer.render(camera)` (or host copies of them), `spec` a
+    `ViewWeights`, `weights_image` an optional float32 (W,H) image that is multiplied in.  Returns a float32 (W,H) `DeviceArray` --
+    what `add(idx, probs, w)`, `add_many`, `add_labels` and `fuse_views_ranged` take as a weights image; with `return_counts=True`
+    also the uint64 [visible, far, grazing, backfacing] counts, which makes the call wait."""
+    from .device import DeviceBuffer
+    if not isinstance(spec, ViewWeights):
+        raise ValueError("view_weights must be a fusion.ViewWeights, got %r" % (spec,))
+    _triangle_renderer(renderer, "view_weights")
+    device = int(renderer.device)
+    W, H = camera.resolution
+    W, H = int(W), int(H)
+    streams = []
+    ip, ikeep = _dense_plane(primitive_indices, W, H, device, "primitive index plane", streams, np.uint32)
+    dp, dkeep = _dense_plane(depth, W, H, device, "depth plane", streams)
+    wp, wkeep = (None, None) if weights_image is None else _dense_plane(weights_image, W, H, device, "weights image", streams)
+    out = DeviceBuffer(max(W * H * 4, 4), device).view((W, H), np.float32)
+    counts = np.zeros(4, np.uint64) if return_counts else None
+    pod = spec._pod()
+    _lib.check(_lib.lib().smesh_view_weights(renderer._h, ctypes.byref(camera._pod), ctypes.c_void_p(ip), ctypes.c_void_p(dp), W, H, ctypes.byref(pod),
+                                             None if wp is None else ctypes.c_void_p(wp), ctypes.c_void_p(out.ptr),
+                                             None if counts is None else counts.ctypes.data_as(ctypes.c_void_p)))
+    release_to(device, streams)
+    if any(k is not None and not isinstance(k, (DeviceArray, np.ndarray)) for k in (ikeep, dkeep, wkeep)):
+        _lib.synchronize(device)      # (a foreign input may be freed by its owner as soon as we return)
+    out._gate_inputs = (ikeep, dkeep, wkeep)      # (this library's own arrays are freed behind its streams)
+    return (out, counts) if return_counts else out
+
+
+def view_weights(renderer, camera, primitive_indices, depth, spec, weights_image=None, return_counts=False):
+    """`view_weights_device` copied to the host: a numpy array (and the counts)."""
+    r = view_weights_device(renderer, camera, primitive_indices, depth, spec, weights_image, return_counts)
+    return (r[0].numpy(), r[1]) if return_counts else r.numpy()
+
+
+def _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, what):
+    """The `view_weights=` and `view_stats=` keywords of a fuse call, checked: None for a call without them, else the spec."""
+    if view_weights is None:
+        if view_stats:
+            raise ValueError("%s: view_stats=True needs view_weights" % what)
+        return None
+    if not isinstance(view_weights, ViewWeights):
+        raise ValueError("%s: view_weights must be a fusion.ViewWeights, got %r" % (what, view_weights))
+    if sample_in_kernel:
+        raise ValueError("%s: sample_in_kernel=True cannot be combined with view weights" % what)
+    _triangle_renderer(renderer, what)
+    return view_weights
+
+
+def _stats_of(view_counts, depth_counts, view_stats, depth_stats, single=False):
+    """What a weighted / gated fuse call returns: None, one uint64 counts array, or the pair (view counts, depth counts)."""
+    got = [c[0] if single else c for c, asked in ((view_counts, view_stats), (depth_counts, depth_stats)) if asked]
+    return None if not got else got[0] if len(got) == 1 else tuple(got)
 
 
 GROUP_VIEWS = 8                                                     # views per deferred group (= the library's views per launch)
@@ -675,16 +780,18 @@ class _MeshAggregator:
             plane = prepare_labels_device(image, self.classes, (W, H), resize, None if table is not None else m, self.device, table)
         return plane.ptr, (_lib.DEPTH_IMG_LABELS_U8 if plane.dtype == np.uint8 else _lib.DEPTH_IMG_LABELS_U16), plane
 
-    def _fuse_views_gated(self, renderer, cameras, prepare, weights_images, sensors, gate, depth_stats, what):
-        """The gated form of fuse_views / fuse_views_labels: the batch is worked through in chunks of eight views -- the views of a
-        fusion launch; `prepare(i, streams)` gives view i's dense device image as (pointer, image kind, keep-alive), host weights are
+    def _fuse_views_gated(self, renderer, cameras, prepare, weights_images, sensors, gate, depth_stats, what, spec=None, view_stats=False):
+        """The gated / weighted form of fuse_views / fuse_views_labels: the batch is worked through in chunks of eight views -- the views
+        of a fusion launch; `prepare(i, streams)` gives view i's dense device image as (pointer, image kind, keep-alive), host weights are
         copied to the device, and a chunk whose sensor images share size, dtype, strides and memory (and whose images share their kind)
-        is ONE `smesh_fuse_views_depth` call; a mixed chunk goes view by view.  Returns the uint64 [n, 4] counts with `depth_stats`."""
+        is ONE `smesh_fuse_views_depth` call -- with `spec` (a `ViewWeights`) one `smesh_fuse_views_view_weights` call, with or without
+        sensor images; a mixed chunk goes view by view.  Returns (view counts or None, depth counts or None), uint64 [n, 4] each."""
         n = len(cameras)
         counts = np.zeros((n, 4), np.uint64) if depth_stats else None
+        vcounts = np.zeros((n, 4), np.uint64) if view_stats else None
         sensor_streams = []
         # (every sensor image is checked before anything is copied or fused)
-        sdesc = [_describe_sensor(sensors[i], self.device, sensor_streams, "sensor depth image %d" % i) for i in range(n)]
+        sdesc = None if sensors is None else [_describe_sensor(sensors[i], self.device, sensor_streams, "sensor depth image %d" % i) for i in range(n)]
         rh = renderer._h
         for lo in range(0, n, GROUP_VIEWS):
             hi = min(lo + GROUP_VIEWS, n)
@@ -692,14 +799,14 @@ class _MeshAggregator:
             for i in range(lo, hi):
                 W, H = cameras[i].resolution
                 d_img = prepare(i, streams)
-                d_s = sdesc[i]
+                d_s = None if sdesc is None else sdesc[i]
                 wk = (None, None)
                 if weights_images is not None and weights_images[i] is not None:
                     wk = _dense_plane(weights_images[i], W, H, self.device, "weights image %d" % i, streams)
                 views.append((d_img, d_s, wk))
             runs, start = [], 0
             for j in range(1, len(views) + 1):
-                if j == len(views) or views[j][0][1] != views[start][0][1] or views[j][1][1:5] != views[start][1][1:5]:
+                if j == len(views) or views[j][0][1] != views[start][0][1] or (sdesc is not None and views[j][1][1:5] != views[start][1][1:5]):
                     runs.append((start, j))
                     start = j
             if len(runs) > 1:      # a mixed chunk: view by view
@@ -709,20 +816,32 @@ class _MeshAggregator:
                 first_img, first_s = views[a][0], views[a][1]
                 pods = (_lib.CameraPOD * k)(*[cameras[lo + j]._pod for j in range(a, b)])
                 iptr = (ctypes.c_void_p * k)(*[views[j][0][0] for j in range(a, b)])
-                sptr = (ctypes.c_void_p * k)(*[views[j][1][0] for j in range(a, b)])
+                sptr = None if sdesc is None else (ctypes.c_void_p * k)(*[views[j][1][0] for j in range(a, b)])
                 wptr = None
                 if any(views[j][2][0] is not None for j in range(a, b)):
                     wptr = (ctypes.c_void_p * k)(*[views[j][2][0] for j in range(a, b)])
-                pod = gate._pod(first_s[6])
+                pod = None if sdesc is None else gate._pod(first_s[6])
                 cptr = None if counts is None else ctypes.c_void_p(counts.ctypes.data + (lo + a) * 32)
-                _lib.check(_lib.lib().smesh_fuse_views_depth(rh, self._h, pods, k, iptr, first_img[1], wptr, sptr, first_s[3], _c64(first_s[4]),
-                                                             first_s[1], first_s[2][0], first_s[2][1], ctypes.byref(pod), cptr))
+                if spec is None:
+                    _lib.check(_lib.lib().smesh_fuse_views_depth(rh, self._h, pods, k, iptr, first_img[1], wptr, sptr, first_s[3], _c64(first_s[4]),
+                                                                 first_s[1], first_s[2][0], first_s[2][1], ctypes.byref(pod), cptr))
+                    continue
+                vpod = spec._pod()
+                vptr = None if vcounts is None else ctypes.c_void_p(vcounts.ctypes.data + (lo + a) * 32)
+                if sdesc is None:
+                    _lib.check(_lib.lib().smesh_fuse_views_view_weights(rh, self._h, pods, k, iptr, first_img[1], wptr, ctypes.byref(vpod),
+                                                                        None, 0, None, 0, 0, 0, None, vptr, None))
+                else:
+                    _lib.check(_lib.lib().smesh_fuse_views_view_weights(rh, self._h, pods, k, iptr, first_img[1], wptr, ctypes.byref(vpod),
+                                                                        sptr, first_s[3], _c64(first_s[4]), first_s[1], first_s[2][0], first_s[2][1],
+                                                                        ctypes.byref(pod), vptr, cptr))
             release_to(self.device, streams)
-            self._hold([v[0][2] for v in views] + [v[1][5] for v in views if v[1][1] == _lib.MEM_DEVICE] + [v[2][1] for v in views])
+            self._hold([v[0][2] for v in views] + [v[1][5] for v in views if v[1] is not None and v[1][1] == _lib.MEM_DEVICE] + [v[2][1] for v in views])
         release_to(self.device, sensor_streams)
-        return counts
+        return vcounts, counts
 
-    def _fuse_views_probs_gated(self, renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, gate, depth_stats, what):
+    def _fuse_views_probs_gated(self, renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, gate, depth_stats, what,
+                                spec=None, view_stats=False):
         from .resize import resize_mode
         mode = resize_mode(resize)
         cameras, probs_images = list(cameras), list(probs_images)
@@ -733,9 +852,10 @@ class _MeshAggregator:
         def prepare(i, streams):
             W, H = cameras[i].resolution
             return self._gated_probs(probs_images[i], W, H, mode, probs_dtype, streams, "probs image %d" % i)
-        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what)
+        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats)
 
-    def _fuse_views_labels_gated(self, renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors, gate, depth_stats, what):
+    def _fuse_views_labels_gated(self, renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors, gate, depth_stats, what,
+                                 spec=None, view_stats=False):
         label_resize_mode(resize)
         cameras, label_images = list(cameras), list(label_images)
         wts = None if weights_images is None else list(weights_images)
@@ -746,7 +866,7 @@ class _MeshAggregator:
         def prepare(i, streams):
             W, H = cameras[i].resolution
             return self._gated_labels(label_images[i], W, H, resize, m, streams, "label image %d" % i)
-        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what)
+        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats)
 
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
@@ -1032,14 +1152,15 @@ class _MeshAggregator:
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
 
     def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None, palette=None,
-                         sensor_depth=None, depth_gate=None, depth_stats=False):
+                         sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
         """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`,
-        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate` and `depth_stats`)."""
+        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate`, `depth_stats`, `view_weights` and `view_stats`)."""
         sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, False, "fuse_view_labels")
-        if sensors is not None:
+        spec = _view_keywords(renderer, view_weights, view_stats, False, "fuse_view_labels")
+        if sensors is not None or spec is not None:
             stats = self._fuse_views_labels_gated(renderer, [camera], [label_image], None if weights_image is None else [weights_image],
-                                                  resize, label_map, palette, sensors, depth_gate, depth_stats, "fuse_view_labels")
-            return None if stats is None else stats[0]
+                                                  resize, label_map, palette, sensors, depth_gate, depth_stats, "fuse_view_labels", spec, view_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats, single=True)
         mode, m = label_resize_mode(resize), _palette_or_map(palette, label_map, [label_image], self.classes, self.device)
         W, H = camera.resolution
         if m is not None or (mode is not None and self._shape_of(label_image) != (W, H)):
@@ -1107,7 +1228,7 @@ class _MeshAggregator:
             self._hold([d[5] for d, _ in desc] + [dw[1] for _, dw in desc])
 
     def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None, palette=None,
-                          sensor_depths=None, depth_gate=None, depth_stats=False):
+                          sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
         """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
         views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
         and memory go to the library as one batch; a mixed list is fused view by view.  `resize="nearest"` / `label_map` (see
@@ -1115,12 +1236,15 @@ class _MeshAggregator:
         size are prepared and fused by the library in batches of eight.  `palette` (see add_labels): colour images; a `ColorRemap`
         is first updated with all the call's images, in their order -- their distinct colours are found on the device, eight images
         per synchronisation -- and must then hold no more colours than the aggregator has classes.
-        `sensor_depths=`, `depth_gate=`, `depth_stats=`: see fuse_views -- the masks are prepared in chunks of eight, then gated."""
+        `sensor_depths=`, `depth_gate=`, `depth_stats=`, `view_weights=`, `view_stats=`: see fuse_views -- the masks are prepared in
+        chunks of eight, then weighted and gated."""
         cameras = list(cameras)
         sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), False, "fuse_views_labels")
-        if sensors is not None:
-            return self._fuse_views_labels_gated(renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors,
-                                                 depth_gate, depth_stats, "fuse_views_labels")
+        spec = _view_keywords(renderer, view_weights, view_stats, False, "fuse_views_labels")
+        if sensors is not None or spec is not None:
+            stats = self._fuse_views_labels_gated(renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors,
+                                                  depth_gate, depth_stats, "fuse_views_labels", spec, view_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats)
         mode, m = label_resize_mode(resize), check_label_map(label_map)
         cameras, label_images = list(cameras), list(label_images)
         n = len(cameras)
@@ -1343,18 +1467,21 @@ class _MeshAggregator:
         return ModelRenderer(self)
 
     def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False,
-                  sensor_depth=None, depth_gate=None, depth_stats=False):
+                  sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
         """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
         float32, float16 or bfloat16 (see add()); with `resize="bilinear"` any (w,h,C) image add() takes, resampled to the camera's
         resolution on the device first -- or, with `sample_in_kernel=True`, sampled inside the fusion kernel (see add(); one library
         call per view, after the views already deferred).  `sensor_depth=`, `depth_gate=`, `depth_stats=`: the view is gated by its
-        sensor depth (see fuse_views); the views already deferred are handed over first, then this view is a call of its own."""
+        sensor depth (see fuse_views); the views already deferred are handed over first, then this view is a call of its own.
+        `view_weights=`, `view_stats=`: the view is weighted by its viewing geometry (see fuse_views), under the same rule for
+        deferred views."""
         from .resize import resize_mode
         sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, sample_in_kernel, "fuse_view")
-        if sensors is not None:
+        spec = _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, "fuse_view")
+        if sensors is not None or spec is not None:
             stats = self._fuse_views_probs_gated(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
-                                                 probs_dtype, resize, sensors, depth_gate, depth_stats, "fuse_view")
-            return None if stats is None else stats[0]
+                                                 probs_dtype, resize, sensors, depth_gate, depth_stats, "fuse_view", spec, view_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats, single=True)
         smode = self._sampling_mode(resize, sample_in_kernel, "fuse_view")
         if smode is not None:
             return self._fuse_views_sampled(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
@@ -1429,7 +1556,7 @@ class _MeshAggregator:
                 _lib.PROBS_F32 if code is None else code)
 
     def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False,
-                   sensor_depths=None, depth_gate=None, depth_stats=False):
+                   sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
         accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
@@ -1444,13 +1571,22 @@ class _MeshAggregator:
         rendered depth with the sensor's (include/smesh_depth.h) -- the weights are computed on the device between the rasteriser
         and the fusion launch, eight views per launch, multiplied into `weights_images` where given.  The batch is worked through
         in chunks of eight views; host images are copied to the device per chunk.  `depth_stats=True` returns the uint64 [n, 4]
-        counts [visible, far, missing, inconsistent] per view and waits for them.  Not with `sample_in_kernel=True`."""
+        counts [visible, far, missing, inconsistent] per view and waits for them.  Not with `sample_in_kernel=True`.
+        `view_weights=` (a `ViewWeights`): every pixel's contribution is weighted by its viewing geometry -- the cosine of the angle
+        between the pixel's ray and the normal of the face it shows, to an integer power, with a cut-off angle, an optional distance
+        falloff and depth limit (include/smesh_view_weights.h) --, computed on the device from the render's own index and depth
+        planes, eight views per launch, multiplied into `weights_images` where given; triangle renderers only.  It combines with
+        everything the depth keywords combine with and with the depth keywords themselves: the view weights are computed first, the
+        depth gate then gates them.  `view_stats=True` returns the uint64 [n, 4] counts [visible, far, grazing, backfacing] per view
+        and waits for them; with `depth_stats=True` as well the call returns the pair (view counts, depth counts)."""
         from .resize import image_size, resize_mode
         cameras = list(cameras)
         sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), sample_in_kernel, "fuse_views")
-        if sensors is not None:
-            return self._fuse_views_probs_gated(renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, depth_gate,
-                                                depth_stats, "fuse_views")
+        spec = _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, "fuse_views")
+        if sensors is not None or spec is not None:
+            stats = self._fuse_views_probs_gated(renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, depth_gate,
+                                                 depth_stats, "fuse_views", spec, view_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats)
         mode = resize_mode(resize)
         smode = self._sampling_mode(resize, sample_in_kernel, "fuse_views")
         if smode is not None:
