@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/smesh.h"
+#include "records.hpp"
 
 namespace smesh {
 
@@ -95,6 +96,11 @@ bool opt_group_pipeline();
 // renderer and run without a vertex stage (raster.hip: render_group_into; SMESH_RASTER_MESHLETS=0 / 1).
 constexpr int kRasterMeshletsDefault = 1;
 bool opt_raster_meshlets();
+// compact_records (SMESH_COMPACT_RECORDS; default 1): the raster launches of smesh_fuse_view(s) whose records only k_fuse_tri reads
+// (float32 class vectors, triangle renderer in the caller's face order, images of at most 8 192 x 8 192) leave 8-byte records
+// (records.hpp); 0: every launch leaves TriFrag, kernel for kernel what the library did before.  Same results either way.
+constexpr int kCompactRecordsDefault = 1;
+bool opt_compact_records();
 // pipeline_fit (SMESH_PIPELINE_FIT; default 1): the LDS pad that caps the eight-view fusion launch of the group pipeline is computed from
 // the device's LDS and the instance's own (pipeline_fuse_pad below); 0: the constant 24 576 bytes of rounds 2 - 6, kept selectable so that
 // both can be compared in one process.  Same results either way.
@@ -203,6 +209,8 @@ struct TriFuseArgs {
   uint32_t big_capacity;
   uint32_t tri_blocks;        // blocks 0 .. tri_blocks-1 walk the triangles, the next big_blocks the big-triangle queue, the rest (k_fuse_tri with `mid`) the lists of medium triangles
   uint32_t big_blocks;
+  uint32_t compact = 0u;      // k_fuse_tri only, launch-uniform: nonzero = every view's `frags` is the two-plane allocation of records.hpp (8-byte words,
+                              // the TriFrag of kinds 2 and 3 behind them); 0 = [F] TriFrag
   const uint32_t* prim_id;    // [F] primitive id of triangle f when the renderer re-ordered its triangles (null: id == f)
   // texel primitives (k_fuse_texel) only
   const uint32_t* tex_first;  // [F] first texel id of each triangle
@@ -254,6 +262,7 @@ struct RenderedView {
   PipelineNeighbour beside;     // group pipeline: what the renderer's next group runs beside this view's fusion launch (raster.hip; zeros: unknown)
   const void* image = nullptr;  // what stands in for `probs` in the views of k_fuse_tri_labels, k_fuse_tri_h16 and k_fuse_tri_sampled: the dense label
                                 // plane [W][H], the 16-bit image [W][H][C] (strides: ps0, ps1), the network's (w,h,C) image (view_input.hpp)
+  bool compact = false;         // `frags` holds compact records (records.hpp): only smesh_aggregator_fuse_triangles' k_fuse_tri launches read them
 };
 
 // Medium triangles: a bounding box over 8 x 8 pixels of at most kMidBox pixels (16 x 16: beyond that a whole wave per triangle --

@@ -97,7 +97,7 @@ __device__ __forceinline__ void fuse_mid_entries(const TriFuseArgs& a, const Tri
     if (jsel >= 0) {
       const TriView& w = vw.v[jsel];
       e.fi = w.big_queue[(uint64_t)a.big_capacity + qq];
-      e.rec = w.frags[e.fi];
+      e.rec = full_records(a, w.frags)[e.fi];   // (a listed triangle: kind 2 in this view, whose TriFrag exists in either record format)
       e.view = jsel;
     }
     return e;

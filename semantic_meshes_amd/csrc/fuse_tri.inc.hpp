@@ -359,7 +359,48 @@ __device__ __forceinline__ bool mid_box(const TriFrag& rec, uint32_t W, uint32_t
   return w * h <= kMidBox;
 }
 
-template <int CT, int KIND, bool EXACT, int NV>
+// ---- compact records (records.hpp; TriFuseArgs::compact, launch-uniform): a view's `frags` is then [F] 8-byte words with the TriFrag of
+// the triangles of kinds 2 and 3 in a second plane behind them.
+__device__ __forceinline__ const TriFrag* full_records(const TriFuseArgs& a, const TriFrag* __restrict__ frags) {
+  return a.compact ? reinterpret_cast<const TriFrag*>(reinterpret_cast<const char*>(frags) + rec_full_offset(a.F)) : frags;
+}
+// Triangle f's record of one view as a TriFrag, whatever the launch's format (a kind-3 word comes back as the kind-1 TriFrag it points at).
+// FORMAT: 0 = the launch's records are TriFrag, 1 = compact, 2 = ask a.compact (see k_fuse_tri: which instances do which).
+template <int FORMAT>
+__device__ __forceinline__ TriFrag load_record(const TriFuseArgs& a, const TriFrag* __restrict__ frags, const uint32_t f) {
+  if (FORMAT == 0 || (FORMAT == 2 && !a.compact)) return frags[f];
+  const unsigned long long w = reinterpret_cast<const unsigned long long*>(frags)[f];
+  const uint32_t kind = rec_kind(w);
+  if (kind >= 2u) return full_records(a, frags)[f];
+  TriFrag r;
+  r.x0 = (uint16_t)rec_x0(w); r.y0 = (uint16_t)rec_y0(w); r.kind = (uint16_t)kind; r.pad = 0;
+  r.mask = kind == 1u ? rec_word_mask64(w) : 0ull;
+  return r;
+}
+// What the main waves' prologue wants of triangle f in every view of a compact launch (k_fuse_tri: org, msk, big, large): the NV words
+// are requested together; the few triangles of kinds 2 and 3 then make a second, divergent load of their TriFrag.  The masks are
+// expanded to TriFrag's bit order once, here, so that the pixel walk stays what it is.
+template <int NV, bool MIDK>
+__device__ __forceinline__ void load_compact_views(const TriFuseArgs& a, const TriViews<NV>& vw, const uint64_t f, uint32_t (&org)[NV],
+                                                   unsigned long long (&msk)[NV], bool& big, bool& large) {
+#pragma unroll
+  for (int v = 0; v < NV; v++) msk[v] = reinterpret_cast<const unsigned long long*>(vw.v[v].frags)[f];   // (the words, requested together)
+#pragma unroll
+  for (int v = 0; v < NV; v++) {
+    const unsigned long long w = msk[v];
+    const uint32_t kind = rec_kind(w);
+    org[v] = rec_x0(w) | (rec_y0(w) << 16);
+    msk[v] = kind == 1u ? rec_word_mask64(w) : 0ull;
+    if (kind >= 2u) {
+      const TriFrag rec = full_records(a, vw.v[v].frags)[f];
+      msk[v] = rec.kind == 1 ? rec.mask : 0ull;
+      big = big || rec.kind == 2;
+      large = large || (rec.kind == 2 && !(MIDK && a.mid && mid_box(rec, 0u, 0u)));
+    }
+  }
+}
+
+template <int CT, int KIND, bool EXACT, int NV, int FORMAT>
 __device__ __forceinline__ void fuse_big_triangles(const TriFuseArgs& a, const TriViews<NV>& vw, uint32_t worker, uint32_t nworkers,
                                                    uint32_t* __restrict__ lds_list) {
   uint32_t len[NV], total = 0u;
@@ -400,7 +441,7 @@ __device__ __forceinline__ void fuse_big_triangles(const TriFuseArgs& a, const T
 #pragma unroll
         for (int i = 0; i < NV; i++) {
           if (i <= jsel) {
-            const TriFrag rec = vw.v[i].frags[fi];
+            const TriFrag rec = load_record<FORMAT>(a, vw.v[i].frags, fi);
             const bool counts = rec.kind == 2 && !(a.mid && mid_box(rec, vw.v[i].W, vw.v[i].H));
             if (i < jsel) earlier = earlier || counts;
             else mine = counts;
@@ -417,7 +458,7 @@ __device__ __forceinline__ void fuse_big_triangles(const TriFuseArgs& a, const T
       const uint32_t f = a.prim_id ? a.prim_id[fq] : fq;        // primitive id = value in the index image = accumulator row
 #pragma unroll
       for (int j = 0; j < NV; j++) {
-        const TriFrag rec = vw.v[j].frags[fq];
+        const TriFrag rec = load_record<FORMAT>(a, vw.v[j].frags, fq);
         if (rec.kind == 0 || (a.mid && rec.kind == 2 && mid_box(rec, 0u, 0u))) continue;   // (a medium view: fuse_mid_entries')
         const TriFuseArgs x = with_view(a, vw.v[j]);
         int x1, y1;
@@ -457,7 +498,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(fuse_tri_
     const uint32_t tail = blockIdx.x - a.tri_blocks;
     if (tail < a.big_blocks) {
       uint32_t* lds_list = reinterpret_cast<uint32_t*>(srow);   // the tail waves have no use for the row block: >= 64 entries
-      fuse_big_triangles<CT, KIND, EXACT, NV>(a, vw, tail, a.big_blocks, lds_list);
+      // (the record format, by the register report -- profiles/compact_records_regs_*.txt: the instances with a stated budget take a
+      // launch-uniform branch to one of two copies of the tail code -- the flag tested inside it cost the two-view Summax instance
+      // for 19 classes eight spilled registers; every other instance tests the flag where it loads a record -- two copies cost the
+      // 5-class instances a wave per SIMD in spilled scalars)
+      if constexpr (fuse_tri_min_waves(CT, KIND, NV) > 1) {
+        if (a.compact) fuse_big_triangles<CT, KIND, EXACT, NV, 1>(a, vw, tail, a.big_blocks, lds_list);
+        else fuse_big_triangles<CT, KIND, EXACT, NV, 0>(a, vw, tail, a.big_blocks, lds_list);
+      } else {
+        fuse_big_triangles<CT, KIND, EXACT, NV, 2>(a, vw, tail, a.big_blocks, lds_list);
+      }
     } else if constexpr (KIND != SMESH_AGG_MUL) {
       constexpr int MCT = (CT + 7) / 8 * 8;                     // class-vector register slots of the medium-triangle code: 8, 16 .. 48
       fuse_mid_entries<MCT, KIND, NV>(a, vw, tail - a.big_blocks, gridDim.x - a.tri_blocks - a.big_blocks, (lds_u16*)srow);
@@ -476,7 +526,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(fuse_tri_
   bool big = false, large = false;
 #pragma unroll
   for (int v = 0; v < NV; v++) { org[v] = 0u; msk[v] = 0ull; }
-  if (f < a.F) {
+  if (f < a.F && a.compact) {
+    load_compact_views<NV, KIND != SMESH_AGG_MUL>(a, vw, f, org, msk, big, large);
+  } else if (f < a.F) {
 #pragma unroll
     for (int v = 0; v < NV; v++) {
       const TriFrag rec = vw.v[v].frags[f];

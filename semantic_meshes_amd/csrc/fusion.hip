@@ -2437,6 +2437,11 @@ bool smesh_aggregator_fuses_small_views_by_mask(smesh_aggregator* a) {
   return a->C <= 40u || (a->C <= (uint32_t)kFuseTriMaxC && a->kind == SMESH_AGG_MUL && smesh_aggregator_max_fused_views(a) <= 2);
 }
 
+// May the rasteriser leave this aggregator's fuse_view(s) launches compact records (records.hpp)?  Only k_fuse_tri, fuse_big_triangles
+// and fuse_mid_entries read them: where EVERY triangle-order launch of float32 views is k_fuse_tri -- the same class counts that let each
+// view decide on its own plane.  raster.hip asks per raster launch (compact_records_wanted).
+bool smesh_aggregator_reads_compact_records(smesh_aggregator* a) { return smesh_aggregator_fuses_small_views_by_mask(a); }
+
 // Can the triangle-order fusion of this aggregator read class vectors in place at element strides (ps0, ps1, 1) -- the (H,W,C)
 // output of a network seen as (W,H,C), colorize_cityscapes_mesh.py:65-67 -- instead of a gathered copy?  k_fuse_tri (C <= 48)
 // addresses every pixel's vector on its own; the wide-row kernels keep their dense layout.
@@ -2533,6 +2538,11 @@ int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint3
     else tri_ct = a->C <= 8 ? 8 : a->C <= 16 ? 16 : a->C <= 24 ? 24 : a->C <= 32 ? 32 : a->C <= 40 ? 41 : 48;
   }
   const bool specialised = tri_ct != 0;
+  // compact records: one format per launch, and only k_fuse_tri knows it (raster.hip decides with smesh_aggregator_reads_compact_records)
+  t.compact = views[0].compact ? 1u : 0u;
+  for (int v = 1; v < nviews; v++)
+    if (views[v].compact != views[0].compact) return fail(SMESH_ERR_INVALID, "fuse_triangles: views with different record formats in one launch");
+  if (t.compact && (!specialised || prim_id)) return fail(SMESH_ERR_INVALID, "fuse_triangles: compact records need k_fuse_tri and the caller's face order");
   float* pw = nullptr;
   uint32_t* amax = nullptr;
   uint64_t scratch_stride = N;   // per-view scratch images of the big-triangle waves

@@ -47,6 +47,7 @@ int smesh_aggregator_max_fused_views(smesh_aggregator* a);
 bool smesh_aggregator_takes_strided_probs(smesh_aggregator* a, int64_t ps0, int64_t ps1, int nviews);
 int smesh_aggregator_dense_probs(smesh_aggregator* a, const float* d_probs, const int64_t ps[3], uint64_t W, uint64_t H, const float** out);
 bool smesh_aggregator_fuses_small_views_by_mask(smesh_aggregator* a);
+bool smesh_aggregator_reads_compact_records(smesh_aggregator* a);
 int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint32_t* prim_id, uint32_t big_capacity,
                                     const RenderedView* views, int nviews, int part = 0, int nparts = 1);
 void smesh_fuse_part_rows(uint64_t F, int part, int nparts, uint64_t* f_lo, uint64_t* f_hi);
@@ -299,6 +300,8 @@ struct RasterArgs {
   uint32_t* big_count;        // [0] length of big_queue, [2] length of huge_queue, [1] nonzero: the masks of the per-triangle
                               //     records still hold fragments that lost the depth test (the fusion must check them)
   uint32_t big_capacity;
+  uint32_t compact;           // launch-uniform: nonzero = `frags` takes compact records (records.hpp): an 8-byte word per triangle, and behind
+                              // the words (full_records) the TriFrag of the triangles of kinds 2 and 3 only
   TriFrag* frags;             // per-triangle fragment records for the triangle-order fusion (may be null)
   uint8_t* kinds;             // texel renderers: the records' `kind`, a byte per triangle -- the fusion finds the one triangle in eight that
                               // emitted anything from these instead of from sixteen bytes per triangle and view, and a record is
@@ -326,6 +329,20 @@ struct RasterArgs {
 // Key image layout: same (W,H) y-fastest order as the output planes.  (A 4 x 4 blocked layout was tried to
 // make neighbouring fragments share cache lines: no change in k_raster_small, slower resolve.)
 __device__ __forceinline__ uint64_t key_index(uint32_t x, uint32_t y, uint32_t H) { return (uint64_t)x * H + y; }
+
+// Where the TriFrag of triangle f lies: in `frags` itself, or (compact records) in the plane behind the 8-byte words.
+__device__ __forceinline__ TriFrag* full_records(const RasterArgs& a) {
+  return a.compact ? reinterpret_cast<TriFrag*>(reinterpret_cast<char*>(a.frags) + rec_full_offset(a.F)) : a.frags;
+}
+__device__ __forceinline__ unsigned long long* record_words(const RasterArgs& a) { return reinterpret_cast<unsigned long long*>(a.frags); }
+
+// The owner lane's store of a compact record: the word, and the TriFrag as well where the word cannot hold it (kinds 2 and 3).
+// `wide`: a small triangle's box measures 7 or 8 pixels in x or y.
+__device__ __forceinline__ void store_compact_record(const RasterArgs& a, const uint64_t f, const TriFrag& rec, const bool wide) {
+  const uint32_t kind = rec_kind_of(rec.kind, wide ? 8 : 1, 1);
+  record_words(a)[f] = rec_pack(rec.x0, rec.y0, kind, rec.mask);
+  if (kind >= 2u) full_records(a)[f] = rec;
+}
 
 // Projected vertex i of the view.  A grouped launch that reads meshlets (k_raster_frag_group_ml) has no vertex stage and leaves a.sv null:
 // the few triangles its OTHER kernels handle (the queued ones: raster_huge_block, load_piece) project their vertices on the spot --
@@ -873,8 +890,9 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
   const int lane = threadIdx.x & 63;
   const int part = kSpreadMode ? part_in : -1;
   const bool owner = part <= 0 && !listed;    // (listed: a triangle from the view's list, k_raster_medium -- its owner lane left its record and queue entries)
-  TriFrag rec;
-  rec.x0 = 0; rec.y0 = 0; rec.kind = 0; rec.pad = 0; rec.mask = 0ull;
+  // (the triangle's record is put together where it is stored, from `t` and these two flags: held in registers of its own from here
+  // on, it cost the meshlet instance the registers of its sixth wave per SIMD once the store had two formats)
+  bool placed = false, boxed = false;     // the triangle has a screen box; TriFrag kind 2: box over 8 x 8, or near-plane crossing
   Tri t;
   t.x0 = 0; t.y0 = 0; t.x1 = -1; t.y1 = -1;
   unsigned long long cover = 0ull;
@@ -887,13 +905,12 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
   else { if (f < a.F) have = load_tri_ex<NULLABLE_SV>(a, f, t, i0, i1, i2); }
   if (have) {
     const int bw = t.x1 - t.x0 + 1, bh = t.y1 - t.y0 + 1;
-    rec.x0 = (uint16_t)t.x0; rec.y0 = (uint16_t)t.y0;
+    placed = true;
     CX0 = t.x0; CY0 = t.y0;
     if (bw > 8 || bh > 8 || have == 2) {
       q_big = owner;                                             // every such triangle: the fusion walks this queue
       q_mid = owner && bw * bh <= kMidBox;                       // (push_mid's list)
-      rec.kind = 2;
-      rec.mask = (unsigned long long)(uint32_t)t.x1 | ((unsigned long long)(uint32_t)t.y1 << 16);
+      boxed = true;
       if (bw <= kLaneBox && bh <= kLaneBox && have == 1) {       // rasterised by lanes, sub-box by sub-box
         if (part < 0) lanebox = true;                            // ... this lane, one sub-box per round (below)
         else {                                                   // ... the triangle's kSpread lanes, one sub-box each, now
@@ -966,14 +983,23 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
   }
   {
     const unsigned long long mask = emit_cover<kTex>(a, t, f, pid, CX0, CY0, cover, sub);
-    if (mask && small) rec.kind = 1;
-    if (rec.kind == 1) rec.mask = mask;
+    small = small && mask != 0ull;      // from here on: TriFrag kind 1
+    cover = mask;
   }
   if (owner) {
+    TriFrag rec;
+    rec.x0 = placed ? (uint16_t)t.x0 : (uint16_t)0; rec.y0 = placed ? (uint16_t)t.y0 : (uint16_t)0; rec.pad = 0;
+    rec.kind = boxed ? 2 : (small ? 1 : 0);
+    rec.mask = boxed ? ((unsigned long long)(uint32_t)t.x1 | ((unsigned long long)(uint32_t)t.y1 << 16)) : (small ? cover : 0ull);
+    const bool wide = small && (t.x1 - t.x0 >= kRecBox || t.y1 - t.y0 >= kRecBox);   // (compact records: the mask of such a box does not fit the word)
     // texel renderers (a.kinds): seven triangles in eight emit nothing in a cfg4 view -- those leave their kind byte only, and every
     // reader of a texel renderer's records asks the byte first (cfg4: 5 050 -> 5 210 views/s)
-    if (a.frags && f < a.F && (rec.kind != 0 || !a.kinds)) a.frags[f] = rec;
-    if (a.kinds && f < a.F) a.kinds[f] = (uint8_t)rec.kind;
+    if (a.compact) {      // (launch-uniform; the host sets it only for triangle primitives with records: a.frags, no a.kinds)
+      if (f < a.F) store_compact_record(a, f, rec, wide);
+    } else {
+      if (a.frags && f < a.F && (rec.kind != 0 || !a.kinds)) a.frags[f] = rec;
+      if (a.kinds && f < a.F) a.kinds[f] = (uint8_t)rec.kind;
+    }
   }
   // ---- boxes over 8 x 8 up to kLaneBox x kLaneBox: this lane's sub-boxes, one per round (wave-uniform trip count) -- where the wave
   // holds enough of them: a round costs what a whole small-triangle pass costs (~2 200 instructions) however many lanes take part,
@@ -1260,7 +1286,7 @@ __device__ __forceinline__ void raster_huge_block(const RasterArgs& a, const uin
     const uint32_t qi = qb + (uint32_t)t;
     if (qi < nbig) {
       const uint32_t f = a.huge_queue[qi];
-      const TriFrag rec = a.frags[f];
+      const TriFrag rec = full_records(a)[f];   // (a queued triangle: kind 2, whose TriFrag exists in either format)
       const int bx1 = (int)(rec.mask & 0xFFFFu), by1 = (int)((rec.mask >> 16) & 0xFFFFu);
       if (rec.kind == 2 && (int)rec.x0 <= tx1 && bx1 >= (int)x0 && (int)rec.y0 <= ty1 && by1 >= (int)y0)
         s_hits[atomicAdd(&s_nhits, 1u)] = f;
@@ -1389,10 +1415,22 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
       auto lost = [&](const unsigned long long key, const uint32_t pin) {
         if (key == kNullKey || skeys[pin] == key) return;
         const uint32_t f = (uint32_t)(key & 0xFFFFFFFFull);
-        const TriFrag rec = a.frags[f];
+        TriFrag* __restrict__ full = a.frags;
+        if (a.compact) {             // (launch-uniform) the 8-byte word: kind 1 holds the mask itself, kind 3 points at the TriFrag behind the words
+          const unsigned long long w = record_words(a)[f];
+          const uint32_t kind = rec_kind(w);
+          if (kind == 1u) {
+            const int bit = rec_bit((int)(x0 + (pin >> 6) - rec_x0(w)), (int)(y0 + (pin & 63u) - rec_y0(w)));
+            atomicAnd(&record_words(a)[f], ~(1ull << bit));
+            return;
+          }
+          if (kind != 3u) return;
+          full = full_records(a);
+        }
+        const TriFrag rec = full[f];
         if (rec.kind != 1) return;   // (fragments of triangles with a box over 8 x 8: their record holds the box, not a mask)
         const int bit = (int)(x0 + (pin >> 6) - rec.x0) * 8 + (int)(y0 + (pin & 63u) - rec.y0);
-        atomicAnd(&a.frags[f].mask, ~(1ull << bit));
+        atomicAnd(&full[f].mask, ~(1ull << bit));
       };
 #pragma unroll
       for (uint32_t k = 0; k < kSpec; k++)
@@ -1583,7 +1621,8 @@ struct smesh_renderer {
   struct Side {
     uint32_t* big_queue = nullptr;   // [big_capacity] triangles with a bounding box > 8 x 8
     uint32_t* big_count = nullptr;   // [0] length of the queue; emptied by the next render's vertex kernel
-    TriFrag* frags = nullptr;        // [F] per-triangle fragment records
+    TriFrag* frags = nullptr;        // [F] per-triangle fragment records; or (compact) [F] 8-byte words and the TriFrag plane behind them (records.hpp: rec_alloc_bytes)
+    bool compact = false;            // which of the two the last render into this side left
     uint8_t* kinds = nullptr;        // [F] texel renderers: TriFrag::kind, a byte per triangle
   } side[kSides];
   uint32_t big_capacity = 0;
@@ -1716,6 +1755,18 @@ int plane_optional_level(smesh_renderer* r, smesh_aggregator* a) {
   return smesh_aggregator_fuses_small_views_by_mask(a) ? 2 : 1;
 }
 
+// Does a fuse_view(s) raster launch of these `n` views for FLOAT32 class vectors leave compact records (records.hpp)?  Decided where
+// the plane level is: only when every reader of the records is of the k_fuse_tri family (the aggregator says so), the tile resolve
+// clears the losers itself (plane_optional_allowed: triangle primitives in the caller's face order, fragment-queue path), and every
+// view of the launch fits the 13-bit box origin.  Option "compact_records" 0: never.
+bool compact_records_wanted(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, int n) {
+  if (!opt_compact_records() || !plane_optional_allowed(r) || plane_optional_level(r, a) != 2 || !smesh_aggregator_reads_compact_records(a)) return false;
+  for (int v = 0; v < n; v++)
+    if (!rec_image_fits(cams[v].width, cams[v].height)) return false;
+  return true;
+}
+thread_local int g_last_record_format = 16;   // smesh_last_record_format()
+
 // Consecutive triangle blocks per run of an XCD (xcd_block) in launches of 64 blocks and more (smaller ones: blocks take consecutive
 // triangles in dispatch order).  cfg2, eight views per launch (profiles/r06_raster_experiments.txt): k_raster_frag_group fetches
 // 149.6 MB in dispatch order, 79.1 MB with runs of 8 (x 2: gfx950's FETCH_SIZE unit) -- 562 -> 422 MB of traffic per launch -- and takes
@@ -1830,6 +1881,7 @@ RasterArgs raster_args(smesh_renderer* r, smesh_renderer::ViewScratch& vs, int s
     a.balance = (vs.med_queue && (knob >= 0 ? knob != 0 : (cam && depth_spread(r, cam) > 6.0))) ? (nviews > 1 ? 1u : 2u) : 0u;
   }
   a.frags = r->side[side].frags;
+  a.compact = 0u;
   a.kinds = r->side[side].kinds;
   a.q = FragQueues();
   a.idx_optional = 0u;
@@ -1864,9 +1916,11 @@ uint32_t frag_groups(uint64_t F, int views, uint32_t tpw) {
 }
 
 int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, float* d_depth, hipStream_t st = nullptr,
-                int side = 0, int idx_optional = 0) {
+                int side = 0, int idx_optional = 0, bool compact = false) {
   DeviceCtx* ctx = r->ctx;
   r->last_render_side = side;
+  r->side[side].compact = false;
+  g_last_record_format = 16;
   if (!st) {
     // plain render()/render_device(): main stream, after whatever smesh_fuse_view left on the raster stream
     st = ctx->stream;
@@ -1893,6 +1947,11 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
     int qs = SMESH_OK;
     if (raster_path() == RasterPath::Frag && ensure_queues(r, vs, W, H, st, &qs)) {
       a.q = vs.fq;
+      if (compact && a.idx_optional == 2u && a.frags && !a.kinds) {   // (only the fragment-queue kernels know the format)
+        a.compact = 1u;
+        r->side[side].compact = true;
+        g_last_record_format = 8;
+      }
       {
         const uint32_t nblocks = (uint32_t)div_up(div_up(r->F, a.tpw), 4);
         const uint32_t chunk = nblocks >= 64u ? kRasterXcdRun : 0u;
@@ -2003,9 +2062,11 @@ int prepare_group_slots(smesh_renderer* r, const smesh_camera_t* cams, int n, hi
 // `side_base`: where the records and index planes go (side[side_base + v], fused[side_base + v]) when that is not the view slots'
 // own set (held views: the rasteriser scratch of slots base .. base + n - 1 is free again after the launches, the records stay).
 int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipStream_t st, int base = 0, int side_base = -1,
-                      int idx_optional = 0, bool with_depth = false) {
+                      int idx_optional = 0, bool with_depth = false, bool compact = false) {
   if (side_base < 0) side_base = base;
   if (!plane_optional_allowed(r) || with_depth) idx_optional = 0;
+  compact = compact && idx_optional == 2 && !r->texels;
+  g_last_record_format = compact ? 8 : 16;
   DeviceCtx* ctx = r->ctx;
   ProjectGroup pg;
   RasterGroup rg;
@@ -2034,6 +2095,8 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
     rg.view[v].cam = pg.cam[v];
     rg.view[v].q = vs.fq;
     rg.view[v].idx_optional = (uint32_t)idx_optional;
+    rg.view[v].compact = compact ? 1u : 0u;
+    r->side[side_base + v].compact = compact;
     rg.idx[v] = static_cast<uint32_t*>(r->fused[side_base + v].ptr);
     tiles += (uint32_t)(div_up(W, kQW) * div_up(H, kQH));
     rg.tile_end[v] = tiles;
@@ -2151,7 +2214,8 @@ hipError_t alloc_side(smesh_renderer* r, int i) {
   if (sd.frags) return hipSuccess;
   hipError_t e = dev_malloc(reinterpret_cast<void**>(&sd.big_queue), (size_t)r->big_capacity * 8);   // (upper half: the medium triangles again, push_mid)
   if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&sd.big_count), 32);
-  if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&sd.frags), std::max<uint64_t>(r->F * sizeof(TriFrag), 16));
+  // (room for either format: [F] TriFrag, or the 8-byte words with the TriFrag plane behind them)
+  if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&sd.frags), std::max<uint64_t>(r->texels ? r->F * sizeof(TriFrag) : rec_alloc_bytes(r->F), 16));
   if (e == hipSuccess && r->texels) e = dev_malloc(reinterpret_cast<void**>(&sd.kinds), std::max<uint64_t>(r->F, 16));
   if (e == hipSuccess) e = hipMemsetAsync(sd.big_count, 0, 32, r->ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(r->ctx->stream);
@@ -2391,6 +2455,7 @@ static RenderedView rendered_view(const smesh_renderer::Side& sd, const uint32_t
                                   bool mid_queue) {
   RenderedView rv{sd.frags, sd.big_queue, sd.big_count, d_idx, in.probs(), d_w, W, H, in.ps0, in.ps1, mid_queue};
   if (in.kind != ViewInput::F32) rv.image = in.image;
+  rv.compact = sd.compact;
   return rv;
 }
 
@@ -2457,7 +2522,8 @@ static int fuse_rendered(smesh_renderer* r, smesh_aggregator* a, int slot, const
   if (!r->texels && smesh_aggregator_can_fuse_triangles(a, r->F)) {
     // triangle primitives: every accumulator row is owned by its triangle's lane -- no atomics, no histogram
     // (ps0, ps1: DEVICE class vectors with element strides (ps0, ps1, 1), read in place by k_fuse_tri; 0, 0: the dense image)
-    const RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, d_probs, d_w, W, H, ps0, ps1, true};
+    RenderedView rv{r->side[slot].frags, r->side[slot].big_queue, r->side[slot].big_count, d_idx, d_probs, d_w, W, H, ps0, ps1, true};
+    rv.compact = r->side[slot].compact;
     SMESH_TRY(smesh_aggregator_fuse_triangles(a, r->F, r->prim_id, r->big_capacity, &rv, 1));
     smesh_note_fuse(smesh_aggregator_fuse_kernel_name(a, r->prim_id != nullptr), "render-records");
   } else if (r->texels && smesh_aggregator_can_fuse_texels(a, r->num_primitives)) {
@@ -2476,6 +2542,9 @@ extern "C" {
 const char* smesh_last_fuse_kernel(void) { return g_last_fuse_kernel; }
 const char* smesh_last_add_path(void) { return g_last_add_path; }
 const char* smesh_last_raster_path(void) { return g_last_raster_path; }
+}
+int smesh_last_record_format() { return g_last_record_format; }
+extern "C" {
 
 int smesh_renderer_create_triangles(const float* vertices, uint64_t V, const int32_t* faces, uint64_t F, int device,
                                     smesh_renderer_t** out) {
@@ -2741,7 +2810,9 @@ static int fuse_view_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const smes
   // (a label view: k_fuse_tri_labels follows the raster launch, or -- labels expanded -- the class-vector kernels as ever)
   // (16-bit class vectors: k_fuse_tri_h16 follows and takes the label kernel's level, see scans_all_planes)
   const int tri_path = scans_all_planes(r, a, in.kind, N) ? kLabelsPlaneLevel : plane_optional_level(r, a);
-  SMESH_TRY(render_into(r, cam, d_idx, /*d_depth=*/nullptr, ctx->stream, slot, tri_path));
+  // (float32 class vectors into k_fuse_tri: 8-byte records; every other image kind, expanded or not, keeps TriFrag)
+  const bool compact = in.kind == ViewInput::F32 && tri_path == 2 && compact_records_wanted(r, a, cam, 1);
+  SMESH_TRY(render_into(r, cam, d_idx, /*d_depth=*/nullptr, ctx->stream, slot, tri_path, compact));
   SMESH_TRY(fuse_rendered(r, a, slot, d_idx, in, weights, memkind, W, H));
   r->fused_seq++;
   return SMESH_OK;
@@ -2813,6 +2884,8 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
     // (+2 %): k_fuse_tri stretches from 83 to 95 us per pair launch and the rasteriser stage from 35 to ~70 us per view while they
     // share the CUs -- both are bound by how many of their waves a CU holds (96 / 126 VGPRs), not by two different units.
     const bool group_pipeline = group_pipeline_on;
+    // (one record format per raster launch: the group's fusion launches read all its views alike)
+    const bool compact = grouped && !own_kernel && tri_path == 2 && compact_records_wanted(r, a, &cams[i], gn);
     int base = 0;
     if (use_pipeline) {
       const int bank = (int)(r->group_seq++ & 1u);
@@ -2832,13 +2905,13 @@ static int fuse_views_impl(smesh_renderer_t* r, smesh_aggregator_t* a, const sme
         r->main_pending = false;
       }
       if (!r->bank_used[bank ^ 1]) SMESH_TRY(prepare_group_slots(r, &cams[i], gn, ctx->raster_stream, (bank ^ 1) * kMaxGroup));
-      SMESH_TRY(render_group_into(r, &cams[i], gn, ctx->raster_stream, base, -1, tri_path));
+      SMESH_TRY(render_group_into(r, &cams[i], gn, ctx->raster_stream, base, -1, tri_path, /*with_depth=*/false, compact));
       SMESH_HIP(hipEventRecord(r->ev_bank_rendered[bank], ctx->raster_stream));
       SMESH_HIP(hipStreamWaitEvent(ctx->stream, r->ev_bank_rendered[bank], 0));
       r->bank_used[bank] = true;
       r->raster_pending = true;
     } else if (grouped) {
-      SMESH_TRY(render_group_into(r, &cams[i], gn, ctx->stream, 0, -1, tri_path));
+      SMESH_TRY(render_group_into(r, &cams[i], gn, ctx->stream, 0, -1, tri_path, /*with_depth=*/false, compact));
     } else {   // images too large for kMaxGroup sets of fragment queues, direct rasteriser, or SMESH_RASTER_PAIRS=0: one view at a time
       gn = 2;
       SMESH_HIP(alloc_side(r, 1));
