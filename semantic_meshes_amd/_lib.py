@@ -308,6 +308,24 @@ VIEW_WEIGHTS_SIGNATURES = {
                                               P(c_void_p), c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(DepthGatePOD), c_void_p, c_void_p]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_edge_gate.h: fusion gated at occlusion edges from the
+# rendered depth plane, product-only like the tables above (no profile slot; image kinds and sensor arguments are those of smesh_depth.h)
+EDGE_MAX_RADIUS = 8                                                 # SMESH_EDGE_MAX_RADIUS
+EDGE_TILE_X, EDGE_TILE_Y = 32, 64                                   # SMESH_EDGE_TILE_X / _Y: the tile of one workgroup of k_edge_weights
+
+
+class EdgeGatePOD(ctypes.Structure):
+    """smesh_edge_gate_t (include/smesh_edge_gate.h)."""
+    _fields_ = [("radius", ctypes.c_int32), ("abs_tol", c_float), ("rel_tol", c_float), ("behind", ctypes.c_int32), ("front", ctypes.c_int32),
+                ("silhouette", ctypes.c_int32)]
+
+
+EDGE_GATE_SIGNATURES = {
+    "smesh_edge_weights": (c_int, [c_void_p, c_u64, c_u64, P(EdgeGatePOD), c_void_p, c_void_p, c_void_p, c_int]),
+    "smesh_fuse_views_weighted": (c_int, [c_void_p, c_void_p, P(CameraPOD), c_u64, P(c_void_p), c_int, P(c_void_p), P(ViewWeightsPOD), P(EdgeGatePOD),
+                                          P(c_void_p), c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(DepthGatePOD), c_void_p, c_void_p, c_void_p]),
+}
+
 # name -> (restype, argtypes); one entry per symbol declared in include/smesh_face_graph.h: the faces across every face's edges and the
 # propagation of fused rows over them, product-only like the tables above (no profile slot; the output modes are SMESH_VTX_*)
 FG_SMOOTH, FG_FILL = 0, 1                                           # SMESH_FG_*
@@ -463,7 +481,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(EDGE_GATE_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

@@ -49,6 +49,7 @@ uint64_t smesh_label_prep_launches();      // label_prep.hip
 uint64_t smesh_label_colors_launches();    // label_colors.hip
 uint64_t smesh_depth_weights_launches();   // depth_weights.hip
 uint64_t smesh_view_weights_launches();    // view_weights.hip
+uint64_t smesh_edge_weights_launches();    // edge_weights.hip
 
 // "fuse_sampled" (fusion_sampled.hip): 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- a test hook, like
 // SMESH_FUSE_H16=0.  -1: not set by smesh_set_option -- the environment's SMESH_FUSE_SAMPLED, read at every call, else on.
@@ -447,6 +448,7 @@ int smesh_get_option(const char* name, int64_t* value) {
   // read-only (smesh_depth.h): this process's launches of k_depth_weights
   if (!strcmp(name, "depth_weights_launches")) { *value = (int64_t)smesh_depth_weights_launches(); return SMESH_OK; }
   if (!strcmp(name, "view_weights_launches")) { *value = (int64_t)smesh_view_weights_launches(); return SMESH_OK; }
+  if (!strcmp(name, "edge_weights_launches")) { *value = (int64_t)smesh_edge_weights_launches(); return SMESH_OK; }
   // read-only (smesh_probs_labels.h): the largest class count the tiled path serves
   if (!strcmp(name, "probs_labels_tile_max_classes")) { *value = (int64_t)kProbsLabelsTileMaxC; return SMESH_OK; }
   // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --

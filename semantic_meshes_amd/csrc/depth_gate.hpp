@@ -1,5 +1,5 @@
-// depth_gate.hpp -- what raster.hip's gated view driver, depth_weights.hip (include/smesh_depth.h) and view_weights.hip
-// (include/smesh_view_weights.h) share.
+// depth_gate.hpp -- what raster.hip's gated view driver, depth_weights.hip (include/smesh_depth.h), view_weights.hip
+// (include/smesh_view_weights.h) and edge_weights.hip (include/smesh_edge_gate.h) share.
 #pragma once
 
 #include <functional>
@@ -12,11 +12,11 @@
 namespace smesh {
 
 // Device scratch of the gated entry points, owned by the renderer: the weights planes of a group of views, the staged host sensor
-// images of that group, and the group's counts (the depth gate's; the view weights').  Everything that writes or reads them is ordered
-// on the context's main stream.
+// images of that group, and the group's counts (the depth gate's; the view weights'; the edge gate's).  Everything that writes or
+// reads them is ordered on the context's main stream.
 struct DepthScratch {
-  Scratch w, sensor, counts, view_counts;
-  void release() { w.release(); sensor.release(); counts.release(); view_counts.release(); }
+  Scratch w, sensor, counts, view_counts, edge_counts;
+  void release() { w.release(); sensor.release(); counts.release(); view_counts.release(); edge_counts.release(); }
 };
 
 // One view of a group between the rasteriser and the fusion launch: its depth plane, the caller's weights (or null) and the plane the
@@ -77,3 +77,13 @@ int smesh_renderer_fuse_views_gated(smesh_renderer* r, smesh_aggregator* a, cons
                                     const void* const* images, const float* const* weights, const smesh::GateFn& gate);
 // raster.hip
 int smesh_renderer_mesh(smesh_renderer* r, smesh::RendererMesh* out);
+
+struct smesh_view_weights_spec;
+namespace smesh {
+// view_weights.hip, for callers that run another stage behind the view weights (edge_weights.hip).
+// What every entry point of smesh_view_weights.h refuses about the spec and the renderer; fills `mesh`.
+int view_weights_check(smesh_renderer* r, const smesh_view_weights_spec* spec, RendererMesh* mesh);
+// k_view_weights for a group of m views; `counts_host`: [m][4] or null (asking makes the call wait).
+int view_weights_group(DeviceCtx* ctx, const RendererMesh& mesh, DepthScratch& scratch, const GatedView* views, int m,
+                       const smesh_view_weights_spec& spec, uint64_t* counts_host);
+}  // namespace smesh

@@ -264,6 +264,17 @@ int weigh_group(DeviceCtx* ctx, const RendererMesh& mesh, Scratch& counts_scratc
 // (context.cpp: the read-only option "view_weights_launches")
 namespace smesh {
 uint64_t smesh_view_weights_launches() { return g_launches.load(); }
+
+// (edge_weights.hip: the view weights as the first stage of smesh_fuse_views_weighted -- depth_gate.hpp)
+int view_weights_check(smesh_renderer* r, const smesh_view_weights_spec_t* spec, RendererMesh* mesh) {
+  SMESH_TRY(spec_check(spec));
+  return mesh_check(r, mesh);
+}
+
+int view_weights_group(DeviceCtx* ctx, const RendererMesh& mesh, DepthScratch& scratch, const GatedView* views, int m,
+                       const smesh_view_weights_spec_t& spec, uint64_t* counts_host) {
+  return weigh_group(ctx, mesh, scratch.view_counts, views, m, spec, counts_host);
+}
 }  // namespace smesh
 
 extern "C" int smesh_view_weights(smesh_renderer_t* renderer, const smesh_camera_t* camera, const uint32_t* indices, const float* depth, uint64_t W,

@@ -482,10 +482,96 @@ def _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, what):
     return view_weights
 
 
-def _stats_of(view_counts, depth_counts, view_stats, depth_stats, single=False):
-    """What a weighted / gated fuse call returns: None, one uint64 counts array, or the pair (view counts, depth counts)."""
-    got = [c[0] if single else c for c, asked in ((view_counts, view_stats), (depth_counts, depth_stats)) if asked]
+def _stats_of(view_counts, depth_counts, view_stats, depth_stats, single=False, edge_counts=None, edge_stats=False):
+    """What a weighted / gated fuse call returns: None, one uint64 counts array bare, or the tuple of those asked for in the order
+    (view counts, edge counts, depth counts)."""
+    got = [c[0] if single else c for c, asked in ((view_counts, view_stats), (edge_counts, edge_stats), (depth_counts, depth_stats)) if asked]
     return None if not got else got[0] if len(got) == 1 else tuple(got)
+
+
+class EdgeGate:
+    """The gate of the occlusion-edge weights (include/smesh_edge_gate.h, where the rule is stated to the bit): a pixel of the rendered
+    depth plane loses its weight when a depth discontinuity lies within `radius` pixels (1 .. 8, a square window) of it.  With d the
+    pixel's depth, lo / hi the smallest / largest finite depth in the window and t = abs_tol + rel_tol * d in float32: `behind` drops
+    the pixel when d - lo > t (a nearer surface close by: its labels bleed onto this pixel), `front` when hi - d > t (the rim of an
+    occluder), `silhouette` when the window holds background.  `abs_tol` has no default: the caller states it."""
+
+    def __init__(self, radius, abs_tol, rel_tol=0.0, behind=True, front=False, silhouette=False):
+        if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= _lib.EDGE_MAX_RADIUS:
+            raise ValueError("EdgeGate: radius must be an integer in [1, %d], got %r" % (_lib.EDGE_MAX_RADIUS, radius))
+        self.radius = int(radius)
+
+        def number(v, name):
+            try:
+                f = float(np.float32(v))
+            except (TypeError, ValueError):
+                raise ValueError("EdgeGate: %s must be a number, got %r" % (name, v))
+            if f != f or f < 0.0 or f == float("inf"):
+                raise ValueError("EdgeGate: %s must be a finite number >= 0, got %r" % (name, v))
+            return f
+        self.abs_tol = number(abs_tol, "abs_tol")
+        self.rel_tol = number(rel_tol, "rel_tol")
+        for name, v in (("behind", behind), ("front", front), ("silhouette", silhouette)):
+            if not isinstance(v, (bool, np.bool_)):
+                raise ValueError("EdgeGate: %s must be True or False, got %r" % (name, v))
+        self.behind, self.front, self.silhouette = bool(behind), bool(front), bool(silhouette)
+
+    def _pod(self):
+        return _lib.EdgeGatePOD(self.radius, self.abs_tol, self.rel_tol, int(self.behind), int(self.front), int(self.silhouette))
+
+    def __repr__(self):
+        return "EdgeGate(radius=%r, abs_tol=%r, rel_tol=%r, behind=%r, front=%r, silhouette=%r)" % (
+            self.radius, self.abs_tol, self.rel_tol, self.behind, self.front, self.silhouette)
+
+
+def edge_weights_device(depth, gate, weights_image=None, return_counts=False, device=0):
+    """The occlusion-edge weights of ONE view on the device (`smesh_edge_weights`, include/smesh_edge_gate.h): `depth` the float32
+    (W,H) depth plane of `renderer.render(camera)` (a host copy of one, or any plane of the caller's), `gate` an `EdgeGate`,
+    `weights_image` an optional float32 (W,H) image that is multiplied in.  Returns a float32 (W,H) `DeviceArray` -- what
+    `add(idx, probs, w)`, `add_many`, `add_labels` and `fuse_views_ranged` take as a weights image; with `return_counts=True` also the
+    uint64 [visible, behind, front, silhouette] counts, which makes the call wait.  A host plane goes to `device`."""
+    from .device import DeviceBuffer
+    if not isinstance(gate, EdgeGate):
+        raise ValueError("edge_gate must be a fusion.EdgeGate, got %r" % (gate,))
+    if isinstance(depth, DeviceArray):
+        device = depth.device
+    device = int(device)
+    shape = tuple(getattr(depth, "shape", None) or np.shape(depth))
+    if len(shape) != 2:
+        raise ValueError("depth plane must have rank 2, got shape %s" % (shape,))
+    W, H = int(shape[0]), int(shape[1])
+    streams = []
+    dp, dkeep = _dense_plane(depth, W, H, device, "depth plane", streams)
+    wp, wkeep = (None, None) if weights_image is None else _dense_plane(weights_image, W, H, device, "weights image", streams)
+    out = DeviceBuffer(max(W * H * 4, 4), device).view((W, H), np.float32)
+    counts = np.zeros(4, np.uint64) if return_counts else None
+    pod = gate._pod()
+    _lib.check(_lib.lib().smesh_edge_weights(ctypes.c_void_p(dp), W, H, ctypes.byref(pod), None if wp is None else ctypes.c_void_p(wp),
+                                             ctypes.c_void_p(out.ptr), None if counts is None else counts.ctypes.data_as(ctypes.c_void_p), device))
+    release_to(device, streams)
+    if any(k is not None and not isinstance(k, (DeviceArray, np.ndarray)) for k in (dkeep, wkeep)):
+        _lib.synchronize(device)      # (a foreign input may be freed by its owner as soon as we return)
+    out._gate_inputs = (dkeep, wkeep)      # (this library's own arrays are freed behind its streams)
+    return (out, counts) if return_counts else out
+
+
+def edge_weights(depth, gate, weights_image=None, return_counts=False, device=0):
+    """`edge_weights_device` copied to the host: a numpy array (and the counts)."""
+    r = edge_weights_device(depth, gate, weights_image, return_counts, device)
+    return (r[0].numpy(), r[1]) if return_counts else r.numpy()
+
+
+def _edge_keywords(edge_gate, edge_stats, sample_in_kernel, what):
+    """The `edge_gate=` and `edge_stats=` keywords of a fuse call, checked: None for a call without them, else the gate."""
+    if edge_gate is None:
+        if edge_stats:
+            raise ValueError("%s: edge_stats=True needs edge_gate" % what)
+        return None
+    if not isinstance(edge_gate, EdgeGate):
+        raise ValueError("%s: edge_gate must be a fusion.EdgeGate, got %r" % (what, edge_gate))
+    if sample_in_kernel:
+        raise ValueError("%s: sample_in_kernel=True cannot be combined with an edge gate" % what)
+    return edge_gate
 
 
 GROUP_VIEWS = 8                                                     # views per deferred group (= the library's views per launch)
@@ -780,15 +866,18 @@ class _MeshAggregator:
             plane = prepare_labels_device(image, self.classes, (W, H), resize, None if table is not None else m, self.device, table)
         return plane.ptr, (_lib.DEPTH_IMG_LABELS_U8 if plane.dtype == np.uint8 else _lib.DEPTH_IMG_LABELS_U16), plane
 
-    def _fuse_views_gated(self, renderer, cameras, prepare, weights_images, sensors, gate, depth_stats, what, spec=None, view_stats=False):
+    def _fuse_views_gated(self, renderer, cameras, prepare, weights_images, sensors, gate, depth_stats, what, spec=None, view_stats=False,
+                          edge=None, edge_stats=False):
         """The gated / weighted form of fuse_views / fuse_views_labels: the batch is worked through in chunks of eight views -- the views
         of a fusion launch; `prepare(i, streams)` gives view i's dense device image as (pointer, image kind, keep-alive), host weights are
         copied to the device, and a chunk whose sensor images share size, dtype, strides and memory (and whose images share their kind)
         is ONE `smesh_fuse_views_depth` call -- with `spec` (a `ViewWeights`) one `smesh_fuse_views_view_weights` call, with or without
-        sensor images; a mixed chunk goes view by view.  Returns (view counts or None, depth counts or None), uint64 [n, 4] each."""
+        sensor images, with `edge` (an `EdgeGate`) one `smesh_fuse_views_weighted` call with whichever of the three stages are given;
+        a mixed chunk goes view by view.  Returns (view counts or None, depth counts or None, edge counts or None), uint64 [n, 4] each."""
         n = len(cameras)
         counts = np.zeros((n, 4), np.uint64) if depth_stats else None
         vcounts = np.zeros((n, 4), np.uint64) if view_stats else None
+        ecounts = np.zeros((n, 4), np.uint64) if edge_stats else None
         sensor_streams = []
         # (every sensor image is checked before anything is copied or fused)
         sdesc = None if sensors is None else [_describe_sensor(sensors[i], self.device, sensor_streams, "sensor depth image %d" % i) for i in range(n)]
@@ -822,6 +911,16 @@ class _MeshAggregator:
                     wptr = (ctypes.c_void_p * k)(*[views[j][2][0] for j in range(a, b)])
                 pod = None if sdesc is None else gate._pod(first_s[6])
                 cptr = None if counts is None else ctypes.c_void_p(counts.ctypes.data + (lo + a) * 32)
+                if edge is not None:
+                    vpod, epod = None if spec is None else spec._pod(), edge._pod()
+                    vptr = None if vcounts is None else ctypes.c_void_p(vcounts.ctypes.data + (lo + a) * 32)
+                    eptr = None if ecounts is None else ctypes.c_void_p(ecounts.ctypes.data + (lo + a) * 32)
+                    stail = (None, 0, None, 0, 0, 0, None) if sdesc is None else (sptr, first_s[3], _c64(first_s[4]), first_s[1], first_s[2][0],
+                                                                                 first_s[2][1], ctypes.byref(pod))
+                    _lib.check(_lib.lib().smesh_fuse_views_weighted(rh, self._h, pods, k, iptr, first_img[1], wptr,
+                                                                    None if vpod is None else ctypes.byref(vpod), ctypes.byref(epod), *stail,
+                                                                    vptr, eptr, cptr))
+                    continue
                 if spec is None:
                     _lib.check(_lib.lib().smesh_fuse_views_depth(rh, self._h, pods, k, iptr, first_img[1], wptr, sptr, first_s[3], _c64(first_s[4]),
                                                                  first_s[1], first_s[2][0], first_s[2][1], ctypes.byref(pod), cptr))
@@ -838,10 +937,10 @@ class _MeshAggregator:
             release_to(self.device, streams)
             self._hold([v[0][2] for v in views] + [v[1][5] for v in views if v[1] is not None and v[1][1] == _lib.MEM_DEVICE] + [v[2][1] for v in views])
         release_to(self.device, sensor_streams)
-        return vcounts, counts
+        return vcounts, counts, ecounts
 
     def _fuse_views_probs_gated(self, renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, gate, depth_stats, what,
-                                spec=None, view_stats=False):
+                                spec=None, view_stats=False, edge=None, edge_stats=False):
         from .resize import resize_mode
         mode = resize_mode(resize)
         cameras, probs_images = list(cameras), list(probs_images)
@@ -852,10 +951,10 @@ class _MeshAggregator:
         def prepare(i, streams):
             W, H = cameras[i].resolution
             return self._gated_probs(probs_images[i], W, H, mode, probs_dtype, streams, "probs image %d" % i)
-        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats)
+        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats, edge, edge_stats)
 
     def _fuse_views_labels_gated(self, renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors, gate, depth_stats, what,
-                                 spec=None, view_stats=False):
+                                 spec=None, view_stats=False, edge=None, edge_stats=False):
         label_resize_mode(resize)
         cameras, label_images = list(cameras), list(label_images)
         wts = None if weights_images is None else list(weights_images)
@@ -866,7 +965,7 @@ class _MeshAggregator:
         def prepare(i, streams):
             W, H = cameras[i].resolution
             return self._gated_labels(label_images[i], W, H, resize, m, streams, "label image %d" % i)
-        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats)
+        return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats, edge, edge_stats)
 
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
@@ -1152,15 +1251,16 @@ class _MeshAggregator:
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
 
     def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None, palette=None,
-                         sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
+                         sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
         """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`,
-        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate`, `depth_stats`, `view_weights` and `view_stats`)."""
+        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate`, `depth_stats`, `view_weights`, `view_stats`, `edge_gate` and `edge_stats`)."""
         sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, False, "fuse_view_labels")
         spec = _view_keywords(renderer, view_weights, view_stats, False, "fuse_view_labels")
-        if sensors is not None or spec is not None:
+        edge = _edge_keywords(edge_gate, edge_stats, False, "fuse_view_labels")
+        if sensors is not None or spec is not None or edge is not None:
             stats = self._fuse_views_labels_gated(renderer, [camera], [label_image], None if weights_image is None else [weights_image],
-                                                  resize, label_map, palette, sensors, depth_gate, depth_stats, "fuse_view_labels", spec, view_stats)
-            return _stats_of(stats[0], stats[1], view_stats, depth_stats, single=True)
+                                                  resize, label_map, palette, sensors, depth_gate, depth_stats, "fuse_view_labels", spec, view_stats, edge, edge_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats, single=True, edge_counts=stats[2], edge_stats=edge_stats)
         mode, m = label_resize_mode(resize), _palette_or_map(palette, label_map, [label_image], self.classes, self.device)
         W, H = camera.resolution
         if m is not None or (mode is not None and self._shape_of(label_image) != (W, H)):
@@ -1228,7 +1328,7 @@ class _MeshAggregator:
             self._hold([d[5] for d, _ in desc] + [dw[1] for _, dw in desc])
 
     def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None, palette=None,
-                          sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
+                          sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
         """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
         views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
         and memory go to the library as one batch; a mixed list is fused view by view.  `resize="nearest"` / `label_map` (see
@@ -1236,15 +1336,16 @@ class _MeshAggregator:
         size are prepared and fused by the library in batches of eight.  `palette` (see add_labels): colour images; a `ColorRemap`
         is first updated with all the call's images, in their order -- their distinct colours are found on the device, eight images
         per synchronisation -- and must then hold no more colours than the aggregator has classes.
-        `sensor_depths=`, `depth_gate=`, `depth_stats=`, `view_weights=`, `view_stats=`: see fuse_views -- the masks are prepared in
-        chunks of eight, then weighted and gated."""
+        `sensor_depths=`, `depth_gate=`, `depth_stats=`, `view_weights=`, `view_stats=`, `edge_gate=`, `edge_stats=`: see fuse_views --
+        the masks are prepared in chunks of eight, then weighted and gated."""
         cameras = list(cameras)
         sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), False, "fuse_views_labels")
         spec = _view_keywords(renderer, view_weights, view_stats, False, "fuse_views_labels")
-        if sensors is not None or spec is not None:
+        edge = _edge_keywords(edge_gate, edge_stats, False, "fuse_views_labels")
+        if sensors is not None or spec is not None or edge is not None:
             stats = self._fuse_views_labels_gated(renderer, cameras, label_images, weights_images, resize, label_map, palette, sensors,
-                                                  depth_gate, depth_stats, "fuse_views_labels", spec, view_stats)
-            return _stats_of(stats[0], stats[1], view_stats, depth_stats)
+                                                  depth_gate, depth_stats, "fuse_views_labels", spec, view_stats, edge, edge_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats, edge_counts=stats[2], edge_stats=edge_stats)
         mode, m = label_resize_mode(resize), check_label_map(label_map)
         cameras, label_images = list(cameras), list(label_images)
         n = len(cameras)
@@ -1467,21 +1568,22 @@ class _MeshAggregator:
         return ModelRenderer(self)
 
     def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False,
-                  sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
+                  sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
         """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
         float32, float16 or bfloat16 (see add()); with `resize="bilinear"` any (w,h,C) image add() takes, resampled to the camera's
         resolution on the device first -- or, with `sample_in_kernel=True`, sampled inside the fusion kernel (see add(); one library
         call per view, after the views already deferred).  `sensor_depth=`, `depth_gate=`, `depth_stats=`: the view is gated by its
         sensor depth (see fuse_views); the views already deferred are handed over first, then this view is a call of its own.
-        `view_weights=`, `view_stats=`: the view is weighted by its viewing geometry (see fuse_views), under the same rule for
-        deferred views."""
+        `view_weights=`, `view_stats=`, `edge_gate=`, `edge_stats=`: the view is weighted by its viewing geometry, gated at its
+        occlusion edges (see fuse_views), under the same rule for deferred views."""
         from .resize import resize_mode
         sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, sample_in_kernel, "fuse_view")
         spec = _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, "fuse_view")
-        if sensors is not None or spec is not None:
+        edge = _edge_keywords(edge_gate, edge_stats, sample_in_kernel, "fuse_view")
+        if sensors is not None or spec is not None or edge is not None:
             stats = self._fuse_views_probs_gated(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
-                                                 probs_dtype, resize, sensors, depth_gate, depth_stats, "fuse_view", spec, view_stats)
-            return _stats_of(stats[0], stats[1], view_stats, depth_stats, single=True)
+                                                 probs_dtype, resize, sensors, depth_gate, depth_stats, "fuse_view", spec, view_stats, edge, edge_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats, single=True, edge_counts=stats[2], edge_stats=edge_stats)
         smode = self._sampling_mode(resize, sample_in_kernel, "fuse_view")
         if smode is not None:
             return self._fuse_views_sampled(renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
@@ -1556,7 +1658,7 @@ class _MeshAggregator:
                 _lib.PROBS_F32 if code is None else code)
 
     def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False,
-                   sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False):
+                   sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
         accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
@@ -1578,15 +1680,21 @@ class _MeshAggregator:
         planes, eight views per launch, multiplied into `weights_images` where given; triangle renderers only.  It combines with
         everything the depth keywords combine with and with the depth keywords themselves: the view weights are computed first, the
         depth gate then gates them.  `view_stats=True` returns the uint64 [n, 4] counts [visible, far, grazing, backfacing] per view
-        and waits for them; with `depth_stats=True` as well the call returns the pair (view counts, depth counts)."""
+        and waits for them; with `depth_stats=True` as well the call returns the pair (view counts, depth counts).
+        `edge_gate=` (an `EdgeGate`): every pixel within a few pixels of a depth discontinuity of the render loses its weight
+        (include/smesh_edge_gate.h) -- the cure for labels bleeding across occlusion edges, from the rendered depth alone, eight views
+        per launch; it takes any renderer, combines with everything `view_weights=` combines with and runs between the view weights
+        and the depth gate.  `edge_stats=True` returns the uint64 [n, 4] counts [visible, behind, front, silhouette] per view and
+        waits; the stats asked for come back in the order (view, edge, depth), a single one bare."""
         from .resize import image_size, resize_mode
         cameras = list(cameras)
         sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), sample_in_kernel, "fuse_views")
         spec = _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, "fuse_views")
-        if sensors is not None or spec is not None:
+        edge = _edge_keywords(edge_gate, edge_stats, sample_in_kernel, "fuse_views")
+        if sensors is not None or spec is not None or edge is not None:
             stats = self._fuse_views_probs_gated(renderer, cameras, probs_images, weights_images, probs_dtype, resize, sensors, depth_gate,
-                                                 depth_stats, "fuse_views", spec, view_stats)
-            return _stats_of(stats[0], stats[1], view_stats, depth_stats)
+                                                 depth_stats, "fuse_views", spec, view_stats, edge, edge_stats)
+            return _stats_of(stats[0], stats[1], view_stats, depth_stats, edge_counts=stats[2], edge_stats=edge_stats)
         mode = resize_mode(resize)
         smode = self._sampling_mode(resize, sample_in_kernel, "fuse_views")
         if smode is not None:
