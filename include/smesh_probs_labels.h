@@ -31,7 +31,9 @@
  * the GENERIC path: one lane per pixel, strided loads.  smesh_set_option("probs_labels_tiles", 0 | 1) (default 1) is a test hook:
  * 0 sends every image down the generic path; results are the same.  smesh_confusion_add_probs labels and counts in ONE kernel up to
  * 63 classes (the small LDS histogram of smesh_eval.h); beyond that the labels go as int32 into library scratch and k_confusion
- * counts them (two launches).
+ * counts them (two launches).  Read-only, reporting (smesh_get_option): "last_probs_labels_grid" is the number of workgroups of the
+ * calling thread's last launch of either path, "last_probs_labels_work" what they shared out -- tiles on the tiled path, rounds of
+ * 256 pixels on the generic one; a launch with work > grid had workgroups that took more than one.  Both are 0 before the first launch.
  */
 #ifndef SMESH_PROBS_LABELS_H
 #define SMESH_PROBS_LABELS_H

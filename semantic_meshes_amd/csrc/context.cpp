@@ -50,6 +50,7 @@ uint64_t smesh_label_colors_launches();    // label_colors.hip
 uint64_t smesh_depth_weights_launches();   // depth_weights.hip
 uint64_t smesh_view_weights_launches();    // view_weights.hip
 uint64_t smesh_edge_weights_launches();    // edge_weights.hip
+void smesh_last_probs_labels_launch(uint64_t* grid, uint64_t* work);   // probs_labels.hip: the calling thread's last launch
 
 // "fuse_sampled" (fusion_sampled.hip): 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- a test hook, like
 // SMESH_FUSE_H16=0.  -1: not set by smesh_set_option -- the environment's SMESH_FUSE_SAMPLED, read at every call, else on.
@@ -451,6 +452,16 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "edge_weights_launches")) { *value = (int64_t)smesh_edge_weights_launches(); return SMESH_OK; }
   // read-only (smesh_probs_labels.h): the largest class count the tiled path serves
   if (!strcmp(name, "probs_labels_tile_max_classes")) { *value = (int64_t)kProbsLabelsTileMaxC; return SMESH_OK; }
+  // read-only, reporting (like "last_fuse_slot"): the calling thread's last launch of k_probs_labels_tiled / _generic --
+  // "last_probs_labels_grid": its workgroups; "last_probs_labels_work": what they shared out, tiles on the tiled path, rounds of 256
+  // pixels on the generic one (work > grid: some workgroup took more than one); both 0 before the first launch
+  const bool want_grid = !strcmp(name, "last_probs_labels_grid");
+  if (want_grid || !strcmp(name, "last_probs_labels_work")) {
+    uint64_t grid, work;
+    smesh_last_probs_labels_launch(&grid, &work);
+    *value = (int64_t)(want_grid ? grid : work);
+    return SMESH_OK;
+  }
   // read-only, reporting: the instance of the calling thread's last triangle-order fusion launch (smesh_aggregator_fuse_triangles) --
   // "last_fuse_slot": the class-count slot handed to k_fuse_tri (5 / 13 / 19 / 20 / 21 / 40: the exact instances; 8 / 16 / 24 / 32 / 41 / 48:
   // the run-time-C instances with 8 .. 32, 40 and 48 register slots), 0 when the launch was k_fuse_tri_any, k_fuse_tri_wide or

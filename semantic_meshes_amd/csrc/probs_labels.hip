@@ -34,6 +34,9 @@ constexpr uint32_t kMinRunShare = 8;
 constexpr int kGroupsPerCuCount = 4, kGroupsPerCuPlain = 6;
 static_assert(kGroupsPerCuCount * (kStageWords + kLdsWordsSmall) * 4 <= 160 * 1024, "four counting workgroups must fit a CU's LDS");
 
+// The calling thread's last launch, for reporting (the read-only options "last_probs_labels_grid" / "last_probs_labels_work").
+thread_local uint64_t g_last_grid = 0, g_last_work = 0;
+
 size_t probs_itemsize(int dt) { return dt == SMESH_PROBS_F32 ? 4 : 2; }
 
 struct PlArgs {
@@ -414,6 +417,7 @@ int launch_probs_labels(DeviceCtx* ctx, PlArgs a) {
     else hipLaunchKernelGGL(k_probs_labels_generic<false>, g, b, 0, ctx->stream, a);
   }
   SMESH_HIP(hipGetLastError());
+  g_last_grid = g.x; g_last_work = work;   // (reporting only)
   return SMESH_OK;
 }
 
@@ -436,6 +440,11 @@ struct ScratchGuard {     // scratch of one call of smesh_probs_labels
 };
 
 }  // namespace
+
+// (context.cpp: the read-only options "last_probs_labels_grid" / "last_probs_labels_work")
+namespace smesh {
+void smesh_last_probs_labels_launch(uint64_t* grid, uint64_t* work) { *grid = g_last_grid; *work = g_last_work; }
+}  // namespace smesh
 
 extern "C" {
 

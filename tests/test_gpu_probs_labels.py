@@ -2,8 +2,10 @@
 fusion.argmax_labels / argmax_labels_device, ConfusionMatrix.add_probs).
 
 Every expectation is numpy: the explicit class loop of probs_labels_ref.ref_labels on the exactly widened image, and np.add.at for
-the matrices.  Outputs are integers: all comparisons are array_equal.  Shapes are the smallest that exercise the tiling: runs shorter
-and longer than a tile, W H not a multiple of one, a single-pixel tail."""
+the matrices.  Outputs are integers: all comparisons are array_equal.  Shapes are the smallest with runs shorter and longer than a
+tile, W H not a multiple of one and a single-pixel tail; at these shapes every workgroup runs ONE round -- the largest, (130, 67) at 255
+classes, is 363 tiles for a grid capped at a thousand or more.  The rounds after the first (the prefetch, the carry of the next
+tile's pixel and ground truth, the grid-stride loop of the generic path) are tests/test_gpu_image_kernels_scale.py's."""
 import ctypes
 
 import numpy as np
