@@ -101,6 +101,11 @@ bool opt_raster_meshlets();
 // (records.hpp); 0: every launch leaves TriFrag, kernel for kernel what the library did before.  Same results either way.
 constexpr int kCompactRecordsDefault = 1;
 bool opt_compact_records();
+// packed_fragments (SMESH_PACKED_FRAGMENTS; default 1): the fragment queues of a triangle renderer of at most 2^22 faces hold one 8-byte
+// entry per fragment (fragments.hpp) instead of a 64-bit key and a 16-bit pixel in two arrays; read per raster launch.  0, texel
+// renderers and larger meshes: the 10-byte format, kernel for kernel what the library did before.  Same results either way.
+constexpr int kPackedFragmentsDefault = 1;
+bool opt_packed_fragments();
 // pipeline_fit (SMESH_PIPELINE_FIT; default 1): the LDS pad that caps the eight-view fusion launch of the group pipeline is computed from
 // the device's LDS and the instance's own (pipeline_fuse_pad below); 0: the constant 24 576 bytes of rounds 2 - 6, kept selectable so that
 // both can be compared in one process.  Same results either way.

@@ -96,6 +96,18 @@ bool opt_compact_records() {
   return v != 0;
 }
 
+// "packed_fragments" (common.hpp, fragments.hpp): 8-byte fragment-queue entries between the rasteriser and the tile resolve.  Same results either way.
+static std::atomic<int> g_packed_fragments{-1};   // -1: not decided yet (the environment, else the default)
+bool opt_packed_fragments() {
+  int v = g_packed_fragments.load();
+  if (v < 0) {
+    const char* e = getenv("SMESH_PACKED_FRAGMENTS");
+    v = e ? (atoi(e) != 0 ? 1 : 0) : kPackedFragmentsDefault;
+    g_packed_fragments.store(v);
+  }
+  return v != 0;
+}
+
 // "pipeline_fit", "pipeline_fuse_waves", "pipeline_fuse_pad" (common.hpp): how the group pipeline's two kernels are fitted into a CU.
 // -2: not set by smesh_set_option -- the environment, read once, else the default.
 static std::atomic<int> g_pipeline_fit{-2}, g_pipeline_fuse_waves{-2}, g_pipeline_fuse_pad{-2};
@@ -381,7 +393,8 @@ void smesh_last_fuse_instance(int* slot, int* views);   // fusion.hip: the calli
 uint32_t smesh_last_fuse_lds_pad();                     // fusion.hip: dynamic LDS of the calling thread's last eight-view k_fuse_tri launch
 int smesh_last_fuse_beside();                           // fusion.hip: rasteriser workgroups per CU the last computed pad leaves room for
 int smesh_last_record_format();                         // raster.hip: bytes per record (8 or 16) the calling thread's last raster launch left
-int smesh_last_fuse_probs_dtype();                      // raster.hip: SMESH_PROBS_* of the class vectors the calling thread's last fusion read
+int smesh_last_fragment_format();                       // raster.hip: bytes per queued fragment (8 or 10) of the calling thread's last raster launch
+int smesh_last_fuse_probs_dtype();                     // raster.hip: SMESH_PROBS_* of the class vectors the calling thread's last fusion read
 
 extern "C" {
 
@@ -397,6 +410,7 @@ int smesh_set_option(const char* name, int64_t value) {
   if (!strcmp(name, "group_pipeline")) { g_group_pipeline.store(value != 0 ? 1 : 0); return SMESH_OK; }
   if (!strcmp(name, "raster_meshlets")) { g_raster_meshlets.store(value != 0 ? 1 : 0); return SMESH_OK; }
   if (!strcmp(name, "compact_records")) { g_compact_records.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  if (!strcmp(name, "packed_fragments")) { g_packed_fragments.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // how the group pipeline's two kernels share a CU (common.hpp): same results whatever the values
   if (!strcmp(name, "pipeline_fit")) { g_pipeline_fit.store(value != 0 ? 1 : 0); return SMESH_OK; }
   if (!strcmp(name, "pipeline_fuse_waves")) { g_pipeline_fuse_waves.store((int)std::min<int64_t>(32, std::max<int64_t>(2, value))); return SMESH_OK; }
@@ -421,6 +435,9 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "compact_records")) { *value = opt_compact_records() ? 1 : 0; return SMESH_OK; }
   // read-only (reporting): bytes per per-triangle record the calling thread's last raster launch left: 8 (records.hpp) or 16 (TriFrag; also before the first)
   if (!strcmp(name, "last_record_format")) { *value = (int64_t)smesh_last_record_format(); return SMESH_OK; }
+  if (!strcmp(name, "packed_fragments")) { *value = opt_packed_fragments() ? 1 : 0; return SMESH_OK; }
+  // read-only (reporting): bytes per queued fragment of the calling thread's last raster launch: 8 (fragments.hpp) or 10 (key + pixel; also before the first)
+  if (!strcmp(name, "last_fragment_format")) { *value = (int64_t)smesh_last_fragment_format(); return SMESH_OK; }
   if (!strcmp(name, "pipeline_fit")) { *value = opt_pipeline_fit(); return SMESH_OK; }
   if (!strcmp(name, "pipeline_fuse_waves")) { *value = opt_pipeline_fuse_waves(); return SMESH_OK; }
   if (!strcmp(name, "pipeline_fuse_pad")) { *value = opt_pipeline_fuse_pad(); return SMESH_OK; }

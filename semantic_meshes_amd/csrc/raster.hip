@@ -20,6 +20,7 @@
 // z resolves to the lower id, so the result does not depend on the order triangles are processed in.
 #include "common.hpp"
 #include "meshlets.hpp"
+#include "fragments.hpp"
 #include "half_scratch.hpp"
 #include "depth_gate.hpp"
 #include "../../include/smesh_meshlets.h"
@@ -275,10 +276,16 @@ constexpr int kQSub = 4;      // sub-queues per tile: a wave appends to sub-queu
                               // 32.7 / 32.0 us, k_tile_resolve (which reads them back) 8.2 / 9.0 / 10.7 / 15.1 us.
 constexpr int kMedium = 64;   // boxes up to kMedium x kMedium (and larger than 8 x 8) are rasterised by a whole wave inside k_raster_frag
 constexpr unsigned long long kNullKey = ~0ull;   // loses every depth test, including against the background key
+static_assert(kQW == kFragTileW && kQH == kFragTileH && kQPixels <= 2048, "fragments.hpp packs the pixel of a tile into 11 bits");
+static_assert(kNullKey == kFragNull && kBackgroundKey == kFragKeyBackground, "fragments.hpp converts the keys of the key image");
 
 struct FragQueues {
-  unsigned long long* key = nullptr;   // [ntiles * kQSub * cap] depth-test keys
-  uint16_t* pix = nullptr;             // [ntiles * kQSub * cap] pixel inside the tile: (x - tile_x0) * kQH + (y - tile_y0)
+  unsigned long long* key = nullptr;   // [ntiles * kQSub * cap] depth-test keys; or (packed launches) the packed entries of fragments.hpp
+  uint16_t* pix = nullptr;             // [ntiles * kQSub * cap] pixel inside the tile: (x - tile_x0) * kQH + (y - tile_y0).  NULL in the
+                                       // kernel arguments of a launch = its entries are packed (launch-uniform, the same for every view of a
+                                       // group; the renderer decides: packed_fragments_wanted) and the host launched the PACKED instances of
+                                       // the writers and of the reader.  A view slot's allocation exists from the first launch of the slot
+                                       // that needs the 10-byte format (ensure_queues)
   uint32_t* count = nullptr;           // [ntiles * kQSub] fragments queued per sub-queue (may exceed cap: the excess went to the key image)
   uint32_t* flag = nullptr;            // [ntiles] nonzero: the global key image holds fragments of this tile
   uint32_t cap = 0, tiles_y = 0;       // cap: slots per SUB-queue
@@ -710,7 +717,10 @@ __device__ __forceinline__ unsigned long long walk_box(const Tri& t, const int X
 // TEX (compile time, = a.tex_res != nullptr): with a run-time test the compiler computed the two divisions of the texel's barycentric
 // coordinates for every fragment of every renderer and selected afterwards -- three FP64 divisions per fragment instead of one,
 // a tenth of k_raster_frag's vector instructions at cfg2 (round 6).
-template <bool TEX>
+// PACKED (compile time, never with TEX): the queue takes ONE 8-byte entry per fragment (fragments.hpp) and a.q.pix is null.  Not a
+// run-time flag (built first: same register counts, two more SGPRs): the renderers that keep the 10-byte format -- texels, meshes
+// over 2^22 faces -- run instances that are the code they were, by the register report line for line (NOTES/packed_fragments.md 3).
+template <bool TEX, bool PACKED>
 __device__ __forceinline__ unsigned long long emit_cover(const RasterArgs& a, const Tri& t, const uint64_t f, const uint32_t pid,
                                                          const int X0, const int Y0, unsigned long long cover, const uint32_t sub) {
   const int lane = threadIdx.x & 63;
@@ -767,8 +777,9 @@ __device__ __forceinline__ unsigned long long emit_cover(const RasterArgs& a, co
     // pixel inside its tile: (x mod 32) * 64 + (y mod 64)
     const uint16_t pin = (uint16_t)((((uint32_t)x & (kQW - 1)) * kQH) | ((uint32_t)y & (kQH - 1)));
     if (e < lim) {
-      a.q.key[e] = key;
-      a.q.pix[e] = pin;
+      // (the packed entry is put together here, at its store, from the key: held beside the key it would cost registers of the loop)
+      if constexpr (PACKED) a.q.key[e] = key == kNullKey ? kFragNull : frag_pack((uint32_t)(key >> 32), pin, (uint32_t)key);
+      else { a.q.key[e] = key; a.q.pix[e] = pin; }
     } else if (key != kNullKey) {
       atomicMin(&a.keys[key_index((uint32_t)x, (uint32_t)y, a.H)], key);
       atomicOr(&a.q.flag[(tx0 + (hx ? 1u : 0u)) * a.q.tiles_y + ty0 + (hy ? 1u : 0u)], 1u);
@@ -808,7 +819,7 @@ __device__ __forceinline__ void coop_reserve(const RasterArgs& a, const Tri& t, 
   for (int j = 0; j < 6; j++) rb[j] = reserve(j);     // in flight together
 }
 // The triangle of lane `src` (its set-up `t`, its reservations `rb`, triangle number f / index value pid in that lane), all 64 lanes on its box.
-template <bool TEX>
+template <bool TEX, bool PACKED>
 __device__ __forceinline__ void coop_walk(const RasterArgs& a, const Tri& t, const uint32_t (&rb)[6], const int src, const uint64_t fsrc,
                                           const uint32_t psrc, const uint32_t sub) {
   const int lane = threadIdx.x & 63;
@@ -862,8 +873,13 @@ __device__ __forceinline__ void coop_walk(const RasterArgs& a, const Tri& t, con
       if (!in_box) continue;
       if (slot < a.q.cap) {
         const uint64_t e = ((uint64_t)tile * kQSub + sub) * a.q.cap + slot;
-        a.q.key[e] = key;
-        a.q.pix[e] = (uint16_t)((x - jx * kQW) * kQH + (y - jy * kQH));
+        if constexpr (PACKED) {
+          const uint32_t pin = (uint32_t)((x - jx * kQW) * kQH + (y - jy * kQH));
+          a.q.key[e] = key == kNullKey ? kFragNull : frag_pack((uint32_t)(key >> 32), pin, (uint32_t)key);
+        } else {
+          a.q.key[e] = key;
+          a.q.pix[e] = (uint16_t)((x - jx * kQW) * kQH + (y - jy * kQH));
+        }
       } else if (key != kNullKey) {
         atomicMin(&a.keys[key_index((uint32_t)x, (uint32_t)y, a.H)], key);
         atomicOr(&a.q.flag[tile], 1u);
@@ -874,7 +890,7 @@ __device__ __forceinline__ void coop_walk(const RasterArgs& a, const Tri& t, con
 
 // MODE (an instance of the kernels per mode: the code of the other modes costs the small-triangle instance registers it does not
 // have -- k_raster_frag_group is held to 96 for five waves per SIMD): bit 0 = RasterArgs::wg_push, bit 1 = RasterArgs::spread,
-// bit 2 = texel primitives (RasterArgs::tex_res != nullptr; emit_cover).  (Round 6 also built a bit 3: an 8-byte PIXEL CELL per vertex -- first / last
+// bit 2 = texel primitives (RasterArgs::tex_res != nullptr; emit_cover), bit 3 = packed fragment-queue entries (emit_cover's PACKED; never with bit 2).  (Round 6 also built a bit 3: an 8-byte PIXEL CELL per vertex -- first / last
 // sample column and row a box ending / beginning there can reach -- read first, so that the seven in eight sub-pixel triangles of cfg4 that hold no
 // sample centre are dropped on 24 bytes instead of 72: k_raster_frag_group 667 -> 728 us per eight cfg4 views, 2 342 -> 2 579 at cfg5, the vertex stage
 // 97 -> 125: a second dependent round trip for every wave costs more than the bytes.  Not kept.)  (Round 6 also built instances whose lanes project their
@@ -886,7 +902,8 @@ template <int MODE, bool ML = false, bool NULLABLE_SV = false>
 __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64_t f, const int32_t i0, const int32_t i1, const int32_t i2,
                                                const uint32_t sub, const int part_in = -1, const bool listed = false,
                                                const MeshletTri* ml = nullptr) {
-  constexpr bool kWgPush = (MODE & 1) != 0, kSpreadMode = (MODE & 2) != 0, kTex = (MODE & 4) != 0;
+  constexpr bool kWgPush = (MODE & 1) != 0, kSpreadMode = (MODE & 2) != 0, kTex = (MODE & 4) != 0, kPacked = (MODE & 8) != 0;
+  static_assert(!(kTex && kPacked), "a texel renderer's key holds a texel id: never packed");
   const int lane = threadIdx.x & 63;
   const int part = kSpreadMode ? part_in : -1;
   const bool owner = part <= 0 && !listed;    // (listed: a triangle from the view's list, k_raster_medium -- its owner lane left its record and queue entries)
@@ -982,7 +999,7 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
     if (q_huge && slot[2] < a.big_capacity) a.huge_queue[slot[2]] = (uint32_t)f;
   }
   {
-    const unsigned long long mask = emit_cover<kTex>(a, t, f, pid, CX0, CY0, cover, sub);
+    const unsigned long long mask = emit_cover<kTex, kPacked>(a, t, f, pid, CX0, CY0, cover, sub);
     small = small && mask != 0ull;      // from here on: TriFrag kind 1
     cover = mask;
   }
@@ -1028,7 +1045,7 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
       const bool on = bw > 0 && bh > 0;
       if (__ballot(on) == 0ull) continue;
       const unsigned long long cv = on ? walk_box(t, X0, Y0, bw, bh) : 0ull;
-      (void)emit_cover<kTex>(a, t, f, pid, on ? X0 : 0, on ? Y0 : 0, cv, sub);
+      (void)emit_cover<kTex, kPacked>(a, t, f, pid, on ? X0 : 0, on ? Y0 : 0, cv, sub);
     }
   }
 
@@ -1059,14 +1076,14 @@ __device__ __forceinline__ void raster_frag_64(const RasterArgs& a, const uint64
   while (todo) {
     const int src = __ffsll((long long)todo) - 1;
     todo &= todo - 1ull;
-    coop_walk<kTex>(a, t, rb, src, f, pid, sub);
+    coop_walk<kTex, kPacked>(a, t, rb, src, f, pid, sub);
   }
 }
 
 // The view's list of medium triangles (RasterArgs::med_queue, filled by the balanced instances of k_raster_frag), a triangle per wave
 // and turn: every lane sets the triangle up for itself -- the same loads and arithmetic as its owner lane's, the same bits -- lane 0
 // reserves its tiles' sub-rectangles, the wave walks its box.
-template <bool TEX>
+template <bool TEX, bool PACKED>
 __device__ __forceinline__ void raster_medium_wave(const RasterArgs& a, const uint32_t wave, const uint32_t nwaves) {
   const int lane = threadIdx.x & 63;
   const uint32_t n = min(a.big_count[4], a.big_capacity);
@@ -1078,7 +1095,7 @@ __device__ __forceinline__ void raster_medium_wave(const RasterArgs& a, const ui
     if (load_tri_ex<true>(a, g, t, g0, g1, g2) != 1) continue;            // (never: its owner lane found it drawable)
     uint32_t rb[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     if (lane == 0) coop_reserve(a, t, i & (kQSub - 1), rb);
-    coop_walk<TEX>(a, t, rb, 0, g, a.prim_id ? a.prim_id[g] : g, i & (kQSub - 1));
+    coop_walk<TEX, PACKED>(a, t, rb, 0, g, a.prim_id ? a.prim_id[g] : g, i & (kQSub - 1));
   }
   // ... and the listed triangles with boxes of 9 .. kLaneBox pixels (from the far end of the list), seven per wave and turn: a spread wave
   constexpr int kLanes = kSpread, kTris = kSpreadTris;
@@ -1091,12 +1108,12 @@ __device__ __forceinline__ void raster_medium_wave(const RasterArgs& a, const ui
     if (tri < kTris && e < nl) fs = a.med_queue[a.big_capacity - 1u - e];
     int32_t s0 = 0, s1 = 0, s2 = 0;
     if (fs < a.F) { s0 = a.faces[3 * fs + 0]; s1 = a.faces[3 * fs + 1]; s2 = a.faces[3 * fs + 2]; }
-    raster_frag_64<TEX ? 6 : 2, false, true>(a, fs, s0, s1, s2, i & (kQSub - 1), lane % kLanes, true);
+    raster_frag_64<(TEX ? 6 : 2) | (PACKED ? 8 : 0), false, true>(a, fs, s0, s1, s2, i & (kQSub - 1), lane % kLanes, true);
   }
 }
-template <bool TEX>
+template <bool TEX, bool PACKED = false>
 __global__ __launch_bounds__(256) void k_raster_medium(RasterArgs a) {
-  raster_medium_wave<TEX>(a, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
+  raster_medium_wave<TEX, PACKED>(a, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, (gridDim.x * blockDim.x) >> 6);
 }
 
 // One wave = a.groups x a.tpw consecutive triangles (tpw: 64 for large meshes; fewer for small ones, so that the cooperative
@@ -1162,7 +1179,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 3) 
   if (tb >= nblocks) return;     // (block-uniform)
   raster_frag_wave<false, MODE>(a, ((uint64_t)tb * blockDim.x + threadIdx.x) >> 6);
 }
-int raster_mode(const RasterArgs& a) { return (a.spread ? 3 : a.wg_push ? 1 : 0) | (a.tex_res ? 4 : 0); }   // (spread views are views of medium triangles: wg_push too)   // (spread views are views of medium triangles: wg_push too)
+int raster_mode(const RasterArgs& a) { return (a.spread ? 3 : a.wg_push ? 1 : 0) | (a.tex_res ? 4 : 0); }   // (spread views are views of medium triangles: wg_push too; bit 3, packed entries: the caller's, where it launches)
 
 // Several views in one launch: blocks [v * blocks_per_view, (v + 1) * blocks_per_view) rasterise view v.
 struct RasterGroup {
@@ -1257,10 +1274,10 @@ __global__ void k_reset_big_counts(CountGroup g) {
   const uint32_t v = threadIdx.x / 6u, k = threadIdx.x - v * 6u;
   if (v < g.n) g.big_count[v][k] = 0u;
 }
-template <bool TEX>
+template <bool TEX, bool PACKED = false>
 __global__ __launch_bounds__(256) void k_raster_medium_group(RasterGroup g, uint32_t blocks_per_view) {
   const uint32_t v = blockIdx.x / blocks_per_view;   // block-uniform
-  raster_medium_wave<TEX>(g.view[v], ((blockIdx.x - v * blocks_per_view) * blockDim.x + threadIdx.x) >> 6, (blocks_per_view * blockDim.x) >> 6);
+  raster_medium_wave<TEX, PACKED>(g.view[v], ((blockIdx.x - v * blocks_per_view) * blockDim.x + threadIdx.x) >> 6, (blocks_per_view * blockDim.x) >> 6);
 }
 // The largest triangles (box over kMedium x kMedium) and the triangles that cross the near plane (clip_piece), between k_raster_frag
 // and k_tile_resolve: one workgroup per screen tile scans their queue, keeps those whose box overlaps the tile and shades the
@@ -1328,7 +1345,11 @@ __global__ __launch_bounds__(256) void k_raster_huge(RasterArgs a, uint32_t ntil
 // samples at a time), then the output planes are written once.  "Big" here means larger than kMedium x kMedium.
 // `planes_wanted()`: false = nobody will read this view's planes (RasterArgs::idx_optional; decided by the kernel per view or for the whole launch, asked
 // only where the planes would be written: its loads are not on the block's way in).
-template <typename PlanesWanted>
+// PACKED (a.q.pix is null; launch-uniform: the host picks the instance): the queue holds the 8-byte entries of fragments.hpp -- one load per
+// entry, the pixel comes out of the entry -- and the LDS slots hold packed entries too: every candidate of a pixel carries the same pixel
+// field, so ds_min_u64 orders them as it orders their keys, and lost() compares like with like.  The slots are seeded with the pixel's
+// background entry (keys merged from the key image are converted on the way in) and unpacked where the planes are written.
+template <bool PACKED, typename PlanesWanted>
 __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t* __restrict__ idx_out, float* __restrict__ depth_out,
                                                    const uint32_t tile, PlanesWanted planes_wanted) {
   __shared__ unsigned long long skeys[kQPixels];
@@ -1345,13 +1366,15 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
   const uint32_t sq = (uint32_t)t / kGroup, sq_lane = (uint32_t)t % kGroup;
   const uint64_t qbase = ((uint64_t)tile * kQSub + sq) * q.cap;
   unsigned long long spec_key[kSpec];
-  uint16_t spec_pix[kSpec];
+  uint16_t spec_pix[kSpec] = {};      // (PACKED: unused)
 #pragma unroll
   for (uint32_t k = 0; k < kSpec; k++) {
     const uint32_t i = min(sq_lane + k * kGroup, q.cap - 1u);
     spec_key[k] = q.key[qbase + i];
-    spec_pix[k] = q.pix[qbase + i];
+    if constexpr (!PACKED) spec_pix[k] = q.pix[qbase + i];
   }
+  // the LDS slot of an entry (a null entry names slot 2047 and changes nothing there)
+  auto slot_of = [](const unsigned long long key, const uint16_t pin) -> uint32_t { return PACKED ? frag_pixel(key) : (uint32_t)pin; };
   const uint32_t n = min(q.count[tile * kQSub + sq], q.cap);
   if (sq_lane == 0u) scount[sq] = n;
   // bit 0: fragments of small triangles that did not fit the queue went through the global key image; bit 1: k_raster_huge left the
@@ -1360,10 +1383,11 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
   const bool merge = tile_flag != 0u;
   for (int p = t; p < kQPixels; p += 256) {
     const uint32_t gx = x0 + (uint32_t)(p >> 6), gy = y0 + (uint32_t)(p & 63);
-    unsigned long long k = kBackgroundKey;
+    unsigned long long k = PACKED ? frag_background((uint32_t)p) : kBackgroundKey;
     if (merge && gx < W && gy < H) {   // fragments that did not fit the queue went through the global key image
       const uint64_t g = key_index(gx, gy, H);
-      k = a.keys[g];
+      k = a.keys[g];                // (always today's keys: the overflow path and k_raster_huge do not pack)
+      if constexpr (PACKED) k = frag_from_key(k, (uint32_t)p);
       a.keys[g] = kBackgroundKey;   // re-armed for the next render
     }
     skeys[p] = k;
@@ -1371,7 +1395,7 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
   __syncthreads();
 #pragma unroll
   for (uint32_t k = 0; k < kSpec; k++)
-    if (sq_lane + k * kGroup < n) atomicMin(&skeys[spec_pix[k]], spec_key[k]);
+    if (sq_lane + k * kGroup < n) atomicMin(&skeys[slot_of(spec_key[k], spec_pix[k])], spec_key[k]);
   // (skipping the null keys of the cooperative loop's sub-rectangles here was measured slower: 10 000 triangles 0.083 -> 0.090 ms per view)
   // What the speculative loads did not cover -- entries kHead ... of every sub-queue -- is ONE list for all 256 threads (sub-queue after
   // sub-queue), four entries of a thread in flight: the sub-queues of a tile fill evenly only where many waves reach it.  A medium
@@ -1389,17 +1413,17 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
   };
   for (uint32_t j0 = (uint32_t)t; j0 < total; j0 += 4u * 256u) {
     unsigned long long k4[4];
-    uint16_t p4[4];
+    uint16_t p4[4] = {};
 #pragma unroll
     for (uint32_t u = 0; u < 4u; u++) {
       const uint32_t j = j0 + u * 256u;
       const uint64_t e = j < total ? entry_of(j) : qbase;
       k4[u] = q.key[e];
-      p4[u] = q.pix[e];
+      if constexpr (!PACKED) p4[u] = q.pix[e];
     }
 #pragma unroll
     for (uint32_t u = 0; u < 4u; u++)
-      if (j0 + u * 256u < total) atomicMin(&skeys[p4[u]], k4[u]);
+      if (j0 + u * 256u < total) atomicMin(&skeys[slot_of(k4[u], p4[u])], k4[u]);
   }
   __syncthreads();
   // The depth test is decided: tell the triangle-order fusion which fragments of the small triangles LOST it, by clearing their
@@ -1412,9 +1436,10 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
     if (tile_flag & 1u) {
       if (t == 0) a.big_count[1] = 1u;
     } else {
-      auto lost = [&](const unsigned long long key, const uint32_t pin) {
+      auto lost = [&](const unsigned long long key, const uint16_t pin16) {
+        const uint32_t pin = slot_of(key, pin16);
         if (key == kNullKey || skeys[pin] == key) return;
-        const uint32_t f = (uint32_t)(key & 0xFFFFFFFFull);
+        const uint32_t f = PACKED ? frag_id(key) : (uint32_t)(key & 0xFFFFFFFFull);
         TriFrag* __restrict__ full = a.frags;
         if (a.compact) {             // (launch-uniform) the 8-byte word: kind 1 holds the mask itself, kind 3 points at the TriFrag behind the words
           const unsigned long long w = record_words(a)[f];
@@ -1437,13 +1462,13 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
         if (sq_lane + k * kGroup < n) lost(spec_key[k], spec_pix[k]);
       for (uint32_t j0 = (uint32_t)t; j0 < total; j0 += 4u * 256u) {
         unsigned long long k4[4];
-        uint16_t p4[4];
+        uint16_t p4[4] = {};
 #pragma unroll
         for (uint32_t u = 0; u < 4u; u++) {
           const uint32_t j = j0 + u * 256u;
           const uint64_t e = j < total ? entry_of(j) : qbase;
           k4[u] = q.key[e];
-          p4[u] = q.pix[e];
+          if constexpr (!PACKED) p4[u] = q.pix[e];
         }
 #pragma unroll
         for (uint32_t u = 0; u < 4u; u++)
@@ -1455,7 +1480,7 @@ __device__ __forceinline__ void tile_resolve_block(const RasterArgs& a, uint32_t
   for (int p = t; p < kQPixels; p += 256) {
     const uint32_t gx = x0 + (uint32_t)(p >> 6), gy = y0 + (uint32_t)(p & 63);
     if (gx < W && gy < H) {
-      const unsigned long long k = skeys[p];
+      const unsigned long long k = PACKED ? frag_key(skeys[p]) : skeys[p];   // (a background entry: {+inf, -1} again)
       const uint64_t g = (uint64_t)gx * H + gy;
       idx_out[g] = (uint32_t)(k & 0xFFFFFFFFull);
       if (depth_out) depth_out[g] = __uint_as_float((uint32_t)(k >> 32));
@@ -1475,8 +1500,9 @@ __device__ __forceinline__ bool view_needs_planes(const RasterArgs& a) { return 
 // (k_tile_resolve_group 41.6 against 51 us per eight cfg2 views, where a view or two of a group usually has a handful of queued triangles).
 // == 1: k_fuse_tri_any / _wide, whose k_fuse_big_any scans the planes of such views: one decision for the raster launch.
 
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_tile_resolve(RasterArgs a, uint32_t* __restrict__ idx_out, float* __restrict__ depth_out) {
-  tile_resolve_block(a, idx_out, depth_out, blockIdx.x, [&] { return view_needs_planes(a); });     // (idx_optional here: a view that is fused alone, smesh_fuse_view)
+  tile_resolve_block<PACKED>(a, idx_out, depth_out, blockIdx.x, [&] { return view_needs_planes(a); });     // (idx_optional here: a view that is fused alone, smesh_fuse_view)
 }
 
 __global__ __launch_bounds__(256) void k_raster_huge_group(RasterGroup g) {
@@ -1492,13 +1518,14 @@ __global__ __launch_bounds__(256) void k_raster_huge_group(RasterGroup g) {
 }
 
 // Several views in one launch (index planes only).
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_tile_resolve_group(RasterGroup g) {
   uint32_t v = 0;
   while (v + 1 < g.n && blockIdx.x >= g.tile_end[v]) v++;   // block-uniform, n <= kMaxGroup
   // the views of a raster launch are fused together (in launches of 8 / 4 / 2 / 1 of them): one decision for all of them (level 1) -- a view
   // without queued triangles of its own is still scanned for the triangles that are big in ANOTHER view of the launch (round 6: 2 of 7 500
   // random soups caught a per-view decision there, profiles/r06_differential_sweeps.txt) -- unless the fusion kernel does not do that (level 2)
-  tile_resolve_block(g.view[v], g.idx[v], nullptr, blockIdx.x - (v ? g.tile_end[v - 1] : 0u), [&] {
+  tile_resolve_block<PACKED>(g.view[v], g.idx[v], nullptr, blockIdx.x - (v ? g.tile_end[v - 1] : 0u), [&] {
     if (g.view[v].idx_optional == 2u) return view_needs_planes(g.view[v]);
     bool planes = false;
     for (uint32_t u = 0; u < g.n; u++) planes = planes || view_needs_planes(g.view[u]);
@@ -1508,11 +1535,12 @@ __global__ __launch_bounds__(256) void k_tile_resolve_group(RasterGroup g) {
 
 // k_tile_resolve_group for views whose DEPTH planes are read as well (smesh_renderer_fuse_views_gated): every plane of every view is
 // written -- the index plane, and the depth plane behind it in the view's slot of 8 W H bytes.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void k_tile_resolve_group_depth(RasterGroup g) {
   uint32_t v = 0;
   while (v + 1 < g.n && blockIdx.x >= g.tile_end[v]) v++;   // block-uniform, n <= kMaxGroup
   float* depth = reinterpret_cast<float*>(g.idx[v] + (uint64_t)g.view[v].W * g.view[v].H);
-  tile_resolve_block(g.view[v], g.idx[v], depth, blockIdx.x - (v ? g.tile_end[v - 1] : 0u), [] { return true; });
+  tile_resolve_block<PACKED>(g.view[v], g.idx[v], depth, blockIdx.x - (v ? g.tile_end[v - 1] : 0u), [] { return true; });
 }
 
 // Split the key image into the two output planes and re-arm the keys for the next render.
@@ -1767,6 +1795,12 @@ bool compact_records_wanted(smesh_renderer* r, smesh_aggregator* a, const smesh_
 }
 thread_local int g_last_record_format = 16;   // smesh_last_record_format()
 
+// Do the fragment queues of this renderer's next raster launch hold packed entries (fragments.hpp)?  The renderer's own property
+// (triangle primitives, every id below 2^22 -- with a prim_id table too: its values are caller ids below F) and the option, read per
+// launch: one process can run both formats, and a view slot's queues serve either.
+bool packed_fragments_wanted(const smesh_renderer* r) { return opt_packed_fragments() && frag_packed_allowed(r->texels, r->F); }
+thread_local int g_last_fragment_format = 10;   // smesh_last_fragment_format()
+
 // Consecutive triangle blocks per run of an XCD (xcd_block) in launches of 64 blocks and more (smaller ones: blocks take consecutive
 // triangles in dispatch order).  cfg2, eight views per launch (profiles/r06_raster_experiments.txt): k_raster_frag_group fetches
 // 149.6 MB in dispatch order, 79.1 MB with runs of 8 (x 2: gfx950's FETCH_SIZE unit) -- 562 -> 422 MB of traffic per launch -- and takes
@@ -1783,7 +1817,8 @@ uint64_t frag_cap_forced() {
 // (SMESH_FRAG_CAP overrides the capacity of a sub-queue; fragments beyond it fall back to the global key image), shrunk
 // if the whole set would exceed 8 GiB.  Returns false (queues unusable -> direct path) for images with so many tiles
 // that a sub-queue would drop under 256 slots.
-bool ensure_queues(smesh_renderer* r, smesh_renderer::ViewScratch& vs, uint64_t W, uint64_t H, hipStream_t st, int* status) {
+// `packed`: the launch stores packed entries in fq.key and needs no fq.pix; a slot gets that array with its first launch that does.
+bool ensure_queues(smesh_renderer* r, smesh_renderer::ViewScratch& vs, uint64_t W, uint64_t H, hipStream_t st, int* status, bool packed) {
   *status = SMESH_OK;
   const uint64_t tiles_x = div_up(W, kQW), tiles_y = div_up(H, kQH), ntiles = tiles_x * tiles_y;
   uint64_t cap = frag_cap_forced();   // per sub-queue
@@ -1801,7 +1836,7 @@ bool ensure_queues(smesh_renderer* r, smesh_renderer::ViewScratch& vs, uint64_t 
     vs.fq = FragQueues();
     vs.fq_tiles = 0;
     hipError_t e = dev_malloc(reinterpret_cast<void**>(&vs.fq.key), ntiles * kQSub * cap * 8);
-    if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&vs.fq.pix), ntiles * kQSub * cap * 2);
+    if (e == hipSuccess && !packed) e = dev_malloc(reinterpret_cast<void**>(&vs.fq.pix), ntiles * kQSub * cap * 2);
     if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&vs.fq.count), ntiles * kQSub * 4);
     if (e == hipSuccess) e = dev_malloc(reinterpret_cast<void**>(&vs.fq.flag), ntiles * 4);
     if (e == hipSuccess) e = hipMemsetAsync(vs.fq.count, 0, ntiles * kQSub * 4, st);
@@ -1809,6 +1844,10 @@ bool ensure_queues(smesh_renderer* r, smesh_renderer::ViewScratch& vs, uint64_t 
     if (e != hipSuccess) { *status = fail_hip(e, "fragment queue allocation", __FILE__, __LINE__); return false; }
     vs.fq.cap = (uint32_t)cap;
     vs.fq_tiles = ntiles;
+  }
+  if (!packed && !vs.fq.pix) {   // (a slot whose launches so far were all packed; nothing in flight reads the array)
+    const hipError_t e = dev_malloc(reinterpret_cast<void**>(&vs.fq.pix), vs.fq_tiles * kQSub * vs.fq.cap * 2);
+    if (e != hipSuccess) { vs.fq.pix = nullptr; *status = fail_hip(e, "fragment queue allocation", __FILE__, __LINE__); return false; }
   }
   vs.fq.tiles_y = (uint32_t)tiles_y;
   return true;
@@ -1921,6 +1960,8 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
   r->last_render_side = side;
   r->side[side].compact = false;
   g_last_record_format = 16;
+  g_last_fragment_format = 10;
+  const bool packed = packed_fragments_wanted(r);
   if (!st) {
     // plain render()/render_device(): main stream, after whatever smesh_fuse_view left on the raster stream
     st = ctx->stream;
@@ -1945,8 +1986,9 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
     a.idx_optional = (idx_optional && plane_optional_allowed(r)) ? (uint32_t)idx_optional : 0u;
     const uint32_t big_grid = (uint32_t)std::min<uint64_t>(r->F, (uint64_t)ctx->num_cus);
     int qs = SMESH_OK;
-    if (raster_path() == RasterPath::Frag && ensure_queues(r, vs, W, H, st, &qs)) {
+    if (raster_path() == RasterPath::Frag && ensure_queues(r, vs, W, H, st, &qs, packed)) {
       a.q = vs.fq;
+      if (packed) { a.q.pix = nullptr; g_last_fragment_format = 8; }
       if (compact && a.idx_optional == 2u && a.frags && !a.kinds) {   // (only the fragment-queue kernels know the format)
         a.compact = 1u;
         r->side[side].compact = true;
@@ -1956,7 +1998,10 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
         const uint32_t nblocks = (uint32_t)div_up(div_up(r->F, a.tpw), 4);
         const uint32_t chunk = nblocks >= 64u ? kRasterXcdRun : 0u;
         const dim3 grid(chunk ? 8u * xcd_slots(nblocks, chunk) : nblocks);
-        switch (raster_mode(a)) {
+        switch (raster_mode(a) | (packed ? 8 : 0)) {
+          case 11: hipLaunchKernelGGL(k_raster_frag<11>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
+          case 9:  hipLaunchKernelGGL(k_raster_frag<9>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
+          case 8:  hipLaunchKernelGGL(k_raster_frag<8>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
           case 7:  hipLaunchKernelGGL(k_raster_frag<7>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
           case 5:  hipLaunchKernelGGL(k_raster_frag<5>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
           case 4:  hipLaunchKernelGGL(k_raster_frag<4>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
@@ -1967,6 +2012,7 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
         if ((raster_mode(a) & 3) != 0 && a.balance) {    // the list the balanced instances left: four waves per SIMD's worth of waves walk it
           const dim3 mgrid(4u * (uint32_t)std::max(1, ctx->num_cus));
           if (a.tex_res) hipLaunchKernelGGL(k_raster_medium<true>, mgrid, dim3(256), 0, st, a);
+          else if (packed) hipLaunchKernelGGL((k_raster_medium<false, true>), mgrid, dim3(256), 0, st, a);
           else hipLaunchKernelGGL(k_raster_medium<false>, mgrid, dim3(256), 0, st, a);
         }
       }
@@ -1974,7 +2020,8 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
       const uint32_t ntiles = (uint32_t)(div_up(W, kQW) * div_up(H, kQH));
       if (!no_huge_possible(r, cam)) hipLaunchKernelGGL(k_raster_huge, dim3(std::min<uint32_t>(ntiles, 2u * (uint32_t)ctx->num_cus)), dim3(256), 0, st, a, ntiles);
       SMESH_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_tile_resolve, dim3((uint32_t)(div_up(W, kQW) * div_up(H, kQH))), dim3(256), 0, st, a, d_idx, d_depth);
+      if (packed) hipLaunchKernelGGL(k_tile_resolve<true>, dim3((uint32_t)(div_up(W, kQW) * div_up(H, kQH))), dim3(256), 0, st, a, d_idx, d_depth);
+      else hipLaunchKernelGGL(k_tile_resolve<false>, dim3((uint32_t)(div_up(W, kQW) * div_up(H, kQH))), dim3(256), 0, st, a, d_idx, d_depth);
       SMESH_HIP(hipGetLastError());
       return SMESH_OK;
     }
@@ -1998,17 +2045,21 @@ thread_local const char* g_last_raster_path = "none";   // smesh_last_raster_pat
 // kernel, from the code object, asked once.
 PipelineNeighbour raster_pipeline_neighbour(const smesh_renderer* r) {
   static std::once_flag once;
-  static uint32_t ml_vgprs = 96u, ml_lds = 0u, plain_vgprs = 96u, plain_lds = 0u;
+  static uint32_t vgprs[2][2] = {{96u, 96u}, {96u, 96u}}, lds[2][2] = {{0u, 0u}, {0u, 0u}};   // [meshlets][packed entries]
   std::call_once(once, [] {
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_raster_frag_group_ml<0>)) == hipSuccess) { ml_vgprs = (uint32_t)std::max(1, fa.numRegs); ml_lds = (uint32_t)fa.sharedSizeBytes; }
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_raster_frag_group<0>)) == hipSuccess) { plain_vgprs = (uint32_t)std::max(1, fa.numRegs); plain_lds = (uint32_t)fa.sharedSizeBytes; }
+    const void* const fn[2][2] = {{reinterpret_cast<const void*>(&k_raster_frag_group<0>), reinterpret_cast<const void*>(&k_raster_frag_group<8>)},
+                                  {reinterpret_cast<const void*>(&k_raster_frag_group_ml<0>), reinterpret_cast<const void*>(&k_raster_frag_group_ml<8>)}};
+    for (int m = 0; m < 2; m++)
+      for (int p = 0; p < 2; p++) {
+        hipFuncAttributes fa;
+        if (hipFuncGetAttributes(&fa, fn[m][p]) == hipSuccess) { vgprs[m][p] = (uint32_t)std::max(1, fa.numRegs); lds[m][p] = (uint32_t)fa.sharedSizeBytes; }
+      }
     (void)hipGetLastError();
   });
   PipelineNeighbour nb;
-  const bool meshlets = r->ml.tris != nullptr && opt_raster_meshlets();
-  nb.wg_vgprs = meshlets ? ml_vgprs : plain_vgprs;
-  nb.wg_lds = meshlets ? ml_lds : plain_lds;
+  const int meshlets = r->ml.tris != nullptr && opt_raster_meshlets() ? 1 : 0, packed = packed_fragments_wanted(r) ? 1 : 0;
+  nb.wg_vgprs = vgprs[meshlets][packed];
+  nb.wg_lds = lds[meshlets][packed];
   return nb;
 }
 
@@ -2049,7 +2100,7 @@ int prepare_group_slots(smesh_renderer* r, const smesh_camera_t* cams, int n, hi
     smesh_renderer::ViewScratch& vs = r->vs[base + v];
     SMESH_TRY(ensure_keys(vs, W, H, st));
     int qs = SMESH_OK;
-    if (!ensure_queues(r, vs, W, H, st, &qs)) return qs != SMESH_OK ? qs : fail(SMESH_ERR_RUNTIME, "fragment queues unavailable");
+    if (!ensure_queues(r, vs, W, H, st, &qs, packed_fragments_wanted(r))) return qs != SMESH_OK ? qs : fail(SMESH_ERR_RUNTIME, "fragment queues unavailable");
     if (r->fused[base + v].bytes < N * 8) {
       SMESH_HIP(hipStreamSynchronize(st));   // growing a slot frees the old buffer: nothing may still be reading it
       SMESH_HIP(hipStreamSynchronize(r->ctx->stream));
@@ -2067,6 +2118,8 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   if (!plane_optional_allowed(r) || with_depth) idx_optional = 0;
   compact = compact && idx_optional == 2 && !r->texels;
   g_last_record_format = compact ? 8 : 16;
+  const bool packed = packed_fragments_wanted(r);   // one decision for the launch: its views share the kernels
+  g_last_fragment_format = packed ? 8 : 10;
   DeviceCtx* ctx = r->ctx;
   ProjectGroup pg;
   RasterGroup rg;
@@ -2080,7 +2133,7 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
     smesh_renderer::ViewScratch& vs = r->vs[base + v];
     SMESH_TRY(ensure_keys(vs, W, H, st));
     int qs = SMESH_OK;
-    if (!ensure_queues(r, vs, W, H, st, &qs)) return qs != SMESH_OK ? qs : fail(SMESH_ERR_RUNTIME, "fragment queues unavailable");
+    if (!ensure_queues(r, vs, W, H, st, &qs, packed)) return qs != SMESH_OK ? qs : fail(SMESH_ERR_RUNTIME, "fragment queues unavailable");
     if (r->fused[side_base + v].bytes < N * 8) {
       SMESH_HIP(hipStreamSynchronize(st));   // growing a slot frees the old buffer: nothing may still be reading it
       SMESH_HIP(hipStreamSynchronize(r->ctx->stream));
@@ -2094,6 +2147,7 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
     { const RasterArgs own = raster_args(r, vs, side_base + v, W, H, 1, &cams[v]); rg.view[v].wg_push = own.wg_push; rg.view[v].balance = own.balance; }
     rg.view[v].cam = pg.cam[v];
     rg.view[v].q = vs.fq;
+    if (packed) rg.view[v].q.pix = nullptr;
     rg.view[v].idx_optional = (uint32_t)idx_optional;
     rg.view[v].compact = compact ? 1u : 0u;
     r->side[side_base + v].compact = compact;
@@ -2149,9 +2203,13 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
     const dim3 grid(rg.chunk ? 8u * xcd_slots(rg.blocks_per_view, rg.chunk) * (uint32_t)n : (uint32_t)n * rg.blocks_per_view);
     if (meshlets) {
       if (mode & 4) hipLaunchKernelGGL(k_raster_frag_group_ml<4>, grid, dim3(256), 0, st, rg);
+      else if (packed) hipLaunchKernelGGL(k_raster_frag_group_ml<8>, grid, dim3(256), 0, st, rg);
       else hipLaunchKernelGGL(k_raster_frag_group_ml<0>, grid, dim3(256), 0, st, rg);
     } else
-    switch (mode) {     // (one mode per launch: render_group_into made the views agree)
+    switch (mode | (packed ? 8 : 0)) {     // (one mode per launch: render_group_into made the views agree)
+      case 11: hipLaunchKernelGGL(k_raster_frag_group<11>, grid, dim3(256), 0, st, rg); break;
+      case 9:  hipLaunchKernelGGL(k_raster_frag_group<9>, grid, dim3(256), 0, st, rg); break;
+      case 8:  hipLaunchKernelGGL(k_raster_frag_group<8>, grid, dim3(256), 0, st, rg); break;
       case 7:  hipLaunchKernelGGL(k_raster_frag_group<7>, grid, dim3(256), 0, st, rg); break;
       case 5:  hipLaunchKernelGGL(k_raster_frag_group<5>, grid, dim3(256), 0, st, rg); break;
       case 4:  hipLaunchKernelGGL(k_raster_frag_group<4>, grid, dim3(256), 0, st, rg); break;
@@ -2162,6 +2220,7 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
     if ((raster_mode(rg.view[0]) & 3) != 0 && rg.view[0].balance) {
       const uint32_t per_view = std::max(64u, 4u * (uint32_t)std::max(1, ctx->num_cus) / (uint32_t)n);
       if (rg.view[0].tex_res) hipLaunchKernelGGL(k_raster_medium_group<true>, dim3((uint32_t)n * per_view), dim3(256), 0, st, rg, per_view);
+      else if (packed) hipLaunchKernelGGL((k_raster_medium_group<false, true>), dim3((uint32_t)n * per_view), dim3(256), 0, st, rg, per_view);
       else hipLaunchKernelGGL(k_raster_medium_group<false>, dim3((uint32_t)n * per_view), dim3(256), 0, st, rg, per_view);
     }
   }
@@ -2170,8 +2229,13 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   for (int v = 0; v < n; v++) huge_needed = huge_needed || !no_huge_possible(r, &cams[v]);
   if (huge_needed) hipLaunchKernelGGL(k_raster_huge_group, dim3(std::min<uint32_t>(tiles, 4u * (uint32_t)ctx->num_cus)), dim3(256), 0, st, rg);
   SMESH_HIP(hipGetLastError());
-  if (with_depth) hipLaunchKernelGGL(k_tile_resolve_group_depth, dim3(tiles), dim3(256), 0, st, rg);   // (the depth planes: behind the index planes, in the slots)
-  else hipLaunchKernelGGL(k_tile_resolve_group, dim3(tiles), dim3(256), 0, st, rg);
+  if (with_depth) {   // (the depth planes: behind the index planes, in the slots)
+    if (packed) hipLaunchKernelGGL(k_tile_resolve_group_depth<true>, dim3(tiles), dim3(256), 0, st, rg);
+    else hipLaunchKernelGGL(k_tile_resolve_group_depth<false>, dim3(tiles), dim3(256), 0, st, rg);
+  } else {
+    if (packed) hipLaunchKernelGGL(k_tile_resolve_group<true>, dim3(tiles), dim3(256), 0, st, rg);
+    else hipLaunchKernelGGL(k_tile_resolve_group<false>, dim3(tiles), dim3(256), 0, st, rg);
+  }
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }
@@ -2544,6 +2608,7 @@ const char* smesh_last_add_path(void) { return g_last_add_path; }
 const char* smesh_last_raster_path(void) { return g_last_raster_path; }
 }
 int smesh_last_record_format() { return g_last_record_format; }
+int smesh_last_fragment_format() { return g_last_fragment_format; }
 extern "C" {
 
 int smesh_renderer_create_triangles(const float* vertices, uint64_t V, const int32_t* faces, uint64_t F, int device,
