@@ -54,8 +54,14 @@ __device__ __forceinline__ float log_of_power(float p, float w) {
 //   * k_fuse_tri / fuse_box sum a view's contributions separately, from zero, in double, and fold them into (hi, lo) once per
 //     view in double: hi + lo carries ~48 bits;
 //   * a row is re-centred on its largest finite element whenever a view adds to it, so that hi stays a small number for the
-//     classes that matter -- which also keeps the kernels that only know the hi plane (any class count, texels, the generic
-//     scatter-add: their float32 additions stay valid, hi + lo is still the value) as accurate as float32 allows.
+//     classes that matter: after a fold the largest finite hi is at most the fold's largest |part| (plus the centre class's lo);
+//   * every other fold site treats the pair the same way -- the kernels for any class count and for wide rows (in slices of classes),
+//     the texel kernels (a texel of a big triangle once per view, from float64 scratch rows; every other texel per pixel), the generic
+//     scatter-add and the sparse primitives of the image records (float64 atomics into scratch rows, then one fold per touched
+//     row).  No Mul kernel adds float32 to the hi plane alone.
+//   * k_mul_normalise folds lo away (lo := 0) only for the readers that hand out one plane: get_raw, set_raw, raw_pointer, the exchange.
+// tests/test_gpu_mul_state.py holds every site to the bound of tests/mul_state_ref.py (2^-48 |t| per fold plus the double summation)
+// over runs of up to 256 views.
 template <int CT, bool EXACT>
 __device__ __forceinline__ float row_centre(const float (&r)[CT], int C) {
   float m = -INFINITY;

@@ -2107,8 +2107,9 @@ int launch_hist(const ScatterArgs& a, hipStream_t st) {
 
 // Mul only (fuse_tri.inc.hpp, "Mul state"): re-centre every row of the (hi, lo) accumulator pair on its largest finite element and
 // renormalise the pair (hi = the float32 nearest to the value, lo = the remainder; `fold`: lo := 0, the value rounded to the
-// hi plane alone -- what leaves the library as "the raw accumulator").  Runs ahead of the fusion kernels that only know the hi
-// plane, in get(), and before the raw accumulator is read or all-reduced.
+// hi plane alone -- what leaves the library as "the raw accumulator").  Without `fold` it runs ahead of the generic scatter-add and
+// of the launches for any class count and wide rows (which fold the pair themselves: the pass only re-centres it) and in get()
+// beyond the LDS tiles; with `fold` before the raw accumulator is read, set or all-reduced.
 namespace {
 __global__ void k_mul_normalise(float* __restrict__ acc, float* __restrict__ acc_lo, uint64_t P, uint32_t C, int fold) {
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -426,7 +426,8 @@ __global__ __launch_bounds__(kBlock) void k_rec_resolve_group(RecGroup g, uint32
 }
 
 // Pixels of the sparse primitives (k_rec_big), in pixel order: Mesh.h:94-106 with one float atomic per class.  One thread per pixel;
-// an image without sparse primitives -- every rendering -- leaves at the first test.  Mul adds on the hi plane (hi + lo is the value).
+// an image without sparse primitives -- every rendering -- leaves at the first test.  Mul adds float64 atomics to the aggregator's
+// scratch rows, which k_fold_sparse folds into the (hi, lo) pair once per image.
 // One pixel of pass D: Mesh.h:94-106 for a pixel of a sparse primitive, one float atomic per class.
 template <int KIND>
 __device__ __forceinline__ void scatter_sparse_pixel(uint64_t i, const uint32_t* __restrict__ idx, const float* __restrict__ probs,
