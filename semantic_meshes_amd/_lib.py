@@ -354,6 +354,24 @@ FACE_SEGMENTS_SIGNATURES = {
     "smesh_aggregator_face_segments_despeckle": (c_int, [c_void_p, c_void_p, c_u32, c_void_p, c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_lens.h: images from cameras with lens distortion,
+# undistorted on the device, product-only like the tables above (no profile slot)
+LENS_MODELS = ("SIMPLE_RADIAL", "RADIAL", "OPENCV", "FULL_OPENCV")     # COLMAP's polynomial models, subsets of FULL_OPENCV
+
+
+class LensPOD(ctypes.Structure):
+    """smesh_lens_t (include/smesh_lens.h)."""
+    _fields_ = [("focal", ctypes.c_double * 2), ("principal", ctypes.c_double * 2), ("k", ctypes.c_double * 6), ("p", ctypes.c_double * 2),
+                ("width", ctypes.c_uint64), ("height", ctypes.c_uint64)]
+
+
+LENS_SIGNATURES = {
+    "smesh_undistort_probs": (c_int, [c_void_p, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, c_u32, P(LensPOD), P(CameraPOD),
+                                      c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int]),
+    "smesh_undistort_pixels": (c_int, [c_void_p, c_int, c_int, P(ctypes.c_int64), c_int, c_u64, c_u64, P(LensPOD), P(CameraPOD),
+                                       c_void_p, c_void_p, c_void_p, c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -481,7 +499,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(EDGE_GATE_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(EDGE_GATE_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()) + list(LENS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

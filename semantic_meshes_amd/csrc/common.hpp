@@ -156,6 +156,9 @@ bool opt_probs_labels_tiles();
 // resize_vector: class-vector images whose layout allows it are resampled with 16-byte loads and stores (default on; 0: every image
 // takes the generic one-lane-per-element path; resize.hip).  Same results either way: a test hook.
 bool opt_resize_vector();
+// lens_vector: class-vector images whose layout allows it are undistorted with 16-byte loads and stores and one map per pixel in LDS
+// (default on; 0: every image takes the generic one-lane-per-element path; lens.hip).  Same results either way: a test hook.
+bool opt_lens_vector();
 // fuse_sampled: the entry points of smesh_sampled.h sample (w,h,C) class vectors inside k_fuse_tri_sampled where it serves the view
 // (default on; 0 / SMESH_FUSE_SAMPLED=0: every call resamples, then fuses; fusion_sampled.hip).  Same sums either way: a test hook.
 bool opt_fuse_sampled();

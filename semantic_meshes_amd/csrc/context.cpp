@@ -42,6 +42,9 @@ bool opt_probs_labels_tiles() { return g_probs_labels_tiles.load() != 0; }
 static std::atomic<int> g_resize_vector{1};   // (off: the generic path everywhere -- a test hook, resize.hip)
 bool opt_resize_vector() { return g_resize_vector.load() != 0; }
 
+static std::atomic<int> g_lens_vector{1};   // (off: the generic path everywhere -- a test hook, lens.hip)
+bool opt_lens_vector() { return g_lens_vector.load() != 0; }
+
 static std::atomic<int> g_points_grid{1};   // (off: the exhaustive scan -- a test hook, points.hip)
 bool opt_points_grid() { return g_points_grid.load() != 0; }
 
@@ -50,6 +53,8 @@ uint64_t smesh_label_colors_launches();    // label_colors.hip
 uint64_t smesh_depth_weights_launches();   // depth_weights.hip
 uint64_t smesh_view_weights_launches();    // view_weights.hip
 uint64_t smesh_edge_weights_launches();    // edge_weights.hip
+uint64_t smesh_lens_launches();            // lens.hip
+int smesh_last_lens_path();                // lens.hip: the calling thread's last launch
 void smesh_last_probs_labels_launch(uint64_t* grid, uint64_t* work);   // probs_labels.hip: the calling thread's last launch
 
 // "fuse_sampled" (fusion_sampled.hip): 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- a test hook, like
@@ -422,6 +427,8 @@ int smesh_set_option(const char* name, int64_t value) {
   if (!strcmp(name, "probs_labels_tiles")) { g_probs_labels_tiles.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // resize.hip: 0 sends every class-vector image down the generic one-lane-per-element path -- same images, same labels
   if (!strcmp(name, "resize_vector")) { g_resize_vector.store(value != 0 ? 1 : 0); return SMESH_OK; }
+  // lens.hip: 0 sends every class-vector image down the generic one-lane-per-element path -- same images, same weights, same counts
+  if (!strcmp(name, "lens_vector")) { g_lens_vector.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // fusion_sampled.hip: 0 sends every call of smesh_sampled.h down the resample-then-fuse route -- same sums
   if (!strcmp(name, "fuse_sampled")) { g_fuse_sampled.store(value != 0 ? 1 : 0); return SMESH_OK; }
   // points.hip: 0 makes smesh_surface_index_nearest scan all faces for every point -- same faces, same distances
@@ -467,6 +474,12 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "depth_weights_launches")) { *value = (int64_t)smesh_depth_weights_launches(); return SMESH_OK; }
   if (!strcmp(name, "view_weights_launches")) { *value = (int64_t)smesh_view_weights_launches(); return SMESH_OK; }
   if (!strcmp(name, "edge_weights_launches")) { *value = (int64_t)smesh_edge_weights_launches(); return SMESH_OK; }
+  // (smesh_lens.h): the test hook of lens.hip, and read-only this process's launches of its kernels
+  if (!strcmp(name, "lens_vector")) { *value = opt_lens_vector() ? 1 : 0; return SMESH_OK; }
+  if (!strcmp(name, "lens_launches")) { *value = (int64_t)smesh_lens_launches(); return SMESH_OK; }
+  // read-only, reporting (like "last_fuse_slot"): the path of the calling thread's last launch of lens.hip -- 0 none yet, 1 the vector
+  // form of k_undistort_probs, 2 its generic form, 3 k_undistort_pixels
+  if (!strcmp(name, "last_lens_path")) { *value = (int64_t)smesh_last_lens_path(); return SMESH_OK; }
   // read-only (smesh_probs_labels.h): the largest class count the tiled path serves
   if (!strcmp(name, "probs_labels_tile_max_classes")) { *value = (int64_t)kProbsLabelsTileMaxC; return SMESH_OK; }
   // read-only, reporting (like "last_fuse_slot"): the calling thread's last launch of k_probs_labels_tiled / _generic --

@@ -68,6 +68,83 @@ class Camera:
         return "Camera(resolution=%s, focal_lengths=%s)" % (self.resolution, self.focal_lengths.tolist())
 
 
+# COLMAP's polynomial lens models as slots of FULL_OPENCV (include/smesh_lens.h): model -> (parameter count, focal lengths,
+# principal point, indices of k1 .. k6 or None, indices of p1, p2 or None) in COLMAP's parameter order
+_LENS_LAYOUTS = {
+    "SIMPLE_RADIAL": (4, (0, 0), (1, 2), (3, None, None, None, None, None), (None, None)),                 # f cx cy k
+    "RADIAL": (5, (0, 0), (1, 2), (3, 4, None, None, None, None), (None, None)),                           # f cx cy k1 k2
+    "OPENCV": (8, (0, 1), (2, 3), (4, 5, None, None, None, None), (6, 7)),                                 # fx fy cx cy k1 k2 p1 p2
+    "FULL_OPENCV": (12, (0, 1), (2, 3), (4, 5, 8, 9, 10, 11), (6, 7)),                                     # ... k3 k4 k5 k6
+}
+
+
+class Lens:
+    """A polynomial lens (smesh_lens_t, include/smesh_lens.h): `focal`, `principal`, `k` (k1 .. k6) and `p` (p1, p2) as float64, and
+    the image size `resolution` = (wc, hc) they were calibrated at."""
+
+    def __init__(self, model, params, resolution, focal, principal, k, p):
+        self.model, self.params, self.resolution = model, tuple(params), (int(resolution[0]), int(resolution[1]))
+        self.focal, self.principal = np.asarray(focal, np.float64), np.asarray(principal, np.float64)
+        self.k, self.p = np.asarray(k, np.float64), np.asarray(p, np.float64)
+        pod = _lib.LensPOD()
+        pod.focal[:] = [float(v) for v in self.focal]
+        pod.principal[:] = [float(v) for v in self.principal]
+        pod.k[:] = [float(v) for v in self.k]
+        pod.p[:] = [float(v) for v in self.p]
+        pod.width, pod.height = self.resolution
+        self._pod = pod
+
+    @property
+    def is_identity(self):
+        """No distortion at all: k and p are zero."""
+        return not (self.k.any() or self.p.any())
+
+    def __repr__(self):
+        return "Lens(%s, params=%s, resolution=%s)" % (self.model, list(self.params), self.resolution)
+
+
+class LensCamera(Camera):
+    """A camera with lens distortion: a `Camera` whose pinhole part is the VIEW that gets rendered, and `.lens`, the sensor's
+    polynomial lens (include/smesh_lens.h).  `resolution`, `focal_lengths`, `principal_point`: the sensor's calibration size, f and c;
+    `model`: "SIMPLE_RADIAL", "RADIAL", "OPENCV" or "FULL_OPENCV"; `params`: the model's distortion parameters in COLMAP's order (k |
+    k1 k2 | k1 k2 p1 p2 | k1 k2 p1 p2 k3 k4 k5 k6) -- or the whole line of cameras.txt, f and c included, which must then agree with
+    `focal_lengths` and `principal_point`.  The view defaults to the lens's own f,
+    c and size -- OpenCV's undistort with newCameraMatrix = cameraMatrix --, `view_focal_lengths`, `view_principal_point` and
+    `view_resolution` choose another.  The lens keeps its parameters in double; the view's are rounded to float32 like every Camera's.
+    The fusion calls take images on this camera's sensor grid with `undistort=True` (fusion.py); fisheye, FOV and thin-prism models
+    are refused by name."""
+
+    def __init__(self, rotation, translation, resolution, focal_lengths, principal_point, model, params,
+                 view_focal_lengths=None, view_principal_point=None, view_resolution=None):
+        model = str(model)
+        if model not in _LENS_LAYOUTS:
+            raise ValueError("lens model %s is not supported: only %s (the fisheye, FOV and thin-prism models need atan, which cannot "
+                             "be pinned to the bit)" % (model, ", ".join(_lib.LENS_MODELS)))
+        count, fi, ci, ki, pi = _LENS_LAYOUTS[model]
+        params = [float(v) for v in np.asarray(params, dtype=np.float64).reshape(-1)]
+        f = _arr(focal_lengths, "focal_lengths", 1, _FLOATS, (2,)).astype(np.float64)
+        c = _arr(principal_point, "principal_point", 1, _FLOATS, (2,)).astype(np.float64)
+        head = len(set(fi)) + 2
+        if len(params) == count - head:        # the distortion parameters alone: f and c are the arguments before them
+            params = [float(f[0]), float(f[1])][:len(set(fi))] + [float(c[0]), float(c[1])] + params
+        elif len(params) != count:
+            raise ValueError("lens model %s takes %d parameters (%d without f and c), got %d" % (model, count, count - head, len(params)))
+        elif [params[i] for i in fi] != list(f) or [params[i] for i in ci] != list(c):
+            raise ValueError("focal_lengths / principal_point %s %s differ from those in params %s" % (f, c, params))
+        if not np.all(np.isfinite(params)) or not (f[0] > 0 and f[1] > 0):
+            raise ValueError("lens parameters must be finite and the focal lengths > 0, got %s" % (params,))
+        res = _arr(resolution, "resolution", 1, _INTS, (2,))
+        super().__init__(rotation, translation, res if view_resolution is None else view_resolution,
+                         f if view_focal_lengths is None else view_focal_lengths, c if view_principal_point is None else view_principal_point)
+        if int(res[0]) <= 0 or int(res[1]) <= 0:
+            raise ValueError("resolution must be positive, got %s" % (res,))
+        self.default_view = view_focal_lengths is None and view_principal_point is None and view_resolution is None
+        self.lens = Lens(model, params, res, f, c, [0.0 if i is None else params[i] for i in ki], [0.0 if i is None else params[i] for i in pi])
+
+    def __repr__(self):
+        return "LensCamera(resolution=%s, focal_lengths=%s, lens=%r)" % (self.resolution, self.focal_lengths.tolist(), self.lens)
+
+
 class Mesh:
     """Triangle mesh as the renderer consumes it: float32[V,3] vertices, int32[F,3] faces
     (what data::Ply hands TriangleRenderer, /root/reference/include/semantic_meshes/data/Ply.h:14-15)."""
@@ -369,7 +446,8 @@ class Colmap:
             return dict(width=int(width), height=int(height), f=(fx, fy), c=(cx, cy))
         # other models may sit in a workspace unused: the error is raised by getCamera() for an image that needs one
         # (the reference's Camera holds only the two pinhole variants, include/semantic_meshes/render/Camera.h:9-12)
-        return dict(width=int(width), height=int(height), unsupported=str(model))
+        # (the parameters are kept for getLensCamera(), which serves the polynomial models among them)
+        return dict(width=int(width), height=int(height), unsupported=str(model), params=tuple(float(v) for v in params))
 
     def _read_cameras(self, path):
         cams = {}
@@ -451,3 +529,30 @@ class Colmap:
 
     def getCameras(self):
         return [self.getCamera(i) for i in range(len(self._images))]
+
+    def getLensCamera(self, image_id):
+        """`getCamera` for workspaces whose cameras have lens distortion: a `LensCamera` for COLMAP's four polynomial models
+        (SIMPLE_RADIAL, RADIAL, OPENCV, FULL_OPENCV), whose view is the lens's own f, c and size; a plain `Camera` for the two pinhole
+        models; ValueError, by name, for every other model."""
+        index = image_id if isinstance(image_id, (int, np.integer)) else self.getImageIndex(image_id)
+        if not 0 <= index < len(self._images):
+            raise IndexError("image index %d out of range" % index)
+        im = self._images[index]
+        cam = self._cameras[im["camera_id"]]
+        if "unsupported" not in cam:
+            return self.getCamera(index)
+        model = cam["unsupported"]
+        if model not in _LENS_LAYOUTS:
+            raise ValueError("COLMAP camera model %s of image %r is not supported (only SIMPLE_PINHOLE, PINHOLE, %s)"
+                             % (model, im["name"], ", ".join(_lib.LENS_MODELS)))
+        count, fi, ci, _, _ = _LENS_LAYOUTS[model]
+        params = cam["params"][:count]
+        if len(params) != count:
+            raise ValueError("COLMAP camera model %s of image %r needs %d parameters, got %d" % (model, im["name"], count, len(params)))
+        return LensCamera(_qvec_to_rotation(im["q"]), np.asarray(im["t"], dtype=np.float64),
+                          np.asarray([cam["width"], cam["height"]], dtype=np.int64),
+                          np.asarray([params[i] for i in fi], dtype=np.float64), np.asarray([params[i] for i in ci], dtype=np.float64),
+                          model, params)
+
+    def getLensCameras(self):
+        return [self.getLensCamera(i) for i in range(len(self._images))]

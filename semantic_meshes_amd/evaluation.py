@@ -305,19 +305,44 @@ class ConfusionMatrix:
                                                         ctypes.c_void_p(lp), P, lmem, ctypes.c_void_p(gp), gcode, _c64(gstr), gmem, W, H))
         self._done(streams, [k0, k1, k2])
 
-    def add_view(self, renderer, camera, labels, gt, gt_resize=None, gt_map=None, gt_palette=None):
-        """Rasterise `camera` with `renderer` and score the view against `gt` (W,H) = camera.resolution (`gt_resize`, `gt_map`,
-        `gt_palette`: see add_image)."""
-        self.add_views(renderer, [camera], labels, [gt], gt_resize, gt_map, gt_palette)
+    def _undistorted_gt(self, gt, camera, gt_map, gt_palette, what):
+        """Ground truth on the sensor grid of a `data.LensCamera`, at any size, as that camera's pinhole view sees it
+        (include/smesh_lens.h, `fusion.undistort_labels_device`): sampled nearest, with a value no class has where the view looks past
+        the sensor, so those pixels count in `ignored`.  With `gt_map` / `gt_palette` the image is first turned into classes at its
+        own size -- both work pixel by pixel, so the order does not matter -- and the plane's don't-care code is the fill."""
+        from .lens import _undistort_pixels, is_plain
+        gshape = tuple(getattr(gt, "shape", None) or np.shape(gt))
+        if is_plain(camera, gshape):
+            return gt, gt_map, gt_palette
+        if gt_map is not None or gt_palette is not None:
+            gt = self._prepared_gt(gt, None, None, gt_map, what, gt_palette)
+        dt = np.dtype(getattr(gt, "dtype", None) or np.asarray(gt).dtype)
+        if dt.kind not in "iu" or (dt.kind == "u" and np.iinfo(dt).max < self.classes):
+            raise ValueError("%s: %s has no value left for the pixels outside the sensor beside %d classes" % (what, dt, self.classes))
+        return _undistort_pixels(gt, camera, -1 if dt.kind == "i" else np.iinfo(dt).max, self.device, what), None, None
 
-    def add_views(self, renderer, cameras, labels, gt_images, gt_resize=None, gt_map=None, gt_palette=None):
+    def add_view(self, renderer, camera, labels, gt, gt_resize=None, gt_map=None, gt_palette=None, gt_undistort=False):
+        """Rasterise `camera` with `renderer` and score the view against `gt` (W,H) = camera.resolution (`gt_resize`, `gt_map`,
+        `gt_palette`: see add_image; `gt_undistort`: see add_views)."""
+        self.add_views(renderer, [camera], labels, [gt], gt_resize, gt_map, gt_palette, gt_undistort)
+
+    def add_views(self, renderer, cameras, labels, gt_images, gt_resize=None, gt_map=None, gt_palette=None, gt_undistort=False):
         """`add_view` for a batch: up to eight views share their rasteriser launches.  Ground-truth images that share dtype, strides
         and memory go to the library as one batch; a mixed list is scored view by view.  `gt_resize`, `gt_map`, `gt_palette`: see
-        add_image."""
+        add_image.  `gt_undistort=True`: the ground truth of every `data.LensCamera` is on that lens's sensor grid, at any size; it is
+        undistorted on the device first, sampled nearest, and the pixels where the view looks past the sensor are ignored.  Not
+        together with `gt_resize=`."""
         cameras, gt_images = list(cameras), list(gt_images)
         n = len(cameras)
         if len(gt_images) != n:
             raise ValueError("add_views needs one ground-truth image per camera")
+        if gt_undistort:
+            if gt_resize is not None:
+                raise ValueError("add_views: gt_undistort=True cannot be combined with gt_resize= (the sensor image is undistorted at any size)")
+            done = [self._undistorted_gt(gt_images[i], cam, gt_map, gt_palette, "ground truth %d" % i) for i, cam in enumerate(cameras)]
+            gt_images = [d[0] if d[1] is None and d[2] is None else self._prepared_gt(d[0], tuple(cam.resolution), None, d[1], "ground truth %d" % i, d[2])
+                         for i, (d, cam) in enumerate(zip(done, cameras))]
+            gt_map = gt_palette = None
         if gt_resize is not None or gt_map is not None or gt_palette is not None:
             gt_images = [self._prepared_gt(gt_images[i], tuple(cam.resolution), gt_resize, gt_map, "ground truth %d" % i, gt_palette)
                          for i, cam in enumerate(cameras)]

@@ -967,6 +967,92 @@ class _MeshAggregator:
             return self._gated_labels(label_images[i], W, H, resize, m, streams, "label image %d" % i)
         return self._fuse_views_gated(renderer, cameras, prepare, wts, sensors, gate, depth_stats, what, spec, view_stats, edge, edge_stats)
 
+    # ---- undistort=True (include/smesh_lens.h, lens.py): images on the sensor grid of a data.LensCamera ---------------------------
+    def _fuse_views_undistorted(self, what, labels, renderer, cameras, images, weights_images, probs_dtype, resize, sample_in_kernel,
+                                label_map, palette, sensor_depths, single, **gates):
+        """The `undistort=True` form of fuse_view(s) / fuse_view(s)_labels: the batch is worked through in chunks of eight views -- the
+        views of a fusion launch, so at most eight undistorted images are alive at once.  Every image handed over for a
+        `data.LensCamera` is on that lens's sensor grid, at any size: a class-vector image becomes its undistorted (W,H,C) plane
+        and its validity weights plane (the caller's (W,H) weights multiplied in), a mask its nearest-sampled plane with the
+        don't-care code outside (a mask with `label_map=` / `palette=` is first turned into classes at its own size: the map is per
+        pixel, so the order does not matter), a sensor depth image its nearest-sampled plane with 0, "missing", outside.  Each run
+        of consecutive lens views, and each run of views that need nothing (a plain `Camera`; a lens without distortion seen
+        through its default view at the image's size), then goes through the call without the keyword: the same additions as
+        fusing those planes by hand, in the same order."""
+        from .device import to_device
+        from .lens import _undistort_pixels, _undistort_probs, is_plain
+        from .resize import image_size
+        if resize is not None or sample_in_kernel:
+            raise ValueError("%s: undistort=True cannot be combined with resize= or sample_in_kernel=True (the sensor image is "
+                             "undistorted at any size)" % what)
+        cameras, images = list(cameras), list(images)
+        n = len(cameras)
+        wts = None if weights_images is None else list(weights_images)
+        sensors = None if sensor_depths is None else list(sensor_depths)
+        if len(images) != n or (wts is not None and len(wts) != n) or (sensors is not None and len(sensors) != n):
+            raise ValueError("%s needs one image (and one weights image or None, one sensor depth image) per camera" % what)
+        m = _palette_or_map(palette, label_map, images, self.classes, self.device) if (labels and n) else None
+        table = m if isinstance(m, ColorTable) else None
+        lmap = None if table is not None else m
+        size_of = self._shape_of if labels else image_size
+        plain = [is_plain(cam, size_of(img)) for cam, img in zip(cameras, images)]
+
+        def call(lo, hi, imgs, w, s, through):
+            if labels:
+                return self.fuse_views_labels(renderer, cameras[lo:hi], imgs, w, label_map=lmap if through else None,
+                                              palette=table if through else None, sensor_depths=s, **gates)
+            return self.fuse_views(renderer, cameras[lo:hi], imgs, w, probs_dtype=probs_dtype, sensor_depths=s, **gates)
+
+        # (every image is checked before the first chunk is fused)
+        if labels and not all(plain):
+            if m is not None and self.classes > 65535:
+                raise ValueError("%s: label_map= / palette= need an aggregator of at most 65535 classes" % what)
+            for i in range(n):
+                if plain[i] or m is not None:
+                    continue
+                dt = np.dtype(getattr(images[i], "dtype", None) or np.asarray(images[i]).dtype)
+                if dt.kind not in "iu":
+                    raise ValueError("label image %d must have an integer dtype, got %s" % (i, dt))
+                if dt.kind == "u" and np.iinfo(dt).max < self.classes:
+                    raise ValueError("label image %d: %s has no value left for don't care beside %d classes" % (i, dt, self.classes))
+        parts = [call(0, n, images, wts, sensors, True)] if all(plain) else []      # (nothing to undistort: the plain call)
+        for lo in ([] if parts else range(0, n, GROUP_VIEWS)):
+            hi = min(lo + GROUP_VIEWS, n)
+            imgs, w, s = list(images[lo:hi]), None if wts is None else list(wts[lo:hi]), None if sensors is None else list(sensors[lo:hi])
+            for j, i in enumerate(range(lo, hi)):
+                if plain[i]:
+                    continue
+                cam = cameras[i]
+                if labels:
+                    src = images[i] if m is None else prepare_labels_device(images[i], self.classes, None, None, lmap, self.device, table)
+                    dt = np.dtype(src.dtype)
+                    imgs[j] = _undistort_pixels(src, cam, -1 if dt.kind == "i" else np.iinfo(dt).max, self.device, "label image %d" % i, hold=self._hold)
+                    if w is not None and isinstance(w[j], np.ndarray):      # the caller's host weights go where the undistorted plane lives
+                        w[j] = to_device(np.ascontiguousarray(w[j], dtype=np.float32), self.device)
+                else:
+                    imgs[j], wj, _ = _undistort_probs(images[i], cam, None, probs_dtype, None if wts is None else wts[i], True, False, self.device,
+                                                      hold=self._hold)
+                    if w is None:
+                        w = [None] * (hi - lo)
+                    w[j] = wj
+                if s is not None:
+                    s[j] = _undistort_pixels(sensors[i], cam, 0, self.device, "sensor depth image %d" % i, hold=self._hold)
+            a = 0
+            for b in range(1, hi - lo + 1):      # runs of consecutive views that were, or were not, undistorted
+                if b == hi - lo or plain[lo + b] != plain[lo + a]:
+                    through = plain[lo + a]
+                    wr = None if (w is None or (through and wts is None)) else w[a:b]
+                    parts.append(call(lo + a, lo + b, imgs[a:b], wr, None if s is None else s[a:b], through))
+                    a = b
+        parts = [p for p in parts if p is not None]
+        if not parts:
+            return None
+        if isinstance(parts[0], tuple):
+            merged = tuple(np.concatenate([p[k] for p in parts]) for k in range(len(parts[0])))
+            return tuple(c[0] for c in merged) if single else merged
+        merged = np.concatenate(parts)
+        return merged[0] if single else merged
+
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
         self._pending = []      # (views nobody can ask the result of any more)
@@ -1251,9 +1337,17 @@ class _MeshAggregator:
                     k2 if (wp is not None and wmem == _lib.MEM_DEVICE) else None])
 
     def fuse_view_labels(self, renderer, camera, label_image, weights_image=None, resize=None, label_map=None, palette=None,
-                         sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
+                         sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False,
+                         undistort=False):
         """`fuse_view(renderer, camera, one_hot(label_image), weights_image)` without the one-hot (see add_labels, also for `resize`,
-        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate`, `depth_stats`, `view_weights`, `view_stats`, `edge_gate` and `edge_stats`)."""
+        `label_map` and `palette`; see fuse_views for `sensor_depth`, `depth_gate`, `depth_stats`, `view_weights`, `view_stats`, `edge_gate`,
+        `edge_stats` and `undistort`)."""
+        if undistort:
+            self.flush()      # (the views already deferred come first)
+            return self._fuse_views_undistorted("fuse_view_labels", True, renderer, [camera], [label_image], None if weights_image is None else [weights_image],
+                                                None, resize, False, label_map, palette, None if sensor_depth is None else [sensor_depth], True,
+                                                depth_gate=depth_gate, depth_stats=depth_stats, view_weights=view_weights, view_stats=view_stats,
+                                                edge_gate=edge_gate, edge_stats=edge_stats)
         sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, False, "fuse_view_labels")
         spec = _view_keywords(renderer, view_weights, view_stats, False, "fuse_view_labels")
         edge = _edge_keywords(edge_gate, edge_stats, False, "fuse_view_labels")
@@ -1328,7 +1422,8 @@ class _MeshAggregator:
             self._hold([d[5] for d, _ in desc] + [dw[1] for _, dw in desc])
 
     def fuse_views_labels(self, renderer, cameras, label_images, weights_images=None, resize=None, label_map=None, palette=None,
-                          sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
+                          sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False,
+                          undistort=False):
         """`fuse_views` for label images, in order (see add_labels): with a triangle renderer and a Sum / Summax aggregator up to eight
         views per fusion launch, each accumulator row read and written once for all of them.  Label images that share dtype, strides
         and memory go to the library as one batch; a mixed list is fused view by view.  `resize="nearest"` / `label_map` (see
@@ -1337,7 +1432,12 @@ class _MeshAggregator:
         is first updated with all the call's images, in their order -- their distinct colours are found on the device, eight images
         per synchronisation -- and must then hold no more colours than the aggregator has classes.
         `sensor_depths=`, `depth_gate=`, `depth_stats=`, `view_weights=`, `view_stats=`, `edge_gate=`, `edge_stats=`: see fuse_views --
-        the masks are prepared in chunks of eight, then weighted and gated."""
+        the masks are prepared in chunks of eight, then weighted and gated.  `undistort=True`: see fuse_views -- masks (and colour
+        masks) are sampled nearest, with the don't-care code where the view looks past the sensor."""
+        if undistort:
+            return self._fuse_views_undistorted("fuse_views_labels", True, renderer, cameras, label_images, weights_images, None, resize, False,
+                                                label_map, palette, sensor_depths, False, depth_gate=depth_gate, depth_stats=depth_stats,
+                                                view_weights=view_weights, view_stats=view_stats, edge_gate=edge_gate, edge_stats=edge_stats)
         cameras = list(cameras)
         sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), False, "fuse_views_labels")
         spec = _view_keywords(renderer, view_weights, view_stats, False, "fuse_views_labels")
@@ -1568,15 +1668,23 @@ class _MeshAggregator:
         return ModelRenderer(self)
 
     def fuse_view(self, renderer, camera, probs_image, weights_image=None, probs_dtype=None, resize=None, sample_in_kernel=False,
-                  sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
+                  sensor_depth=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False,
+                  undistort=False):
         """render(camera) + add(indices, probs) in one call without the indices leaving the device.  `probs_image`: contiguous (W,H,C)
         float32, float16 or bfloat16 (see add()); with `resize="bilinear"` any (w,h,C) image add() takes, resampled to the camera's
         resolution on the device first -- or, with `sample_in_kernel=True`, sampled inside the fusion kernel (see add(); one library
         call per view, after the views already deferred).  `sensor_depth=`, `depth_gate=`, `depth_stats=`: the view is gated by its
         sensor depth (see fuse_views); the views already deferred are handed over first, then this view is a call of its own.
         `view_weights=`, `view_stats=`, `edge_gate=`, `edge_stats=`: the view is weighted by its viewing geometry, gated at its
-        occlusion edges (see fuse_views), under the same rule for deferred views."""
+        occlusion edges (see fuse_views), under the same rule for deferred views.  `undistort=True`: `camera` is a `data.LensCamera` and
+        the images are on its sensor grid (see fuse_views); the views already deferred are handed over first."""
         from .resize import resize_mode
+        if undistort:
+            self.flush()
+            return self._fuse_views_undistorted("fuse_view", False, renderer, [camera], [probs_image], None if weights_image is None else [weights_image],
+                                                probs_dtype, resize, sample_in_kernel, None, None, None if sensor_depth is None else [sensor_depth], True,
+                                                depth_gate=depth_gate, depth_stats=depth_stats, view_weights=view_weights, view_stats=view_stats,
+                                                edge_gate=edge_gate, edge_stats=edge_stats)
         sensors = _gate_keywords(None if sensor_depth is None else [sensor_depth], depth_gate, depth_stats, 1, sample_in_kernel, "fuse_view")
         spec = _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, "fuse_view")
         edge = _edge_keywords(edge_gate, edge_stats, sample_in_kernel, "fuse_view")
@@ -1658,7 +1766,8 @@ class _MeshAggregator:
                 _lib.PROBS_F32 if code is None else code)
 
     def fuse_views(self, renderer, cameras, probs_images, weights_images=None, probs_dtype=None, resize=None, sample_in_kernel=False,
-                   sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False):
+                   sensor_depths=None, depth_gate=None, depth_stats=False, view_weights=None, view_stats=False, edge_gate=None, edge_stats=False,
+                   undistort=False):
         """`fuse_view` for a whole batch, in order (the loop of colorize_cityscapes_mesh.py:54-67 as one call).  With a
         triangle renderer and device-resident images the library rasterises and fuses up to eight views per launch: each
         accumulator row is read and written once for all of them.  All images must live in the same memory (host or device) and
@@ -1685,8 +1794,20 @@ class _MeshAggregator:
         (include/smesh_edge_gate.h) -- the cure for labels bleeding across occlusion edges, from the rendered depth alone, eight views
         per launch; it takes any renderer, combines with everything `view_weights=` combines with and runs between the view weights
         and the depth gate.  `edge_stats=True` returns the uint64 [n, 4] counts [visible, behind, front, silhouette] per view and
-        waits; the stats asked for come back in the order (view, edge, depth), a single one bare."""
+        waits; the stats asked for come back in the order (view, edge, depth), a single one bare.
+        `undistort=True` (include/smesh_lens.h, lens.py): every image handed over for a `data.LensCamera` -- class vectors, and
+        `sensor_depths` -- is on that lens's SENSOR grid, at any size (the network's included); the camera's pinhole part is the view
+        that is rendered.  The batch is worked through in chunks of eight: each image becomes its undistorted plane on the device,
+        bilinear by a rule defined to the bit, with a validity weights plane that is 0 where the view looks past the sensor (times
+        `weights_images`, which stay (W,H) planes of the view); sensor depth is sampled nearest, 0 outside.  The same additions as
+        fusing the planes of `undistort_probs_device` by hand, in the same order.  A plain `Camera` in the batch passes through
+        untouched, and so does a lens without distortion seen through its default view at the image's size.  Not together with
+        `resize=` or `sample_in_kernel=True`."""
         from .resize import image_size, resize_mode
+        if undistort:
+            return self._fuse_views_undistorted("fuse_views", False, renderer, cameras, probs_images, weights_images, probs_dtype, resize,
+                                                sample_in_kernel, None, None, sensor_depths, False, depth_gate=depth_gate, depth_stats=depth_stats,
+                                                view_weights=view_weights, view_stats=view_stats, edge_gate=edge_gate, edge_stats=edge_stats)
         cameras = list(cameras)
         sensors = _gate_keywords(sensor_depths, depth_gate, depth_stats, len(cameras), sample_in_kernel, "fuse_views")
         spec = _view_keywords(renderer, view_weights, view_stats, sample_in_kernel, "fuse_views")
@@ -1851,6 +1972,8 @@ from .evaluation import ConfusionMatrix, confusion_accuracy, confusion_iou, conf
 from .evaluation import argmax_labels, argmax_labels_device  # noqa: E402,F401
 from .label_images import LabelRenderer  # noqa: E402,F401
 from .resize import resize_probs, resize_probs_device  # noqa: E402,F401
+from .lens import (undistort_depth, undistort_depth_device, undistort_labels, undistort_labels_device, undistort_probs,  # noqa: E402,F401
+                   undistort_probs_device)
 from .mesh_results import FaceGraph, FaceSegments, PointTransfer, SurfaceIndex, VertexTransfer  # noqa: E402,F401
 from .label_colors import (ColorRemap, ColorTable, check_palette, describe_color_source, resolve_palette,  # noqa: E402,F401
                            unique_colors)
