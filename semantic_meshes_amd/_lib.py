@@ -552,6 +552,18 @@ def last_raster_path():
     return lib().smesh_last_raster_path().decode()
 
 
+RASTER_REPORT_FIELDS = ("kernel", "mode", "views", "tpw", "groups", "chunk", "stages")
+
+
+def last_raster_instance():
+    """Which instance the calling thread's last raster launch was, as a dict of the read-only options "last_raster_kernel" (0 none yet,
+    1 k_raster_frag, 2 k_raster_frag_group, 3 k_raster_frag_group_ml, 4 the direct path), "_mode" (the MODE template value: 1 wg_push,
+    2 spread waves, 4 texels, 8 packed fragments), "_views", "_tpw", "_groups", "_chunk" and "_stages" (1 a vertex stage ran,
+    2 k_raster_medium, 4 k_raster_huge, 8 the resolve wrote depth planes, 16 the packed resolve); deferred views are handed over first."""
+    flush_pending()
+    return {f: get_option("last_raster_" + f) for f in RASTER_REPORT_FIELDS}
+
+
 def set_option(name, value):
     """`smesh_set_option`: a run-time option by name (include/smesh.h), e.g. "raster_meshlets"."""
     check(lib().smesh_set_option(name.encode(), int(value)))

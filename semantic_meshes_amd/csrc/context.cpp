@@ -399,6 +399,7 @@ uint32_t smesh_last_fuse_lds_pad();                     // fusion.hip: dynamic L
 int smesh_last_fuse_beside();                           // fusion.hip: rasteriser workgroups per CU the last computed pad leaves room for
 int smesh_last_record_format();                         // raster.hip: bytes per record (8 or 16) the calling thread's last raster launch left
 int smesh_last_fragment_format();                       // raster.hip: bytes per queued fragment (8 or 10) of the calling thread's last raster launch
+int smesh_last_raster_report(int field);                // raster.hip: which instance the calling thread's last raster launch was ("last_raster_*")
 int smesh_last_fuse_probs_dtype();                     // raster.hip: SMESH_PROBS_* of the class vectors the calling thread's last fusion read
 
 extern "C" {
@@ -445,6 +446,16 @@ int smesh_get_option(const char* name, int64_t* value) {
   if (!strcmp(name, "packed_fragments")) { *value = opt_packed_fragments() ? 1 : 0; return SMESH_OK; }
   // read-only (reporting): bytes per queued fragment of the calling thread's last raster launch: 8 (fragments.hpp) or 10 (key + pixel; also before the first)
   if (!strcmp(name, "last_fragment_format")) { *value = (int64_t)smesh_last_fragment_format(); return SMESH_OK; }
+  // read-only (reporting): which instance the calling thread's last raster launch was, written by render_into / render_group_into from
+  // the values their launch expressions switch on -- "last_raster_kernel": 0 none yet, 1 k_raster_frag, 2 k_raster_frag_group,
+  // 3 k_raster_frag_group_ml, 4 the direct path; "_mode": the MODE template value (1 wg_push, 2 spread waves, 4 texels, 8 packed
+  // fragments); "_views", "_tpw" (triangles per wave), "_groups", "_chunk" (0 or the XCD run) of the launch; "_stages": 1 a vertex stage
+  // ran, 2 k_raster_medium(_group) was launched, 4 k_raster_huge(_group), 8 the resolve wrote depth planes, 16 it was the packed resolve
+  if (!strncmp(name, "last_raster_", 12)) {
+    static const char* const fields[7] = {"kernel", "mode", "views", "tpw", "groups", "chunk", "stages"};
+    for (int f = 0; f < 7; f++)
+      if (!strcmp(name + 12, fields[f])) { *value = (int64_t)smesh_last_raster_report(f); return SMESH_OK; }
+  }
   if (!strcmp(name, "pipeline_fit")) { *value = opt_pipeline_fit(); return SMESH_OK; }
   if (!strcmp(name, "pipeline_fuse_waves")) { *value = opt_pipeline_fuse_waves(); return SMESH_OK; }
   if (!strcmp(name, "pipeline_fuse_pad")) { *value = opt_pipeline_fuse_pad(); return SMESH_OK; }

@@ -1801,6 +1801,15 @@ thread_local int g_last_record_format = 16;   // smesh_last_record_format()
 bool packed_fragments_wanted(const smesh_renderer* r) { return opt_packed_fragments() && frag_packed_allowed(r->texels, r->F); }
 thread_local int g_last_fragment_format = 10;   // smesh_last_fragment_format()
 
+// Which instance the calling thread's last raster launch was (the read-only options "last_raster_*", smesh_last_raster_report()):
+// render_into and render_group_into fill it from the very values their launch expressions switch on, so a test can hold the
+// library's choice against the dispatch rules.  kernel: 0 none yet, 1 k_raster_frag, 2 k_raster_frag_group, 3 k_raster_frag_group_ml,
+// 4 the direct path (k_raster_small / k_raster_big: everything else stays 0 but `views` and the stage bits 0 and 3).
+// stages: bit 0 a vertex stage ran, bit 1 k_raster_medium(_group) was launched, bit 2 k_raster_huge(_group), bit 3 the resolve wrote
+// depth planes, bit 4 the resolve instance was the packed one.
+struct RasterReport { int kernel = 0, mode = 0, views = 0, tpw = 0, groups = 0, chunk = 0, stages = 0; };
+thread_local RasterReport g_last_raster;
+
 // Consecutive triangle blocks per run of an XCD (xcd_block) in launches of 64 blocks and more (smaller ones: blocks take consecutive
 // triangles in dispatch order).  cfg2, eight views per launch (profiles/r06_raster_experiments.txt): k_raster_frag_group fetches
 // 149.6 MB in dispatch order, 79.1 MB with runs of 8 (x 2: gfx950's FETCH_SIZE unit) -- 562 -> 422 MB of traffic per launch -- and takes
@@ -1961,6 +1970,10 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
   r->side[side].compact = false;
   g_last_record_format = 16;
   g_last_fragment_format = 10;
+  RasterReport& report = g_last_raster;
+  report = RasterReport();
+  report.kernel = 4;   // (until the fragment-queue launch says otherwise)
+  report.views = 1;
   const bool packed = packed_fragments_wanted(r);
   if (!st) {
     // plain render()/render_device(): main stream, after whatever smesh_fuse_view left on the raster stream
@@ -1979,9 +1992,11 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
     hipLaunchKernelGGL(k_project_vertices, dim3((uint32_t)div_up(r->V, 256)), dim3(256), 0, st, r->verts, r->V, ca, vs.sv,
                        r->side[side].big_count);
     SMESH_HIP(hipGetLastError());
+    report.stages |= 1;
   } else {
     SMESH_HIP(hipMemsetAsync(r->side[side].big_count, 0, 32, st));
   }
+  if (d_depth) report.stages |= 8;
   if (r->F) {
     a.idx_optional = (idx_optional && plane_optional_allowed(r)) ? (uint32_t)idx_optional : 0u;
     const uint32_t big_grid = (uint32_t)std::min<uint64_t>(r->F, (uint64_t)ctx->num_cus);
@@ -1998,7 +2013,10 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
         const uint32_t nblocks = (uint32_t)div_up(div_up(r->F, a.tpw), 4);
         const uint32_t chunk = nblocks >= 64u ? kRasterXcdRun : 0u;
         const dim3 grid(chunk ? 8u * xcd_slots(nblocks, chunk) : nblocks);
-        switch (raster_mode(a) | (packed ? 8 : 0)) {
+        const int instance = raster_mode(a) | (packed ? 8 : 0);
+        const bool medium_stage = (raster_mode(a) & 3) != 0 && a.balance;
+        report = RasterReport{1, instance, 1, (int)a.tpw, (int)a.groups, (int)chunk, report.stages | (medium_stage ? 2 : 0)};
+        switch (instance) {
           case 11: hipLaunchKernelGGL(k_raster_frag<11>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
           case 9:  hipLaunchKernelGGL(k_raster_frag<9>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
           case 8:  hipLaunchKernelGGL(k_raster_frag<8>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
@@ -2009,7 +2027,7 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
           case 1:  hipLaunchKernelGGL(k_raster_frag<1>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
           default: hipLaunchKernelGGL(k_raster_frag<0>, grid, dim3(256), 0, st, a, nblocks, chunk); break;
         }
-        if ((raster_mode(a) & 3) != 0 && a.balance) {    // the list the balanced instances left: four waves per SIMD's worth of waves walk it
+        if (medium_stage) {    // the list the balanced instances left: four waves per SIMD's worth of waves walk it
           const dim3 mgrid(4u * (uint32_t)std::max(1, ctx->num_cus));
           if (a.tex_res) hipLaunchKernelGGL(k_raster_medium<true>, mgrid, dim3(256), 0, st, a);
           else if (packed) hipLaunchKernelGGL((k_raster_medium<false, true>), mgrid, dim3(256), 0, st, a);
@@ -2018,8 +2036,10 @@ int render_into(smesh_renderer* r, const smesh_camera_t* cam, uint32_t* d_idx, f
       }
       SMESH_HIP(hipGetLastError());
       const uint32_t ntiles = (uint32_t)(div_up(W, kQW) * div_up(H, kQH));
-      if (!no_huge_possible(r, cam)) hipLaunchKernelGGL(k_raster_huge, dim3(std::min<uint32_t>(ntiles, 2u * (uint32_t)ctx->num_cus)), dim3(256), 0, st, a, ntiles);
+      const bool huge_stage = !no_huge_possible(r, cam);
+      if (huge_stage) hipLaunchKernelGGL(k_raster_huge, dim3(std::min<uint32_t>(ntiles, 2u * (uint32_t)ctx->num_cus)), dim3(256), 0, st, a, ntiles);
       SMESH_HIP(hipGetLastError());
+      report.stages |= (huge_stage ? 4 : 0) | (packed ? 16 : 0);
       if (packed) hipLaunchKernelGGL(k_tile_resolve<true>, dim3((uint32_t)(div_up(W, kQW) * div_up(H, kQH))), dim3(256), 0, st, a, d_idx, d_depth);
       else hipLaunchKernelGGL(k_tile_resolve<false>, dim3((uint32_t)(div_up(W, kQW) * div_up(H, kQH))), dim3(256), 0, st, a, d_idx, d_depth);
       SMESH_HIP(hipGetLastError());
@@ -2201,12 +2221,19 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   {
     rg.chunk = rg.blocks_per_view >= 64u ? kRasterXcdRun : 0u;
     const dim3 grid(rg.chunk ? 8u * xcd_slots(rg.blocks_per_view, rg.chunk) * (uint32_t)n : (uint32_t)n * rg.blocks_per_view);
+    // (one mode per launch: render_group_into made the views agree; the meshlet instances: texel keys are never packed)
+    const int instance = meshlets ? ((mode & 4) ? 4 : packed ? 8 : 0) : (mode | (packed ? 8 : 0));
+    const bool medium_stage = (raster_mode(rg.view[0]) & 3) != 0 && rg.view[0].balance;
+    g_last_raster = RasterReport{meshlets ? 3 : 2, instance, n, (int)rg.view[0].tpw, (int)rg.view[0].groups, (int)rg.chunk,
+                                 (meshlets ? 0 : 1) | (medium_stage ? 2 : 0)};
     if (meshlets) {
-      if (mode & 4) hipLaunchKernelGGL(k_raster_frag_group_ml<4>, grid, dim3(256), 0, st, rg);
-      else if (packed) hipLaunchKernelGGL(k_raster_frag_group_ml<8>, grid, dim3(256), 0, st, rg);
-      else hipLaunchKernelGGL(k_raster_frag_group_ml<0>, grid, dim3(256), 0, st, rg);
+      switch (instance) {
+        case 4:  hipLaunchKernelGGL(k_raster_frag_group_ml<4>, grid, dim3(256), 0, st, rg); break;
+        case 8:  hipLaunchKernelGGL(k_raster_frag_group_ml<8>, grid, dim3(256), 0, st, rg); break;
+        default: hipLaunchKernelGGL(k_raster_frag_group_ml<0>, grid, dim3(256), 0, st, rg); break;
+      }
     } else
-    switch (mode | (packed ? 8 : 0)) {     // (one mode per launch: render_group_into made the views agree)
+    switch (instance) {
       case 11: hipLaunchKernelGGL(k_raster_frag_group<11>, grid, dim3(256), 0, st, rg); break;
       case 9:  hipLaunchKernelGGL(k_raster_frag_group<9>, grid, dim3(256), 0, st, rg); break;
       case 8:  hipLaunchKernelGGL(k_raster_frag_group<8>, grid, dim3(256), 0, st, rg); break;
@@ -2217,7 +2244,7 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
       case 1:  hipLaunchKernelGGL(k_raster_frag_group<1>, grid, dim3(256), 0, st, rg); break;
       default: hipLaunchKernelGGL(k_raster_frag_group<0>, grid, dim3(256), 0, st, rg); break;
     }
-    if ((raster_mode(rg.view[0]) & 3) != 0 && rg.view[0].balance) {
+    if (medium_stage) {
       const uint32_t per_view = std::max(64u, 4u * (uint32_t)std::max(1, ctx->num_cus) / (uint32_t)n);
       if (rg.view[0].tex_res) hipLaunchKernelGGL(k_raster_medium_group<true>, dim3((uint32_t)n * per_view), dim3(256), 0, st, rg, per_view);
       else if (packed) hipLaunchKernelGGL((k_raster_medium_group<false, true>), dim3((uint32_t)n * per_view), dim3(256), 0, st, rg, per_view);
@@ -2229,6 +2256,7 @@ int render_group_into(smesh_renderer* r, const smesh_camera_t* cams, int n, hipS
   for (int v = 0; v < n; v++) huge_needed = huge_needed || !no_huge_possible(r, &cams[v]);
   if (huge_needed) hipLaunchKernelGGL(k_raster_huge_group, dim3(std::min<uint32_t>(tiles, 4u * (uint32_t)ctx->num_cus)), dim3(256), 0, st, rg);
   SMESH_HIP(hipGetLastError());
+  g_last_raster.stages |= (huge_needed ? 4 : 0) | (with_depth ? 8 : 0) | (packed ? 16 : 0);
   if (with_depth) {   // (the depth planes: behind the index planes, in the slots)
     if (packed) hipLaunchKernelGGL(k_tile_resolve_group_depth<true>, dim3(tiles), dim3(256), 0, st, rg);
     else hipLaunchKernelGGL(k_tile_resolve_group_depth<false>, dim3(tiles), dim3(256), 0, st, rg);
@@ -2609,6 +2637,13 @@ const char* smesh_last_raster_path(void) { return g_last_raster_path; }
 }
 int smesh_last_record_format() { return g_last_record_format; }
 int smesh_last_fragment_format() { return g_last_fragment_format; }
+// The fields of the calling thread's last raster launch in the order of the options "last_raster_kernel", "_mode", "_views", "_tpw",
+// "_groups", "_chunk", "_stages" (context.cpp); -1 for any other index.
+int smesh_last_raster_report(int field) {
+  const RasterReport& g = g_last_raster;
+  const int v[7] = {g.kernel, g.mode, g.views, g.tpw, g.groups, g.chunk, g.stages};
+  return field >= 0 && field < 7 ? v[field] : -1;
+}
 extern "C" {
 
 int smesh_renderer_create_triangles(const float* vertices, uint64_t V, const int32_t* faces, uint64_t F, int device,
