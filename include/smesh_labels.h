@@ -19,7 +19,14 @@
  * not labels; smesh_last_fuse_kernel names the kernel from the class count alone): "last_fuse_slot" is the class-count slot handed
  * to k_fuse_tri -- 5, 13, 19, 20, 21, 40 for the exact instances, 8, 16, 24, 32, 41, 48 for the run-time-C instances with 8, 16, 24,
  * 32, 40 and 48 register slots --, 0 when the launch was k_fuse_tri_any, k_fuse_tri_wide or k_fuse_tri_wide_list, -1 before the
- * first such launch; "last_fuse_views" is the number of views of that launch (1, 2, 4 or 8).
+ * first such launch; "last_fuse_views" is the number of views of that launch (1, 2, 4 or 8).  For a k_fuse_tri_labels launch
+ * "last_fuse_slot" is 0, "last_fuse_views" its views, and the read-only "last_fuse_labels_form" reports the rest of the instance: the
+ * bytes per label of the planes it read (1: uint8, 2: uint16), plus 16 where the rows were kept in LDS; 0 before the first launch.
+ * "last_fuse_flagged_views" (read-only; also for k_fuse_tri_h16 and k_fuse_tri_sampled): bit v is set when view v of that launch had
+ * its "check the masks against the index plane" flag up (fragment-queue overflow, direct rasteriser).  It is read back from the
+ * device when asked -- the call waits for the device -- and reads 0 once any renderer has been destroyed since that launch.
+ * "compute_units" (read-only): the compute units of device 0 as the library sizes launches by them (these kernels' tail blocks:
+ * 16 per unit).
  *
  * Conventions are those of smesh.h: label images are (W,H) with y fastest, strides in ELEMENTS and >= 0, every function
  * returns a status, SMESH_ERR_INVALID for a bad dtype, stride or shape.

@@ -401,6 +401,8 @@ int smesh_last_record_format();                         // raster.hip: bytes per
 int smesh_last_fragment_format();                       // raster.hip: bytes per queued fragment (8 or 10) of the calling thread's last raster launch
 int smesh_last_raster_report(int field);                // raster.hip: which instance the calling thread's last raster launch was ("last_raster_*")
 int smesh_last_fuse_probs_dtype();                     // raster.hip: SMESH_PROBS_* of the class vectors the calling thread's last fusion read
+int smesh_last_fuse_flagged_views(int64_t* mask);       // fusion.hip: which views of the calling thread's last label / 16-bit / sampled launch had their masks flagged
+int smesh_last_labels_form();                         // fusion_labels.hip: label bytes (+ 16: rows in LDS) of the calling thread's last k_fuse_tri_labels launch
 
 extern "C" {
 
@@ -468,6 +470,21 @@ int smesh_get_option(const char* name, int64_t* value) {
   // read-only (smesh_half.h): the largest class count k_fuse_tri_h16 serves; the dtype of the class vectors the last fusion read
   if (!strcmp(name, "half_max_classes")) { *value = (int64_t)kHalfMaxClasses; return SMESH_OK; }
   if (!strcmp(name, "last_fuse_probs_dtype")) { *value = (int64_t)smesh_last_fuse_probs_dtype(); return SMESH_OK; }
+  // read-only, reporting: the calling thread's last k_fuse_tri_labels launch -- bytes per label of its planes (1: uint8, 2: uint16),
+  // plus 16 where the main waves kept their rows in LDS; 0 before the first such launch
+  if (!strcmp(name, "last_fuse_labels_form")) { *value = (int64_t)smesh_last_labels_form(); return SMESH_OK; }
+  // read-only, reporting: bit v is set when view v of the calling thread's last k_fuse_tri_labels / _h16 / _sampled launch had its
+  // "check the masks" flag up (fragment-queue overflow, direct rasteriser).  Read back from the device when asked: waits for it, and
+  // holds only while the renderer of that launch is alive; 0 before the first such launch
+  if (!strcmp(name, "last_fuse_flagged_views")) return smesh_last_fuse_flagged_views(value);
+  // read-only, reporting: the compute units the library sizes its launches by on device 0 (the tail blocks of the triangle-order
+  // fusion kernels: 16 per unit)
+  if (!strcmp(name, "compute_units")) {
+    DeviceCtx* ctx;
+    SMESH_TRY(get_ctx(0, &ctx));
+    *value = (int64_t)ctx->num_cus;
+    return SMESH_OK;
+  }
   // read-only: up to this class count k_confusion keeps a workgroup's histogram in LDS, beyond it adds straight into global memory
   if (!strcmp(name, "confusion_lds_max_classes")) { *value = (int64_t)kConfusionLdsMaxC; return SMESH_OK; }
   if (!strcmp(name, "confusion_wave_aggregate")) { *value = opt_confusion_wave_aggregate() ? 1 : 0; return SMESH_OK; }

@@ -276,6 +276,7 @@ dim3 fuse_rows_grid(DeviceCtx* ctx, uint64_t F, uint32_t big_capacity, const Ren
   t->big_capacity = big_capacity;
   t->tri_blocks = (uint32_t)div_up(F, kWave);
   t->big_blocks = no_big ? 0u : 16u * (uint32_t)std::max(1, ctx->num_cus);
+  smesh_note_fuse_rows_views(ctx, views, nviews);   // (reporting only: the read-only option "last_fuse_flagged_views")
   return dim3(t->tri_blocks + t->big_blocks);
 }
 

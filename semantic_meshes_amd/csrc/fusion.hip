@@ -31,6 +31,7 @@
 #include "half_scratch.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <new>
@@ -2488,6 +2489,41 @@ uint32_t smesh_last_fuse_lds_pad() { return g_last_fuse_lds_pad; }
 int smesh_last_fuse_beside() { return g_last_fuse_beside; }
 void smesh_last_fuse_instance(int* slot, int* views) { *slot = g_last_fuse_slot; *views = g_last_fuse_views; }
 void smesh_set_last_fuse_instance(int slot, int views) { g_last_fuse_slot = slot; g_last_fuse_views = views; }   // (fusion_sampled.hip: register slots, views)
+
+// Reporting only (read-only option "last_fuse_flagged_views"): where the views of the calling thread's last k_fuse_tri_labels /
+// _h16 / _sampled launch keep their "check the masks" flag (RenderedView::big_len[1]); read back when asked, never by a launch.
+// The flags live in the renderer's scratch: a renderer destroyed since the launch (smesh_note_renderer_destroyed, raster.hip) may
+// have been that launch's, so the note then counts as gone and the option reads 0 -- freed memory is never read.
+static std::atomic<uint64_t> g_renderers_destroyed{0};
+void smesh_note_renderer_destroyed() { g_renderers_destroyed.fetch_add(1); }
+static thread_local const uint32_t* g_last_rows_len[8] = {};
+static thread_local int g_last_rows_views = 0;
+static thread_local DeviceCtx* g_last_rows_ctx = nullptr;
+static thread_local uint64_t g_last_rows_epoch = 0;
+void smesh_note_fuse_rows_views(DeviceCtx* ctx, const RenderedView* views, int nviews) {
+  g_last_rows_ctx = ctx;
+  g_last_rows_epoch = g_renderers_destroyed.load();
+  g_last_rows_views = std::min(nviews, 8);
+  for (int v = 0; v < g_last_rows_views; v++) g_last_rows_len[v] = views[v].big_len;
+}
+// Bit v: view v of that launch had its flag up.  Waits for the launch's device; 0 once any renderer has been destroyed since.
+int smesh_last_fuse_flagged_views(int64_t* mask) {
+  *mask = 0;
+  DeviceCtx* ctx = g_last_rows_ctx;
+  if (!g_last_rows_views || !ctx) return SMESH_OK;
+  std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+  if (g_last_rows_epoch != g_renderers_destroyed.load()) { g_last_rows_views = 0; return SMESH_OK; }
+  SMESH_HIP(hipSetDevice(ctx->device));
+  SMESH_HIP(hipStreamSynchronize(ctx->raster_stream));
+  uint32_t flag[8] = {};
+  for (int v = 0; v < g_last_rows_views; v++)
+    SMESH_HIP(hipMemcpyAsync(&flag[v], g_last_rows_len[v] + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  SMESH_HIP(hipStreamSynchronize(ctx->stream));
+  if (g_last_rows_epoch != g_renderers_destroyed.load()) { g_last_rows_views = 0; return SMESH_OK; }   // (destroyed by another thread meanwhile)
+  for (int v = 0; v < g_last_rows_views; v++)
+    if (flag[v]) *mask |= (int64_t)1 << v;
+  return SMESH_OK;
+}
 
 // `nviews` = 1, 2, 4 or 8 (smesh_aggregator_max_fused_views): views[0], views[1] ... of the same renderer in one launch.
 // `part` / `nparts`: only the triangles of smesh_fuse_part_rows(F, part, nparts) -- the queued medium triangles (fuse_mid_entries, float

@@ -34,6 +34,7 @@ int smesh_aggregator_refuse_scattered(smesh_aggregator* a, const char* what);
 void smesh_aggregator_label_target(smesh_aggregator* a, float** acc, uint64_t* P, uint32_t* C, int* kind, float* iew);
 HalfScratch& smesh_aggregator_half_scratch(smesh_aggregator* a);
 void smesh_set_last_fuse_instance(int slot, int views);
+void smesh_note_fuse_rows_views(DeviceCtx* ctx, const RenderedView* views, int nviews);
 // raster.hip
 struct smesh_renderer;
 DeviceCtx* smesh_renderer_ctx(smesh_renderer* r);

@@ -39,6 +39,7 @@ LabelScratch& smesh_aggregator_label_scratch(smesh_aggregator* a);
 struct smesh_renderer;
 DeviceCtx* smesh_renderer_ctx(smesh_renderer* r);
 void smesh_set_last_fuse_instance(int slot, int views);
+void smesh_note_fuse_rows_views(DeviceCtx* ctx, const RenderedView* views, int nviews);
 int smesh_renderer_fuse_views_labels(smesh_renderer* r, smesh_aggregator* a, const smesh_camera_t* cams, uint64_t n, const void* const* planes,
                                      const float* const* weights, const ViewInput& in);
 int smesh_renderer_add_rendered_input(smesh_aggregator* a, smesh_renderer* r, const uint32_t* idx_dev, const ViewInput& in, const float* weights,
@@ -459,6 +460,11 @@ bool smesh_labels_native(smesh_aggregator* a, uint64_t F, uint64_t N) {
   return kind != SMESH_AGG_MUL && F != 0 && N >= 8 && smesh_aggregator_can_fuse_triangles(a, F);
 }
 
+// Reporting only (the read-only option "last_fuse_labels_form"): the instance of the calling thread's last k_fuse_tri_labels launch
+// beyond its view count -- bytes per label of the planes (1 or 2), plus 16 where the rows were kept in LDS; 0 before the first launch.
+static thread_local int g_last_labels_form = 0;
+int smesh_last_labels_form() { return g_last_labels_form; }
+
 // views[v].image: dense narrow planes of `label_bytes` (1 or 2) bytes per pixel in device memory.  `nviews` = 1, 2, 4 or 8.
 int smesh_labels_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_capacity, const RenderedView* views, int nviews, int label_bytes) {
   DeviceCtx* ctx = smesh_aggregator_ctx(a);
@@ -489,6 +495,7 @@ int smesh_labels_fuse_triangles(smesh_aggregator* a, uint64_t F, uint32_t big_ca
     if (label_bytes == 1) launch(uint8_t(), NV);
     else launch(uint16_t(), NV);
   });
+  g_last_labels_form = label_bytes + (in_lds ? 16 : 0);
   SMESH_HIP(hipGetLastError());
   return SMESH_OK;
 }

@@ -49,6 +49,7 @@ bool smesh_aggregator_takes_strided_probs(smesh_aggregator* a, int64_t ps0, int6
 int smesh_aggregator_dense_probs(smesh_aggregator* a, const float* d_probs, const int64_t ps[3], uint64_t W, uint64_t H, const float** out);
 bool smesh_aggregator_fuses_small_views_by_mask(smesh_aggregator* a);
 bool smesh_aggregator_reads_compact_records(smesh_aggregator* a);
+void smesh_note_renderer_destroyed();
 int smesh_aggregator_fuse_triangles(smesh_aggregator* a, uint64_t F, const uint32_t* prim_id, uint32_t big_capacity,
                                     const RenderedView* views, int nviews, int part = 0, int nparts = 1);
 void smesh_fuse_part_rows(uint64_t F, int part, int nparts, uint64_t* f_lo, uint64_t* f_hi);
@@ -2765,6 +2766,7 @@ int smesh_renderer_create_texels(const float* vertices, uint64_t V, const int32_
 
 int smesh_renderer_destroy(smesh_renderer_t* r) {
   if (!r) return SMESH_OK;
+  smesh_note_renderer_destroyed();   // (fusion.hip: "last_fuse_flagged_views" no longer reads this renderer's flags)
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->raster_stream);
   (void)hipStreamSynchronize(r->ctx->stream);
