@@ -30,7 +30,8 @@
  *   from rows   where the input is rows (an aggregator), labels is what the finishing step of smesh_vertices.h gives for every row
  *               with SMESH_VTX_ANNOTATIONS and dont_care_threshold: the class with the largest value, the lowest one among equals,
  *               -1 where the row's total is below the threshold.
- * Per-segment areas and per-segment vote sums would need an ordered float reduction per segment; they are not part of this header.
+ * Per-segment areas and per-segment vote sums need an ordered float reduction per segment; they are not part of this header but of
+ * smesh_segment_stats.h, which states that reduction to the bit.
  *
  * Conventions are those of smesh.h and smesh_face_graph.h: every function returns a status, SMESH_ERR_INVALID for a bad argument
  * (NULL, a bad memory kind, P != F, different devices, C == 0, a reduce-scattered accumulator).  Every call returns when its

@@ -354,6 +354,21 @@ FACE_SEGMENTS_SIGNATURES = {
     "smesh_aggregator_face_segments_despeckle": (c_int, [c_void_p, c_void_p, c_u32, c_void_p, c_int]),
 }
 
+# name -> (restype, argtypes); one entry per symbol declared in include/smesh_segment_stats.h: fused rows and areas pooled over the
+# segments, and the despeckle by a per-segment measure, product-only like the tables above (no profile slot)
+_SS_POOL_TAIL = [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int]      # face weights, their memkind, mode, threshold, outs
+SEGMENT_STATS_SIGNATURES = {
+    "smesh_segment_stats_face_areas": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    "smesh_segment_stats_members": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "smesh_segment_stats_pool": (c_int, [c_void_p, c_void_p, c_int, c_u32] + _SS_POOL_TAIL),
+    "smesh_segment_stats_pool_faces": (c_int, [c_void_p, c_void_p, c_int, c_u32] + _SS_POOL_TAIL),
+    "smesh_aggregator_segment_stats_pool": (c_int, [c_void_p, c_void_p] + _SS_POOL_TAIL),
+    "smesh_aggregator_segment_stats_pool_faces": (c_int, [c_void_p, c_void_p] + _SS_POOL_TAIL),
+    "smesh_segment_stats_despeckle_labels": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, P(c_u64), P(c_u64)]),
+    "smesh_segment_stats_despeckle_rows": (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_int, c_u32, c_void_p, c_int]),
+    "smesh_aggregator_segment_stats_despeckle": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int]),
+}
+
 # name -> (restype, argtypes); one entry per symbol declared in include/smesh_lens.h: images from cameras with lens distortion,
 # undistorted on the device, product-only like the tables above (no profile slot)
 LENS_MODELS = ("SIMPLE_RADIAL", "RADIAL", "OPENCV", "FULL_OPENCV")     # COLMAP's polynomial models, subsets of FULL_OPENCV
@@ -499,7 +514,7 @@ def lib():
                         "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback." % LIB_PATH)
                 _preload_hip_runtime()
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(EDGE_GATE_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()) + list(LENS_SIGNATURES.items()):
+                for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(HALF_SIGNATURES.items()) + list(VERTEX_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LABEL_IMAGE_SIGNATURES.items()) + list(MESHLET_SIGNATURES.items()) + list(PROBS_LABELS_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) + list(SAMPLED_SIGNATURES.items()) + list(LABEL_PREP_SIGNATURES.items()) + list(LABEL_COLORS_SIGNATURES.items()) + list(POINTS_SIGNATURES.items()) + list(DEPTH_SIGNATURES.items()) + list(VIEW_WEIGHTS_SIGNATURES.items()) + list(EDGE_GATE_SIGNATURES.items()) + list(FACE_GRAPH_SIGNATURES.items()) + list(FACE_SEGMENTS_SIGNATURES.items()) + list(SEGMENT_STATS_SIGNATURES.items()) + list(LENS_SIGNATURES.items()):
                     fn = getattr(L, name)  # AttributeError if the library does not export the ABI
                     fn.restype = res
                     fn.argtypes = args

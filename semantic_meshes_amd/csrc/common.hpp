@@ -334,6 +334,28 @@ int smesh_vertex_map_tables(const smesh_vertex_map* m, smesh::DeviceCtx** ctx, c
 struct smesh_face_graph;
 int smesh_face_graph_tables(const smesh_face_graph* graph, smesh::DeviceCtx** ctx, const uint32_t** offsets, const uint32_t** neighbours,
                             uint64_t* F, uint64_t* nnz);
+// What the per-segment results (segment_stats.hip) need from face_segments.hip: the device tables of a set of segments, and the slot
+// of its member table.  The member table belongs to the handle, which frees it; segment_stats.hip builds it on first use with the
+// context locked: offsets[S + 1] (the exclusive scan of size), members[labelled] (every segment's faces, ascending, back to back),
+// chunk_start[S + 1] (the exclusive scan of ceil(size / 256)), partial_start[S + 1] (the same over the segments of more than one
+// chunk), and the two totals.
+namespace smesh {
+struct SegmentMembers {
+  uint32_t *offsets = nullptr, *members = nullptr, *chunk_start = nullptr, *partial_start = nullptr;
+  uint64_t chunks = 0, partials = 0;
+  bool built = false;
+};
+struct SegmentTables {
+  DeviceCtx* ctx;
+  uint64_t F, S, labelled;
+  const int32_t* ids;       // [F]
+  const int32_t* labels;    // [F]
+  const uint32_t* size;     // [S]
+  SegmentMembers* members;
+};
+}  // namespace smesh
+struct smesh_face_segments;
+int smesh_face_segments_tables(smesh_face_segments* segments, smesh::SegmentTables* out);
 // What the confusion matrices (eval.hip) need from a renderer: `n` views (at most eight) rasterised on the context's main stream with
 // FULLY WRITTEN index planes, and `use(view, idx, W, H)` called for each with the renderer and its context locked -- what `use`
 // queues on the main stream reads the plane before anything overwrites it.  `P` must be the renderer's primitive count.

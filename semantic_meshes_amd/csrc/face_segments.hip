@@ -34,6 +34,7 @@ struct smesh_face_segments {
   uint32_t* first_face = nullptr;  // [S]
   int32_t* seg_label = nullptr;    // [S]
   uint32_t* size = nullptr;        // [S]
+  SegmentMembers members;          // built on first use by segment_stats.hip, under the context lock
 };
 
 namespace {
@@ -125,24 +126,7 @@ __global__ __launch_bounds__(kBlock) void k_seg_hook(const uint32_t* __restrict_
   }
 }
 
-// Counters: a kernel that counts runs a capped grid (kCountBlocks workgroups striding over the items) and every workgroup adds its
-// lanes' counts once.  One add per wave of a 1 M-face launch is 15 625 adds to one word, which took 0.19 ms whatever the kernel did
-// besides (measured: k_seg_flatten, k_seg_despeckle_labels); 2 048 adds do not show.
-constexpr uint32_t kCountBlocks = 2048;
-
-__device__ __forceinline__ void block_count_add(uint32_t mine, unsigned long long* counter) {
-  __shared__ uint32_t per_wave[kBlock / kWave];
-  for (int d = kWave >> 1; d > 0; d >>= 1) mine += __shfl_xor(mine, d, kWave);
-  if ((threadIdx.x & (kWave - 1)) == 0) per_wave[threadIdx.x / kWave] = mine;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t n = 0;
-    for (int w = 0; w < kBlock / kWave; w++) n += per_wave[w];
-    if (n) atomicAdd(counter, (unsigned long long)n);
-  }
-}
-
-dim3 count_grid(uint64_t n) { return dim3((uint32_t)std::min<uint64_t>(div_up(n, kBlock), kCountBlocks)); }
+#include "count.inc.hpp"  // kCountBlocks, block_count_add, count_grid
 
 // After the launch boundary plain loads are fresh.  root[f] = the root above f (a separate array: nobody reads what this launch
 // writes); flag[f] = 1 for a labelled root -- a segment's first face -- and flag[F] = 0, so that the exclusive scan over F + 1
@@ -252,7 +236,8 @@ __global__ __launch_bounds__(kBlock) void k_seg_despeckle_rows(const T* __restri
 dim3 grid_for(uint64_t n) { return dim3((uint32_t)div_up(n, kBlock)); }
 
 void free_segments(smesh_face_segments* sg) {
-  for (void* p : {(void*)sg->ids, (void*)sg->labels, (void*)sg->first_face, (void*)sg->seg_label, (void*)sg->size})
+  for (void* p : {(void*)sg->ids, (void*)sg->labels, (void*)sg->first_face, (void*)sg->seg_label, (void*)sg->size, (void*)sg->members.offsets,
+                  (void*)sg->members.members, (void*)sg->members.chunk_start, (void*)sg->members.partial_start})
     if (p) (void)dev_free(p);
   delete sg;
 }
@@ -363,6 +348,12 @@ int despeckle_device_rows(const smesh_face_segments* sg, DeviceCtx* ctx, uint32_
 }
 
 }  // namespace
+
+int smesh_face_segments_tables(smesh_face_segments* sg, SegmentTables* out) {
+  if (!sg) return fail(SMESH_ERR_INVALID, "NULL face segments");
+  *out = {sg->ctx, sg->F, sg->S, sg->labelled, sg->ids, sg->labels, sg->size, &sg->members};
+  return SMESH_OK;
+}
 
 extern "C" {
 

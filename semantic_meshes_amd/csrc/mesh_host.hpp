@@ -1,6 +1,6 @@
-// mesh_host.hpp -- the host plumbing that the mesh-side results share (vertices.hip, points.hip, face_graph.hip, face_segments.hip):
-// the device blocks of one call, inputs and outputs that live on the host or on the device, and the handles' destroy / adjacency /
-// owner check.  Host code only.  Included by those four files and by nothing else.
+// mesh_host.hpp -- the host plumbing that the mesh-side results share (vertices.hip, points.hip, face_graph.hip, face_segments.hip,
+// segment_stats.hip): the device blocks of one call, inputs and outputs that live on the host or on the device, and the handles'
+// destroy / adjacency / owner check.  Host code only.  Included by those five files and by nothing else.
 #pragma once
 
 #include "common.hpp"

@@ -1,5 +1,5 @@
-"""Results on the fused mesh beyond its faces (include/smesh_vertices.h, smesh_points.h, smesh_face_graph.h, smesh_face_segments.h):
-VertexTransfer, SurfaceIndex, PointTransfer, FaceGraph and FaceSegments, and the plumbing they share -- a library handle that is
+"""Results on the fused mesh beyond its faces (include/smesh_vertices.h, smesh_points.h, smesh_face_graph.h, smesh_face_segments.h,
+smesh_segment_stats.h): VertexTransfer, SurfaceIndex, PointTransfer, FaceGraph and FaceSegments, and the plumbing they share -- a library handle that is
 destroyed with its owner, the faces check, a `source` of face rows resolved once, and a fresh result on the host or in HBM.
 `fusion` re-exports the classes; that is where callers find them."""
 import ctypes
@@ -112,6 +112,27 @@ def _dense_rows(source, rows, what, device, streams):
         keep = np.ascontiguousarray(keep)
         ptr = keep.ctypes.data
     return ptr, mem, int(shape[1]), keep
+
+
+def _dense_vector(values, n, what, per, device, streams):
+    """(pointer or None, memkind, keep-alive) of an optional float32 vector of `n` elements (`per`: what it has one element of), dense,
+    on the host or on `device`."""
+    if values is None:
+        return None, _lib.MEM_HOST, None
+    if isinstance(values, np.ndarray) and values.dtype != np.float32:
+        raise ValueError("%s must be float32, got %s" % (what, values.dtype))
+    _same_device(values, device, what)
+    ptr, mem, shape, dt, strides, keep = describe(values, 1, what, device, streams)
+    if dt != np.float32:
+        raise ValueError("%s must be float32, got %s" % (what, dt))
+    if shape[0] != n:
+        raise ValueError("%s must have %s (%d), got %d" % (what, per, n, shape[0]))
+    if shape[0] > 1 and strides[0] != 1:
+        if mem != _lib.MEM_HOST:
+            raise ValueError("%s must be dense" % what)
+        keep = np.ascontiguousarray(keep)
+        ptr = keep.ctypes.data
+    return ctypes.c_void_p(ptr), mem, keep
 
 
 class VertexTransfer(_Handle):
@@ -383,22 +404,28 @@ class FaceGraph(_Handle):
 
     def _entry_weights(self, weights, streams):
         """(pointer or None, memkind, keep-alive) of per-entry weights: float32, `num_entries` elements, dense, on this device."""
-        if weights is None:
-            return None, _lib.MEM_HOST, None
-        if isinstance(weights, np.ndarray) and weights.dtype != np.float32:
-            raise ValueError("weights must be float32, got %s" % weights.dtype)
-        _same_device(weights, self.device, "weights")
-        wptr, wmem, wshape, wdt, wstrides, wkeep = describe(weights, 1, "weights", self.device, streams)
-        if wdt != np.float32:
-            raise ValueError("weights must be float32, got %s" % wdt)
-        if wshape[0] != self.num_entries:
-            raise ValueError("weights must have one element per entry of the graph (%d), got %d" % (self.num_entries, wshape[0]))
-        if wshape[0] > 1 and wstrides[0] != 1:
-            if wmem != _lib.MEM_HOST:
-                raise ValueError("weights must be dense")
-            wkeep = np.ascontiguousarray(wkeep)
-            wptr = wkeep.ctypes.data
-        return ctypes.c_void_p(wptr), wmem, wkeep
+        return _dense_vector(weights, self.num_entries, "weights", "one element per entry of the graph", self.device, streams)
+
+    # ---- face areas --------------------------------------------------------------------------------------------------------------
+    def _face_areas(self, vertices, on_device):
+        streams = []
+        ptr, mem, N, keep = _dense_points(vertices, self.device, streams)
+        if N != self.num_vertices:
+            raise ValueError("vertices must be float32[%d,3], got %d rows" % (self.num_vertices, N))
+        out, pout, omem = _out((self.num_faces,), np.float32, self.device, on_device)
+        _lib.check(_lib.lib().smesh_segment_stats_face_areas(self._h, self._faces.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ptr), mem,
+                                                            pout, omem))
+        release_to(self.device, streams)
+        return out
+
+    def face_areas(self, vertices):
+        """float32 [F]: the area of every face (include/smesh_segment_stats.h), half the length of the normal that `normal_weights()`
+        uses; +0 for a face without area.  `vertices`: float32 [V,3], numpy or a dense device array."""
+        return self._face_areas(vertices, False)
+
+    def face_areas_device(self, vertices):
+        """`face_areas()` left in HBM: what `FaceSegments.areas*` and `pool*(face_weights=...)` take."""
+        return self._face_areas(vertices, True)
 
     # ---- propagation -------------------------------------------------------------------------------------------------------------
     def _run(self, source, fg_mode, iterations, alpha, observed_threshold, weights, out_mode, threshold, want_rows, want_labels, on_device,
@@ -544,7 +571,9 @@ class FaceSegments(_Handle):
     `despeckle_*(min_faces)`: a face is kept when its segment has at least `min_faces` faces; `despeckle_labels*` gives the labels
     with every other face at -1 (a label table like any other, for `LabelRenderer`, `ConfusionMatrix.add*`, `PointTransfer`);
     `despeckle_sums*` gives the rows of `source` with the rows of removed faces zeroed, a source for `FaceGraph.fill_*`, which
-    lets the surroundings grow back in.  Everything is an integer result: two calls agree in every bit."""
+    lets the surroundings grow back in.  Everything is an integer result: two calls agree in every bit.
+    `members()`, `pool*`, `pooled_face_*`, `areas()` and `despeckle_*_by(measure, minimum)` (include/smesh_segment_stats.h) add up
+    what the faces of a segment carry, in a stated order, so these float results agree in every bit too."""
 
     _destroy = "smesh_face_segments_destroy"
 
@@ -626,3 +655,153 @@ class FaceSegments(_Handle):
     def despeckle_sums_device(self, source, min_faces):
         """`despeckle_sums()` left in HBM: a `source` for `FaceGraph.fill_*`."""
         return self._despeckle_sums(source, min_faces, True)
+
+    # ---- pooled rows, areas and the despeckle by a measure (include/smesh_segment_stats.h) ------------------------------------------
+    # The pooled row of a segment is the float32 sum of its faces' rows (each times its face weight, where given) in ascending face
+    # order: 256 faces to a chunk sum, the chunk sums one after another.  Two calls agree in every bit.  `source` is what it is for
+    # `despeckle_sums`; `face_weights` and `measure` are float32 vectors, numpy or device.
+    def _members(self, on_device):
+        offsets, po, mem = _out((self.count + 1,), np.uint32, self.device, on_device)
+        members, pm, mem = _out((self.num_labelled,), np.uint32, self.device, on_device)
+        _lib.check(_lib.lib().smesh_segment_stats_members(self._h, po, pm, mem))
+        return offsets, members
+
+    def members(self):
+        """`(offsets uint32[count+1], members uint32[num_labelled])`: the faces of segment s, ascending, are
+        `members[offsets[s]:offsets[s+1]]`."""
+        return self._members(False)
+
+    def members_device(self):
+        """`members()` left in HBM."""
+        return self._members(True)
+
+    def _areas(self, face_areas, on_device):
+        streams = []
+        pa, amem, keep = _dense_vector(face_areas, self.num_faces, "face_areas", "one element per face", self.device, streams)
+        if pa is None:
+            raise ValueError("face_areas is required")
+        out, pout, omem = _out((self.count,), np.float32, self.device, on_device)
+        _lib.check(_lib.lib().smesh_segment_stats_pool(self._h, pa, amem, 1, None, _lib.MEM_HOST, _lib.VTX_SUMS, 0.0, pout, None, omem))
+        release_to(self.device, streams)
+        return out
+
+    def areas(self, face_areas):
+        """float32 [count]: the area of every segment, `pool_sums(face_areas[:, None])[:, 0]`; `face_areas`: `FaceGraph.face_areas*()`."""
+        return self._areas(face_areas, False)
+
+    def areas_device(self, face_areas):
+        """`areas()` left in HBM: a `measure` for `despeckle_*_by`."""
+        return self._areas(face_areas, True)
+
+    def _pool(self, source, face_weights, mode, threshold, want_labels, on_device, faces):
+        streams = []
+        pw, wmem, wkeep = _dense_vector(face_weights, self.num_faces, "face_weights", "one element per face", self.device, streams)
+        src = _Source(source, self.num_faces, self.device, "the segments", "FaceSegments", streams)
+        rows, labels, outs = _rows_and_labels(self.num_faces if faces else self.count, src.classes, self.device, not want_labels, want_labels,
+                                              on_device)
+        name = "pool_faces" if faces else "pool"
+        if src.is_aggregator:
+            # (`_h`: the aggregator's deferred views are handed to the library first, as get() does)
+            _lib.check(getattr(_lib.lib(), "smesh_aggregator_segment_stats_" + name)(source._h, self._h, pw, wmem, mode, float(threshold), *outs))
+        else:
+            _lib.check(getattr(_lib.lib(), "smesh_segment_stats_" + name)(self._h, src.ptr, src.memkind, src.classes, pw, wmem, mode,
+                                                                          float(threshold), *outs))
+        src.finish()
+        return labels if want_labels else rows
+
+    def pool_sums(self, source, face_weights=None):
+        """float32 [count,C]: the pooled rows as they are."""
+        return self._pool(source, face_weights, _lib.VTX_SUMS, 0.0, False, False, False)
+
+    def pool(self, source, face_weights=None, dont_care_threshold=0.9):
+        """float32 [count,C]: the pooled rows divided by their total; all-zero rows where the total is below `dont_care_threshold`."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, False, False)
+
+    def pool_labels(self, source, face_weights=None, dont_care_threshold=0.9):
+        """int32 [count]: the class with the largest pooled value (the lowest one among equals), -1 where don't care."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, False)
+
+    def pool_sums_device(self, source, face_weights=None):
+        """`pool_sums()` left in HBM."""
+        return self._pool(source, face_weights, _lib.VTX_SUMS, 0.0, False, True, False)
+
+    def pool_device(self, source, face_weights=None, dont_care_threshold=0.9):
+        """`pool()` left in HBM."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, False)
+
+    def pool_labels_device(self, source, face_weights=None, dont_care_threshold=0.9):
+        """`pool_labels()` left in HBM."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, True, False)
+
+    def pooled_face_sums(self, source, face_weights=None):
+        """float32 [F,C]: every labelled face carries its segment's pooled row; an unlabelled face keeps its own row, unweighted."""
+        return self._pool(source, face_weights, _lib.VTX_SUMS, 0.0, False, False, True)
+
+    def pooled_face_annotations(self, source, face_weights=None, dont_care_threshold=0.9):
+        """float32 [F,C]: `pooled_face_sums()` renormalised; all-zero rows where the total is below `dont_care_threshold`."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, False, True)
+
+    def pooled_face_labels(self, source, face_weights=None, dont_care_threshold=0.9):
+        """int32 [F]: region voting -- every face of a segment takes the label of the segment's pooled row, -1 where don't care."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, False, True)
+
+    def pooled_face_sums_device(self, source, face_weights=None):
+        """`pooled_face_sums()` left in HBM."""
+        return self._pool(source, face_weights, _lib.VTX_SUMS, 0.0, False, True, True)
+
+    def pooled_face_annotations_device(self, source, face_weights=None, dont_care_threshold=0.9):
+        """`pooled_face_annotations()` left in HBM."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, False, True, True)
+
+    def pooled_face_labels_device(self, source, face_weights=None, dont_care_threshold=0.9):
+        """`pooled_face_labels()` left in HBM: a label table for `LabelRenderer`, `ConfusionMatrix.add*` and `PointTransfer`."""
+        return self._pool(source, face_weights, _lib.VTX_ANNOTATIONS, dont_care_threshold, True, True, True)
+
+    def _measure(self, measure, minimum, streams):
+        if isinstance(minimum, bool) or not isinstance(minimum, (int, float, np.integer, np.floating)):
+            raise ValueError("minimum must be a number, got %r" % (minimum,))
+        pm, mmem, keep = _dense_vector(measure, self.count, "measure", "one element per segment", self.device, streams)
+        if pm is None:
+            raise ValueError("measure is required")
+        return pm, mmem, keep, float(minimum)
+
+    def _despeckle_labels_by(self, measure, minimum, return_removed, on_device):
+        streams = []
+        pm, mmem, keep, minimum = self._measure(measure, minimum, streams)
+        out, ptr, mem = _out((self.num_faces,), np.int32, self.device, on_device)
+        faces, segs = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(_lib.lib().smesh_segment_stats_despeckle_labels(self._h, pm, mmem, minimum, ptr, mem,
+                                                                  ctypes.byref(faces) if return_removed else None,
+                                                                  ctypes.byref(segs) if return_removed else None))
+        release_to(self.device, streams)
+        return (out, int(faces.value), int(segs.value)) if return_removed else out
+
+    def despeckle_labels_by(self, measure, minimum, return_removed=False):
+        """int32 [F]: `despeckle_labels()` with "kept" meaning `measure[segment] >= minimum` -- `measure`: float32 [count], e.g.
+        `areas()` in square metres.  A NaN measure removes its segment.  `return_removed=True`: `(labels, removed faces, removed segments)`."""
+        return self._despeckle_labels_by(measure, minimum, return_removed, False)
+
+    def despeckle_labels_by_device(self, measure, minimum, return_removed=False):
+        """`despeckle_labels_by()` left in HBM."""
+        return self._despeckle_labels_by(measure, minimum, return_removed, True)
+
+    def _despeckle_sums_by(self, source, measure, minimum, on_device):
+        streams = []
+        pm, mmem, keep, minimum = self._measure(measure, minimum, streams)
+        src = _Source(source, self.num_faces, self.device, "the segments", "FaceSegments", streams)
+        out, ptr, mem = _out((self.num_faces, src.classes), np.float32, self.device, on_device)
+        if src.is_aggregator:
+            # (`_h`: the aggregator's deferred views are handed to the library first, as get() does)
+            _lib.check(_lib.lib().smesh_aggregator_segment_stats_despeckle(source._h, self._h, pm, mmem, minimum, ptr, mem))
+        else:
+            _lib.check(_lib.lib().smesh_segment_stats_despeckle_rows(self._h, pm, mmem, minimum, src.ptr, src.memkind, src.classes, ptr, mem))
+        src.finish()
+        return out
+
+    def despeckle_sums_by(self, source, measure, minimum):
+        """float32 [F,C]: `despeckle_sums()` with "kept" meaning `measure[segment] >= minimum`."""
+        return self._despeckle_sums_by(source, measure, minimum, False)
+
+    def despeckle_sums_by_device(self, source, measure, minimum):
+        """`despeckle_sums_by()` left in HBM: a `source` for `FaceGraph.fill_*`."""
+        return self._despeckle_sums_by(source, measure, minimum, True)
